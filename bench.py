@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- headline benchmark of the SeedVR2 hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg2|cfg1]
+    python bench.py --gpus N --steps K --warmup W [--workload cfg3|cfg2|cfg1] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints the result line (`value`, `ms_per_step`, phase times).
+--dump-outputs DIR also writes the frames of the last timed step as .npy (a fixed seeded sample of a large clip).  --full adds
+everything else this script measures or checks: per-launch kernel timing and the roofline (and --by-shape), the in-run MFMA
+calibration, the output guards, the CPU baseline (--no-cpu-baseline skips it), the a-priori prediction and per-rank statistics.
 
 A "step" is one pass of the hot path over one temporal batch of synthetic input already resident in
 HBM:  VAE encode -> one-step DiT (NaDiT-3B, 32 layers) -> VAE decode, i.e. exactly the three runner
@@ -331,6 +336,25 @@ def cpu_baseline(flops_per_frame: float) -> dict:
                       f"3B-width DiT on a 3x48x48 latent ({t_dit:.2f}s); extrapolated to the workload by algorithmic FLOPs"}
 
 
+DUMP_MAX_ELEMENTS = 1 << 23        # float32 elements --dump-outputs writes at most (32 MiB)
+
+
+def dump_outputs(out: torch.Tensor, dirname: str) -> None:
+    """--dump-outputs: the frames the last timed step returned, as DIR/frames.npy (float32, the output's shape) when they fit
+    DUMP_MAX_ELEMENTS, else DIR/frames_sample.npy: the values at DUMP_MAX_ELEMENTS flat positions drawn with torch.Generator seed 0
+    over the output's element count and sorted -- the same positions in every run with the same arguments, so that two builds can
+    be compared output for output."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    if out.numel() <= DUMP_MAX_ELEMENTS:
+        name, arr = "frames", out.float().cpu().numpy()
+    else:
+        idx = torch.randint(out.numel(), (DUMP_MAX_ELEMENTS,), generator=torch.Generator().manual_seed(0)).sort().values
+        name, arr = "frames_sample", out.reshape(-1)[idx.to(out.device)].float().cpu().numpy()
+    np.save(os.path.join(dirname, name + ".npy"), arr)
+    print(f"[bench] wrote {os.path.join(dirname, name + '.npy')} {list(arr.shape)} (output {list(out.shape)} {out.dtype})", file=sys.stderr)
+
+
 def respawn_under_torchrun(n: int) -> int:
     """`python bench.py --gpus N` without a launcher: run N ranks of this script on this node (one per GPU, RCCL)."""
     if "--cpu-double" not in sys.argv and (not torch.cuda.is_available() or torch.cuda.device_count() < n):
@@ -380,7 +404,16 @@ def main():
     ap.add_argument("--cpu-double", action="store_true",
                     help="TESTS ONLY (needs SVR_BENCH_ALLOW_CPU_DOUBLE=1): CPU ranks over gloo with the torch double of the C ABI and "
                          "reduced-width models -- exercises this script's launcher / gather / guard / JSON plumbing, measures nothing")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: per-kernel launch timing and the roofline, the in-run MFMA "
+                         "calibration, the output guards, the CPU baseline (unless --no-cpu-baseline), the a-priori prediction and the "
+                         "per-rank statistics of a multi-rank run.  Without it a run sets up, warms up, times --steps steps and prints")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the frames the last timed step computed to DIR as float32 .npy "
+                         "(all of them, or a fixed seeded sample when they exceed 32 MiB)")
     args = ap.parse_args()
+    if args.by_shape and not args.full:
+        ap.error("--by-shape times every launch: it needs --full")
     double = args.cpu_double
     if double and os.environ.get("SVR_BENCH_ALLOW_CPU_DOUBLE") != "1":
         print("[bench] --cpu-double is a test mode (tests/test_bench_launcher.py); the product path needs the HIP library and a GPU",
@@ -406,7 +439,8 @@ def main():
 
     config, weights, flops = sub("config"), sub("weights"), sub("flops")
     frames, H, W, tiled, desc = WORKLOADS[args.workload]
-    ops = make_double_ops() if double else make_profiled_ops(device)
+    full = args.full
+    ops = make_double_ops() if double else (make_profiled_ops(device) if full else sub("ops").HipOps(device))
     dcfg, vcfg = (config.DIT_7B if args.workload == "cfg5" else config.DIT_3B), config.VAE_V3
     if double:                                            # reduced width, same graphs: the plumbing is what runs here
         dcfg, vcfg = config.DIT_TINY, config.VAE_TINY
@@ -480,7 +514,7 @@ def main():
     first_print = None
     for _ in range(args.warmup):
         out, _ = step(False)
-        if first_print is None:
+        if full and first_print is None:
             first_print = fingerprint(out)
         del out
     sync()
@@ -490,11 +524,11 @@ def main():
     if world > 1:
         torch.distributed.barrier()
     cal = [None, None]
-    if not double:
+    if full and not double:
         cal[0] = ops.mfma_calibrate()
     if world > 1:
         torch.distributed.barrier()
-    ops.recording = True
+    ops.recording = full
     evs = []
     t0 = time.perf_counter()
     for _ in range(args.steps):
@@ -505,41 +539,45 @@ def main():
         torch.distributed.barrier()
     dt = time.perf_counter() - t0
     ops.recording = False
-    if not double:
+    if full and not double:
         cal[1] = ops.mfma_calibrate()
-    # ---- output guards (after the timed region): a kernel that exits early, or a launch that was dropped, must not post a record.
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last_out, args.dump_outputs)
+    # ---- output guards (--full; after the timed region): a kernel that exits early, or a launch that was dropped, must not post a record.
     # (1) every value of the last step's output is finite; (2) its statistics sit in the band the REFERENCE's decoder produces
     # with these synthetic weights (tests/golden/vae_tile1024.pt records mean / std / min / max of the reference's fp32 decode
     # at the real tile size: std 0.58, range about [-3.5, 3]); for the [0, 1] frames of the cfg4 pipeline the band is that of
     # clamped frames; (3) the hot path is deterministic, so the last timed step must reproduce the first warm-up step's
     # output sums bit for bit (same inputs).  On failure: no JSON line, exit code 3.
-    guard = {"finite": all(bool(torch.isfinite(c).all()) for c in (last_out.split(8, 0) if last_out.dim() > 1 else (last_out,)))}
-    fp_last = fingerprint(last_out)
-    n_el = last_out.numel()
-    g_mean, g_std = float(fp_last[0]) / n_el, math.sqrt(max(float(fp_last[1]) / n_el - (float(fp_last[0]) / n_el) ** 2, 0.0))
-    try:
-        gold = torch.load(os.path.join(ROOT, "tests", "golden", "vae_tile1024.pt"), weights_only=True)
-        ref_mean, ref_std = float(gold["dec_mean"]), float(gold["dec_std"])
-    except (OSError, KeyError):
-        ref_mean, ref_std = 0.0, 0.58
-    if double:
-        band_ok = True                                       # (reduced-width stand-in models: the band of the real decoder does not apply)
-    elif sharded:
-        band_ok = 0.05 <= g_std <= 0.6 and 0.2 <= g_mean <= 0.8          # [0, 1] frames after clamp and colour fix
-    else:
-        band_ok = 0.5 * ref_std <= g_std <= 2.0 * ref_std and abs(g_mean - ref_mean) <= ref_std
-    guard.update(mean=g_mean, std=g_std, band_ok=band_ok, reference_decode_mean=ref_mean, reference_decode_std=ref_std,
-                 deterministic=None if first_print is None else bool(torch.equal(first_print, fp_last)))
-    bad = (not guard["finite"]) or (not band_ok) or guard["deterministic"] is False
-    if world > 1:
-        flag = torch.tensor([int(bad)], device=device)
-        torch.distributed.all_reduce(flag)
-        bad = bool(flag.item())
-    if bad:
-        print(f"[bench] rank {rank}: output guard FAILED, refusing to report a number: {guard}", file=sys.stderr)
+    guard = None
+    if full:
+        guard = {"finite": all(bool(torch.isfinite(c).all()) for c in (last_out.split(8, 0) if last_out.dim() > 1 else (last_out,)))}
+        fp_last = fingerprint(last_out)
+        n_el = last_out.numel()
+        g_mean, g_std = float(fp_last[0]) / n_el, math.sqrt(max(float(fp_last[1]) / n_el - (float(fp_last[0]) / n_el) ** 2, 0.0))
+        try:
+            gold = torch.load(os.path.join(ROOT, "tests", "golden", "vae_tile1024.pt"), weights_only=True)
+            ref_mean, ref_std = float(gold["dec_mean"]), float(gold["dec_std"])
+        except (OSError, KeyError):
+            ref_mean, ref_std = 0.0, 0.58
+        if double:
+            band_ok = True                                       # (reduced-width stand-in models: the band of the real decoder does not apply)
+        elif sharded:
+            band_ok = 0.05 <= g_std <= 0.6 and 0.2 <= g_mean <= 0.8          # [0, 1] frames after clamp and colour fix
+        else:
+            band_ok = 0.5 * ref_std <= g_std <= 2.0 * ref_std and abs(g_mean - ref_mean) <= ref_std
+        guard.update(mean=g_mean, std=g_std, band_ok=band_ok, reference_decode_mean=ref_mean, reference_decode_std=ref_std,
+                     deterministic=None if first_print is None else bool(torch.equal(first_print, fp_last)))
+        bad = (not guard["finite"]) or (not band_ok) or guard["deterministic"] is False
         if world > 1:
-            torch.distributed.destroy_process_group()
-        sys.exit(3)
+            flag = torch.tensor([int(bad)], device=device)
+            torch.distributed.all_reduce(flag)
+            bad = bool(flag.item())
+        if bad:
+            print(f"[bench] rank {rank}: output guard FAILED, refusing to report a number: {guard}", file=sys.stderr)
+            if world > 1:
+                torch.distributed.destroy_process_group()
+            sys.exit(3)
     del last_out
     n_ranks = 1
     own_dt = dt
@@ -559,7 +597,7 @@ def main():
     # node that clocks all its GPUs down): every rank's phase times, own wall time and calibrated MFMA rate, gathered after the timing
     own = [own_dt / args.steps * 1e3, phase["encode"], phase["dit"], phase["decode"], phase["gather"], cal[0] or 0.0, cal[1] or 0.0]
     per_rank = [own]
-    if world > 1:
+    if full and world > 1:
         mine = torch.tensor(own, device=device, dtype=torch.float64)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         torch.distributed.all_gather(allr, mine)
@@ -583,54 +621,56 @@ def main():
             # through the DiT, the decoder skips it); `padded_frames_per_s` is the round-1/2 convention (all 33)
             frames_per_step = world * useful
             padded_per_step = world * frames
-        kern = ops.summary()
-        if args.by_shape and not double:
-            with open(args.by_shape, "w") as fh:
-                fh.write(ops.by_shape(args.steps))
-        # dominant kernel: the LDS-halo implicit-GEMM conv (63 % of the step, profiles/r3_cfg3_kernel_stats.csv) -- its launches
-        # ALONE (the thin-output / thin-input / sub-pixel / generic conv kernels are separate classes of `per_kernel`)
-        dom = kern.get("conv_halo") or kern.get("conv_generic") or kern.get("gemm_persistent") or kern["gemm"]
-        c_flops, c_sec, c_n = dom["flops"], dom["seconds"], dom["launches"]
-        traffic, traffic_note = None, None
-        shader_clock = None
-        for name in ("r6_cfg3_pmc_traffic.json", "r5_cfg3_pmc_traffic.json", "r4_cfg3_pmc_traffic.json", "r3_cfg3_pmc_traffic.json", "r2_cfg3_pmc_traffic.json",
-                     "r1_cfg3_pmc_traffic.json"):
-            # HBM bytes per launch come from separate rocprofv3 --pmc passes of this workload (counters cannot be collected
-            # inside the timed run); the file names the commit it was measured on
-            try:
-                pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
-                if pmc.get("workload") == "cfg3" and args.workload == "cfg3" and "conv_halo" in kern:
-                    krec = pmc["kernels"][pmc.get("dominant", "svr::conv_halo2_kernel")]
-                    traffic = krec["hbm_bytes_per_launch"]
-                    shader_clock = krec.get("shader_clock_ghz")
-                    traffic_note = f"bytes/launch, FETCH_SIZE*2 + WRITE_SIZE from profiles/{name}" + \
-                                   (f" (kernels as of {pmc['measured_at']})" if pmc.get("measured_at") else "")
-                    break
-            except (OSError, KeyError, ValueError):
-                continue
-        roof = {"bound": "mfma", "kernel": "svr::conv_halo2_kernel<16, 3> (LDS-halo implicit-GEMM causal Conv3d, register-streamed weights, 16x32-voxel patches x 128 couts, 8 rows x 64 couts per wave, 3x3 spatial taps)",
-                "achieved": c_flops / max(c_sec, 1e-12) / 1e12, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                "frac": c_flops / max(c_sec, 1e-12) / 1e12 / PEAK_BF16_TFLOPS, "traffic": traffic,
-                "traffic_note": traffic_note,
-                # effective shader clock of this kernel under load = GRBM_GUI_ACTIVE cycles / launch duration, from the same PMC
-                # passes (the chip is power-managed: nominal 2.4 GHz is what `peak` assumes)
-                "shader_clock_ghz": shader_clock,
-                "timing_note": ("HIP events on the launch stream; with tile_streams > 1 another tile's kernels share the chip while "
-                                "a launch runs, so durations include that overlap (--tile-streams 1 isolates the kernel)")
-                               if getattr(vae, "tile_streams", 1) > 1 else "HIP events on the launch stream",
-                # in-run calibration (svr_mfma_calibrate right before / after the timed region on this device): the bare-MFMA rate
-                # the power limit allows on random operands; `frac_of_power_limited` separates "this box clocks lower" from "the
-                # kernel got worse" inside the record itself (the nominal `frac` above cannot)
-                "power_limited_peak": None if cal[0] is None else {
-                    "tflops_before": cal[0], "tflops_after": cal[1], "tflops": min(cal), "unit": "TFLOP/s",
-                    "what": "bare v_mfma_f32_32x32x16_bf16 loop on random bf16 operands, 4 x 512 threads per CU, ~0.25 s, median of 3 "
-                            "(svr_mfma_calibrate), on this device in this run"},
-                "frac_of_power_limited": None if cal[0] is None else c_flops / max(c_sec, 1e-12) / 1e12 / min(cal),
-                "launches": c_n, "avg_launch_us": c_sec / max(c_n, 1) * 1e6,
-                "algorithmic_flops_per_launch": c_flops / max(c_n, 1),
-                "share_of_step_time": c_sec / max(dt, 1e-12),
-                "per_kernel": {k: {"launches": v["launches"], "avg_us": round(v["avg_us"], 2), "tflops": round(v["tflops"], 1)}
-                               for k, v in kern.items()}}
+        roof = None
+        if full:                     # (per-launch timing and the roofline: --full)
+            kern = ops.summary()
+            if args.by_shape and not double:
+                with open(args.by_shape, "w") as fh:
+                    fh.write(ops.by_shape(args.steps))
+            # dominant kernel: the LDS-halo implicit-GEMM conv (63 % of the step, profiles/r3_cfg3_kernel_stats.csv) -- its launches
+            # ALONE (the thin-output / thin-input / sub-pixel / generic conv kernels are separate classes of `per_kernel`)
+            dom = kern.get("conv_halo") or kern.get("conv_generic") or kern.get("gemm_persistent") or kern["gemm"]
+            c_flops, c_sec, c_n = dom["flops"], dom["seconds"], dom["launches"]
+            traffic, traffic_note = None, None
+            shader_clock = None
+            for name in ("r6_cfg3_pmc_traffic.json", "r5_cfg3_pmc_traffic.json", "r4_cfg3_pmc_traffic.json", "r3_cfg3_pmc_traffic.json", "r2_cfg3_pmc_traffic.json",
+                         "r1_cfg3_pmc_traffic.json"):
+                # HBM bytes per launch come from separate rocprofv3 --pmc passes of this workload (counters cannot be collected
+                # inside the timed run); the file names the commit it was measured on
+                try:
+                    pmc = json.load(open(os.path.join(ROOT, "profiles", name)))
+                    if pmc.get("workload") == "cfg3" and args.workload == "cfg3" and "conv_halo" in kern:
+                        krec = pmc["kernels"][pmc.get("dominant", "svr::conv_halo2_kernel")]
+                        traffic = krec["hbm_bytes_per_launch"]
+                        shader_clock = krec.get("shader_clock_ghz")
+                        traffic_note = f"bytes/launch, FETCH_SIZE*2 + WRITE_SIZE from profiles/{name}" + \
+                                       (f" (kernels as of {pmc['measured_at']})" if pmc.get("measured_at") else "")
+                        break
+                except (OSError, KeyError, ValueError):
+                    continue
+            roof = {"bound": "mfma", "kernel": "svr::conv_halo2_kernel<16, 3> (LDS-halo implicit-GEMM causal Conv3d, register-streamed weights, 16x32-voxel patches x 128 couts, 8 rows x 64 couts per wave, 3x3 spatial taps)",
+                    "achieved": c_flops / max(c_sec, 1e-12) / 1e12, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                    "frac": c_flops / max(c_sec, 1e-12) / 1e12 / PEAK_BF16_TFLOPS, "traffic": traffic,
+                    "traffic_note": traffic_note,
+                    # effective shader clock of this kernel under load = GRBM_GUI_ACTIVE cycles / launch duration, from the same PMC
+                    # passes (the chip is power-managed: nominal 2.4 GHz is what `peak` assumes)
+                    "shader_clock_ghz": shader_clock,
+                    "timing_note": ("HIP events on the launch stream; with tile_streams > 1 another tile's kernels share the chip while "
+                                    "a launch runs, so durations include that overlap (--tile-streams 1 isolates the kernel)")
+                                   if getattr(vae, "tile_streams", 1) > 1 else "HIP events on the launch stream",
+                    # in-run calibration (svr_mfma_calibrate right before / after the timed region on this device): the bare-MFMA rate
+                    # the power limit allows on random operands; `frac_of_power_limited` separates "this box clocks lower" from "the
+                    # kernel got worse" inside the record itself (the nominal `frac` above cannot)
+                    "power_limited_peak": None if cal[0] is None else {
+                        "tflops_before": cal[0], "tflops_after": cal[1], "tflops": min(cal), "unit": "TFLOP/s",
+                        "what": "bare v_mfma_f32_32x32x16_bf16 loop on random bf16 operands, 4 x 512 threads per CU, ~0.25 s, median of 3 "
+                                "(svr_mfma_calibrate), on this device in this run"},
+                    "frac_of_power_limited": None if cal[0] is None else c_flops / max(c_sec, 1e-12) / 1e12 / min(cal),
+                    "launches": c_n, "avg_launch_us": c_sec / max(c_n, 1) * 1e6,
+                    "algorithmic_flops_per_launch": c_flops / max(c_n, 1),
+                    "share_of_step_time": c_sec / max(dt, 1e-12),
+                    "per_kernel": {k: {"launches": v["launches"], "avg_us": round(v["avg_us"], 2), "tflops": round(v["tflops"], 1)}
+                                   for k, v in kern.items()}}
         family = "7B" if args.workload == "cfg5" else "3B"
         res = {
             "metric": "upscaled frames/sec (720p->4K, SeedVR2-3B)" if args.workload in ("cfg3", "cfg4")
@@ -652,14 +692,14 @@ def main():
             "algorithmic_tflop_per_step": f_step / 1e12,
             "executed_tflop_per_step": f_exec / 1e12,
             "achieved_tflops_per_gpu": f_exec * (1 if sharded else world) * args.steps / dt / 1e12 / world,
-            "roofline": roof,
             "vae_tile_streams": getattr(vae, "tile_streams", 1),
-            "output_guard": guard,
         }
+        if full:
+            res.update(roofline=roof, output_guard=guard)
         # DESIGN.md section 6's prediction for THIS launch, made falsifiable: the compute term is A PRIORI -- the committed 1-GPU line of
         # the same workload (profiles/), never this run's own timings -- plus the communication model (direct xGMI transfers at
         # ~64 GB/s per direction and link).  What this run measured is reported next to it, with the difference.
-        if world > 1 or sharded:
+        if full and (world > 1 or sharded):
             frame_bytes = H * W * 3 * (4 if sharded else 2)      # (the pipeline's frames are fp32, the runner's decode output bf16)
             one_gpu_s, src = None, None
             for name in ((f"r6_bench_{args.workload}_1gpu.json", f"r5_bench_{args.workload}_1gpu.json", f"r4_bench_{args.workload}_1gpu.json")
@@ -686,7 +726,7 @@ def main():
                                   "measured_per_step": dt / args.steps,
                                   "measured_minus_predicted_s": None if pred is None else dt / args.steps - pred,
                                   "own_run_compute_s_rank0": None if sharded else (phase["encode"] + phase["dit"] + phase["decode"]) / 1e3}
-        if world > 1:
+        if full and world > 1:
             cols = ("step_ms", "encode_ms", "dit_ms", "decode_ms", "gather_ms", "mfma_calibrated_tflops_before", "mfma_calibrated_tflops_after")
             stats = {}
             for j, cname in enumerate(cols):
@@ -707,7 +747,7 @@ def main():
         if double:
             res.update(test_mode=True, data="synthetic; TEST MODE (--cpu-double): torch double of the C ABI on CPU ranks over gloo, "
                                             "reduced-width models -- plumbing only, the numbers mean nothing")
-        if not args.no_cpu_baseline and world == 1 and not double:      # (the CPU leg is a 1-GPU line item: the other ranks would idle at the barrier)
+        if full and not args.no_cpu_baseline and world == 1 and not double:      # (the CPU leg is a 1-GPU line item: the other ranks would idle at the barrier)
             res["cpu_baseline"] = (cpu_baseline_cfg1() if args.workload == "cfg1" else
                                    cpu_baseline(f_step / frames_per_step * (world if not sharded else 1)))
         print(json.dumps(res))

@@ -75,6 +75,7 @@ def _start_measurement_build(config, items):
 
 
 def pytest_unconfigure(config):
+    _save_recorded()
     job = getattr(config, "_svr_measurement_build", None)
     if job is not None and job[0].poll() is None:              # (run interrupted before the test collected it: do not leave it behind)
         import signal
@@ -101,3 +102,60 @@ def golden_dir():
 def rel_err(a, b):
     a, b = a.double(), b.double()
     return float((a - b).norm() / b.norm().clamp_min(1e-30))
+
+
+# ------------------------------------------------------------------ recorded reference results
+# A test that compares against the reference's own code runs that code where it is available (oracle/reference_loader.py: the
+# checkout or oracle/_ref) and, everywhere else, compares against the results such a run recorded: tests/golden/recorded_<group>.pt,
+# written by `SVR_RECORD_REFERENCE=1 pytest ...` where the reference is available.  A result that was never recorded fails.
+RECORD = os.environ.get("SVR_RECORD_REFERENCE") == "1"
+_recorded, _recorded_dirty = {}, set()
+
+
+def _recorded_path(group):
+    return os.path.join(GOLDEN, f"recorded_{group}.pt")
+
+
+def _owned(value):
+    """Tensors cloned (a view would save its whole storage), containers rebuilt."""
+    import torch
+    if isinstance(value, torch.Tensor):
+        return value.detach().clone()
+    if isinstance(value, (list, tuple)):
+        return type(value)(_owned(v) for v in value)
+    if isinstance(value, dict):
+        return {k: _owned(v) for k, v in value.items()}
+    return value
+
+
+def recorded(group, key, live):
+    """The reference's result ``live()`` where the reference is available (stored when recording), else the recorded one."""
+    import torch
+    from oracle import reference_loader as rl
+    if group not in _recorded:
+        path = _recorded_path(group)
+        _recorded[group] = torch.load(path, weights_only=True) if os.path.exists(path) else {}
+    table = _recorded[group]
+    if rl.available():
+        value = live()
+        if RECORD:
+            table[key] = _owned(value)
+            _recorded_dirty.add(group)
+        return value
+    assert key in table, f"{key!r} is not recorded in {_recorded_path(group)}: record it where the reference is available (SVR_RECORD_REFERENCE=1)"
+    return table[key]
+
+
+def _save_recorded():
+    import torch
+    for group in sorted(_recorded_dirty):
+        torch.save(_recorded[group], _recorded_path(group))
+    _recorded_dirty.clear()
+
+
+def digest(t):
+    """Bit pattern, shape and dtype of a tensor as one string: bit-exact comparison with a recorded result too large to store."""
+    import hashlib
+    import torch
+    t = t.detach().contiguous().cpu()
+    return f"{tuple(t.shape)} {t.dtype} " + hashlib.sha256(t.reshape(-1).view(torch.uint8).numpy().tobytes()).hexdigest()

@@ -1,6 +1,6 @@
 """The reference's user-facing surface (SURVEY.md 8(b) "API surface to keep") against ours, by ``ast`` over the reference
-source where /root/reference is mounted: node ids, widget names / order / defaults / ranges / combo options
-(src/interfaces/*.py) and the inference_cli.py flag set with defaults, types, choices and actions
+source where it is available (elsewhere: what such a run recorded in tests/golden/recorded_api_surface.pt): node ids, widget
+names / order / defaults / ranges / combo options (src/interfaces/*.py) and the inference_cli.py flag set with defaults, types, choices and actions
 (inference_cli.py:1346-1481).  Plus offline checks that the shim builds its schemas and routes without ComfyUI."""
 import ast
 import importlib
@@ -10,10 +10,9 @@ import sys
 import pytest
 import torch
 
-from conftest import sub, ROOT
+from conftest import sub, ROOT, recorded
 from oracle import reference_loader as rl
 
-needs_ref = pytest.mark.skipif(not rl.available(), reason="/root/reference not mounted")
 REF = rl.REFERENCE_ROOT
 
 
@@ -71,9 +70,10 @@ def _compare(ours, ref, dynamic_ok=()):
             assert getattr(w, key) == want, (name, key, getattr(w, key), want)
 
 
-@needs_ref
-def test_node_widgets_equal_reference():
-    itf = sub("interfaces")
+def reference_surface():
+    """What the node test compares, read from the reference source: the model registry (names by category, default
+    models), the widgets of the four node schemas, the node ids its __init__ names, each node file's node_id / category
+    declaration and the parameter names / defaults of each execute()."""
     reg = ast.parse(open(os.path.join(REF, "src/utils/model_registry.py")).read())
     env = {}
     for node in reg.body:                                         # DEFAULT_DIT / DEFAULT_VAE string constants
@@ -82,35 +82,52 @@ def test_node_widgets_equal_reference():
     registry = next(n for n in reg.body if isinstance(n, ast.Assign) and getattr(n.targets[0], "id", "") == "MODEL_REGISTRY")
     names = [ast.literal_eval(k) for k in registry.value.keys]
     cats = [next((ast.literal_eval(kw.value) for kw in v.keywords if kw.arg == "category"), "dit") for v in registry.value.values]
-    assert itf.DIT_MODELS == [n for n, c in zip(names, cats) if c == "dit"]
-    assert itf.VAE_MODELS == [n for n, c in zip(names, cats) if c == "vae"]
-    assert (itf.DEFAULT_DIT, itf.DEFAULT_VAE) == (env["DEFAULT_DIT"], env["DEFAULT_VAE"])
-    env.update(dit_models=itf.DIT_MODELS, vae_models=itf.VAE_MODELS)
-    dyn = ("device", "offload_device")                            # device lists depend on the host
-    _compare(itf.upscaler_widgets(), reference_widgets("src/interfaces/video_upscaler.py", env), dyn)
-    _compare(itf.dit_loader_widgets(), reference_widgets("src/interfaces/dit_model_loader.py", env), dyn)
-    _compare(itf.vae_loader_widgets(), reference_widgets("src/interfaces/vae_model_loader.py", env), dyn)
-    _compare(itf.compile_widgets(), reference_widgets("src/interfaces/torch_compile_settings.py", env), dyn)
-    # node ids and the registry / entry point
-    init = open(os.path.join(REF, "src/interfaces/__init__.py")).read()
-    for node_id in itf.NODE_TABLE:
-        assert node_id in init and hasattr(itf, node_id)
-    for rel, node_id in (("video_upscaler.py", "SeedVR2VideoUpscaler"), ("dit_model_loader.py", "SeedVR2LoadDiTModel"),
-                         ("vae_model_loader.py", "SeedVR2LoadVAEModel"), ("torch_compile_settings.py", "SeedVR2TorchCompileSettings")):
+    surf = {"dit_models": [n for n, c in zip(names, cats) if c == "dit"], "vae_models": [n for n, c in zip(names, cats) if c == "vae"],
+            "defaults": (env["DEFAULT_DIT"], env["DEFAULT_VAE"])}
+    env.update(dit_models=surf["dit_models"], vae_models=surf["vae_models"])
+    surf["widgets"] = {rel: reference_widgets(f"src/interfaces/{rel}", env) for rel in NODE_FILES}
+    init = ast.parse(open(os.path.join(REF, "src/interfaces/__init__.py")).read())
+    surf["init_names"] = sorted({n.id for n in ast.walk(init) if isinstance(n, ast.Name)} |
+                                {a.name for n in ast.walk(init) if isinstance(n, ast.ImportFrom) for a in n.names} |
+                                {n.value for n in ast.walk(init) if isinstance(n, ast.Constant) and str(n.value).isidentifier()})
+    surf["declares"], surf["execute"] = {}, {}
+    for rel, node_id in NODE_FILES.items():
         src = open(os.path.join(REF, "src/interfaces", rel)).read()
-        assert f'node_id="{node_id}"' in src and 'category="SEEDVR2"' in src
+        surf["declares"][rel] = f'node_id="{node_id}"' in src and 'category="SEEDVR2"' in src
+        fn = next(n for n in ast.walk(ast.parse(src)) if isinstance(n, ast.FunctionDef) and n.name == "execute")
+        surf["execute"][rel] = ([a.arg for a in fn.args.args][1:], [ast.literal_eval(d) for d in fn.args.defaults])
+    return surf
+
+
+NODE_FILES = {"video_upscaler.py": "SeedVR2VideoUpscaler", "dit_model_loader.py": "SeedVR2LoadDiTModel",
+              "vae_model_loader.py": "SeedVR2LoadVAEModel", "torch_compile_settings.py": "SeedVR2TorchCompileSettings"}
+
+
+def test_node_widgets_equal_reference():
+    itf = sub("interfaces")
+    ref = recorded("api_surface", "nodes", reference_surface)
+    assert itf.DIT_MODELS == ref["dit_models"]
+    assert itf.VAE_MODELS == ref["vae_models"]
+    assert (itf.DEFAULT_DIT, itf.DEFAULT_VAE) == tuple(ref["defaults"])
+    dyn = ("device", "offload_device")                            # device lists depend on the host
+    _compare(itf.upscaler_widgets(), ref["widgets"]["video_upscaler.py"], dyn)
+    _compare(itf.dit_loader_widgets(), ref["widgets"]["dit_model_loader.py"], dyn)
+    _compare(itf.vae_loader_widgets(), ref["widgets"]["vae_model_loader.py"], dyn)
+    _compare(itf.compile_widgets(), ref["widgets"]["torch_compile_settings.py"], dyn)
+    # node ids and the registry / entry point
+    for node_id in itf.NODE_TABLE:
+        assert node_id in ref["init_names"] and hasattr(itf, node_id)
+    for rel in NODE_FILES:
+        assert ref["declares"][rel], rel
     # execute() signatures: same parameter names and defaults
     for rel, cls in (("video_upscaler.py", itf.SeedVR2VideoUpscaler), ("dit_model_loader.py", itf.SeedVR2LoadDiTModel),
                      ("vae_model_loader.py", itf.SeedVR2LoadVAEModel), ("torch_compile_settings.py", itf.SeedVR2TorchCompileSettings)):
-        tree = ast.parse(open(os.path.join(REF, "src/interfaces", rel)).read())
-        fn = next(n for n in ast.walk(tree) if isinstance(n, ast.FunctionDef) and n.name == "execute")
-        args = [a.arg for a in fn.args.args][1:]
-        defaults = [ast.literal_eval(d) for d in fn.args.defaults]
+        args, defaults = ref["execute"][rel]
         import inspect
         sig = inspect.signature(cls.execute)
-        assert list(sig.parameters) == args, (rel, list(sig.parameters), args)
+        assert list(sig.parameters) == list(args), (rel, list(sig.parameters), args)
         ours_defaults = [p.default for p in sig.parameters.values() if p.default is not inspect.Parameter.empty]
-        assert ours_defaults == defaults, (rel, ours_defaults, defaults)
+        assert ours_defaults == list(defaults), (rel, ours_defaults, defaults)
 
 
 def reference_cli_flags():
@@ -130,7 +147,6 @@ def reference_cli_flags():
     return flags
 
 
-@needs_ref
 def test_cli_flags_equal_reference():
     sys.path.insert(0, ROOT)
     cli = importlib.import_module("inference_cli")
@@ -141,7 +157,7 @@ def test_cli_flags_equal_reference():
             continue
         key = a.option_strings[0] if a.option_strings else a.dest
         ours[key] = a
-    ref = reference_cli_flags()
+    ref = recorded("api_surface", "cli_flags", reference_cli_flags)
     assert set(ours) == set(ref), (sorted(set(ref) - set(ours)), sorted(set(ours) - set(ref)))
     for key, kw in ref.items():
         a = ours[key]

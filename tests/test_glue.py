@@ -1,7 +1,8 @@
 """Phase glue (transforms.py, colorfix.py, pipeline.py): host/device plumbing checked on CPU.
 
-* against the reference's own function text where /root/reference is mounted (compiled unmodified by
-  oracle/reference_loader.reference_glue()) -- bit-exact for index/padding logic, <= 1e-6 for fp32 colour maths;
+* against the reference's own function text (compiled unmodified by oracle/reference_loader.reference_glue()) where it is
+  available, elsewhere against its results recorded in tests/golden/recorded_glue.pt / recorded_colorfix.pt (conftest.recorded)
+  -- bit-exact for index/padding logic, <= 1e-6 for fp32 colour maths;
 * size-independent properties everywhere (4n+1 lengths, mirror structure, blend weights, batch plans cover
   every frame once, an identity runner reproduces the transformed input through all four phases).
 """
@@ -10,19 +11,16 @@ import math
 import pytest
 import torch
 
-from conftest import sub
+from conftest import digest, recorded, sub
 from oracle import reference_loader as rl
-
-needs_ref = pytest.mark.skipif(not rl.available(), reason="/root/reference not mounted")
 
 
 @pytest.fixture(scope="module")
 def ref():
-    return rl.reference_glue()
+    return rl.reference_glue() if rl.available() else None
 
 
 # ------------------------------------------------------------------ temporal padding / blending
-@needs_ref
 @pytest.mark.parametrize("t,count,dim,prepend", [(5, 0, 0, False), (6, 0, 1, False), (8, 0, 0, False), (2, 0, 1, False),
                                                  (1, 0, 0, False), (7, 3, 0, True), (3, 5, 0, True), (3, 7, 1, False),
                                                  (1, 4, 0, False), (9, 2, 1, True)])
@@ -30,7 +28,8 @@ def test_pad_video_temporal_equals_reference(ref, t, count, dim, prepend):
     tr = sub("transforms")
     shape = (t, 3, 4, 5) if dim == 0 else (3, t, 4, 5)
     x = torch.arange(math.prod(shape), dtype=torch.float32).reshape(shape)
-    want = ref["pad_video_temporal"](x, count=count, temporal_dim=dim, prepend=prepend)
+    want = recorded("glue", f"pad/{t},{count},{dim},{prepend}",
+                    lambda: ref["pad_video_temporal"](x, count=count, temporal_dim=dim, prepend=prepend))
     assert torch.equal(tr.pad_video_temporal(x, count=count, temporal_dim=dim, prepend=prepend), want)
 
 
@@ -45,32 +44,36 @@ def test_4n1_padding_properties(t):
         assert pad == [float(t - 2 - i) for i in range(len(pad))]
 
 
-@needs_ref
 @pytest.mark.parametrize("overlap", [1, 2, 3, 4, 7])
 def test_blend_equals_reference(ref, overlap):
     tr = sub("transforms")
     g = torch.Generator().manual_seed(overlap)
     a, b = torch.rand(overlap, 6, 5, 3, generator=g), torch.rand(overlap, 6, 5, 3, generator=g)
-    assert torch.equal(tr.blend_overlapping_frames(a, b, overlap), ref["blend_overlapping_frames"](a, b, overlap))
+    want = recorded("glue", f"blend/{overlap}", lambda: ref["blend_overlapping_frames"](a, b, overlap))
+    assert torch.equal(tr.blend_overlapping_frames(a, b, overlap), want)
     assert torch.allclose(tr.blend_overlapping_frames(a, a, overlap), a, atol=1e-6)      # weights sum to one
 
 
 # ------------------------------------------------------------------ input transform
-@needs_ref
 @pytest.mark.parametrize("h,w,res,mx", [(120, 212, 256, 0), (478, 320, 400, 0), (90, 160, 720, 1000), (64, 64, 100, 0),
                                          (100, 37, 64, 150)])
 def test_video_transform_equals_reference(ref, h, w, res, mx):
     tr = sub("transforms")
     g = torch.Generator().manual_seed(h + w)
     x = torch.rand(3, 3, h, w, generator=g)
-    want = ref["SideResize"](size=res, max_size=mx)(x)
+
+    def live():
+        resized = ref["SideResize"](size=res, max_size=mx)(x)
+        padded = ref["DivisiblePad"]((16, 16))(torch.clamp(resized, 0.0, 1.0))
+        return {"shape": tuple(resized.shape), "resized": digest(resized), "full": digest(((padded - 0.5) / 0.5).permute(1, 0, 2, 3))}
+
+    want = recorded("glue", f"video_transform/{h},{w},{res},{mx}", live)
     got = tr.side_resize(x, res, mx)
-    assert got.shape == want.shape and torch.equal(got, want)
+    assert tuple(got.shape) == want["shape"] and digest(got) == want["resized"]
     th, tw = tr.true_target_dims(h, w, res, mx)
-    assert (th, tw) == ((want.shape[-2] // 2) * 2, (want.shape[-1] // 2) * 2)
-    padded = ref["DivisiblePad"]((16, 16))(torch.clamp(want, 0.0, 1.0))
+    assert (th, tw) == ((want["shape"][-2] // 2) * 2, (want["shape"][-1] // 2) * 2)
     full = tr.video_transform(x, res, mx)
-    assert torch.equal(full, ((padded - 0.5) / 0.5).permute(1, 0, 2, 3))
+    assert digest(full) == want["full"]
     assert full.shape[-1] % 16 == 0 and full.shape[-2] % 16 == 0 and float(full.min()) >= -1 and float(full.max()) <= 1
 
 
@@ -83,30 +86,32 @@ def test_resized_output_size_matches_interpolate_shapes():
 
 
 # ------------------------------------------------------------------ colour correction
-@needs_ref
 @pytest.mark.parametrize("method", ["adain", "wavelet", "lab", "hsv", "wavelet_adaptive"])
 def test_colorfix_equals_reference(ref, method):
     cf = sub("colorfix")
     g = torch.Generator().manual_seed(7)
     content = (torch.rand(2, 3, 48, 72, generator=g) * 2 - 1) * 0.9
     style = (torch.rand(2, 3, 48, 72, generator=g) * 2 - 1) * 0.6 + 0.1
+
+    class _Dbg:
+        def log(self, *a, **k):
+            pass
+
     if method in ("hsv", "wavelet_adaptive"):
-        class _Dbg:
-            def log(self, *a, **k):
-                pass
         content[:, :, :8, :8] = 0.3                     # grey block: the zero-range (hue 0, saturation 0) branch
         content[:, 0, 8:16] = content[:, 1, 8:16]       # r == g ties
-        fn = ref["hsv_saturation_histogram_match" if method == "hsv" else "wavelet_adaptive_color_correction"]
-        want = fn(content.clone(), style.clone(), _Dbg())
-    elif method == "adain":
-        want = ref["adaptive_instance_normalization"](content.clone(), style.clone())
-    elif method == "wavelet":
-        want = ref["wavelet_reconstruction"](content.clone(), style.clone())
-    else:
-        class _Dbg:
-            def log(self, *a, **k):
-                pass
-        want = ref["lab_color_transfer"](content.clone(), style.clone(), _Dbg(), luminance_weight=0.8)
+
+    def live():
+        if method in ("hsv", "wavelet_adaptive"):
+            fn = ref["hsv_saturation_histogram_match" if method == "hsv" else "wavelet_adaptive_color_correction"]
+            return fn(content.clone(), style.clone(), _Dbg())
+        if method == "adain":
+            return ref["adaptive_instance_normalization"](content.clone(), style.clone())
+        if method == "wavelet":
+            return ref["wavelet_reconstruction"](content.clone(), style.clone())
+        return ref["lab_color_transfer"](content.clone(), style.clone(), _Dbg(), luminance_weight=0.8)
+
+    want = recorded("colorfix", method, live)
     got = cf.METHODS[method](content, style)
     assert got.shape == want.shape
     if method != "lab":
@@ -116,15 +121,41 @@ def test_colorfix_equals_reference(ref, method):
     # 3x3 conv evaluated as two three-tap passes (same weights, another order of fp32 additions: <= 2e-6, the "wavelet"
     # case above), so a few near-tied pixels swap ranks and exchange their matched values.  Hence: (a) everything after
     # the blur is exact when it is given the reference's wavelet base, (b) composed, all but a handful of values agree.
+    # (Without the reference: its wavelet base for the inputs this code hands it, as recorded -- the inputs are checked.)
+    if ref is not None:
+        calls = []
+
+        def wavelet(c, s):
+            out = ref["wavelet_reconstruction"](c.clone(), s.clone(), _Dbg())
+            calls.append((c.clone(), s.clone(), out))
+            return out
+    else:
+        calls = list(recorded("colorfix", "lab/wavelet_calls", None))
+
+        def wavelet(c, s):
+            rc, rs, out = calls.pop(0)
+            assert torch.allclose(c, rc, rtol=1e-6, atol=2e-6) and torch.allclose(s, rs, rtol=1e-6, atol=2e-6)
+            return out
     monkey = pytest.MonkeyPatch()
     try:
-        monkey.setattr(cf, "wavelet_reconstruction", lambda c, s: ref["wavelet_reconstruction"](c.clone(), s.clone(), _Dbg()))
+        monkey.setattr(cf, "wavelet_reconstruction", wavelet)
         staged = cf.lab_color_transfer(content, style, luminance_weight=0.8)
     finally:
         monkey.undo()
-    assert float((staged - want).abs().max()) < 2e-6
-    d = (got - want).abs()
-    assert float((d > 2e-6).float().mean()) < 5e-3 and float(d.max()) < 1e-3
+    if ref is not None:
+        recorded("colorfix", "lab/wavelet_calls", lambda: calls)
+        tol = 2e-6
+    else:
+        assert not calls
+        # a recorded result may come from another host: the colour-space conversions' transcendental functions are vectorised
+        # differently from one CPU to another (3.8e-5 measured between two x86 hosts), so the "exact" bar becomes that of such
+        # ulp-level differences
+        tol = 1e-4
+    d_staged, d = (staged - want).abs(), (got - want).abs()
+    print(f"lab: staged max {float(d_staged.max()):.2e}; composed max {float(d.max()):.2e}, share above {tol:g}: "
+          f"{float((d > tol).float().mean()):.2e}")
+    assert float(d_staged.max()) < tol
+    assert float((d > tol).float().mean()) < 5e-3 and float(d.max()) < 1e-3
 
 
 def test_colorfix_properties():

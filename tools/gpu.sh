@@ -6,8 +6,8 @@
 #   variants             pytest -m variants (non-default kernel generations)
 #   smoke                __graft_entry__.smoke()
 #   kbench[:<only>[:<SVR_OPTIONS>]]   tools/kbench.py --only <only>
-#   bench[:<workload>[:<extra args, '+' for spaces>]]   bench.py --steps 2 --warmup 1 (no cpu baseline)
-#   benchfull[:<workload>]  bench.py with its defaults (the driver's line)
+#   bench[:<workload>[:<extra args, '+' for spaces>]]   bench.py --full --steps 2 --warmup 1 (no cpu baseline)
+#   benchfull[:<workload>]  bench.py --full with its other defaults (the driver's line and every figure behind --full)
 #   prof[:<workload>]    rocprofv3 --kernel-trace --stats of a 2-step bench -> gpurun_out/<tag>_prof_kernel_stats.csv
 #   pmc[:<workload>]     separate --pmc passes (FETCH_SIZE / WRITE_SIZE / MFMA busy / L2) of a 1-step bench
 #   trace[:<only>]       rocprofv3 --kernel-trace --stats of tools/kbench.py --only <only>
@@ -26,9 +26,9 @@ for step in "$@"; do
     variants) timeout 900 python -m pytest tests -q -m variants -p no:cacheprovider > $log 2>&1; rc=$?; tail -4 $log ;;
     smoke)    timeout 600 python __graft_entry__.py smoke > $log 2>&1; rc=$?; tail -5 $log ;;
     kbench)   SVR_OPTIONS=${b:-} timeout 600 python tools/kbench.py --reps 5 --only ${a:-conv,gemm,attn,side} > $log 2> $log.err; rc=$?; cat $log ;;
-    bench)    timeout 1500 python bench.py --workload ${a:-cfg3} --steps 2 --warmup 1 --no-cpu-baseline ${b//+/ } > $log 2> $log.err; rc=$?
+    bench)    timeout 1500 python bench.py --full --workload ${a:-cfg3} --steps 2 --warmup 1 --no-cpu-baseline ${b//+/ } > $log 2> $log.err; rc=$?
               cut -c1-1500 $log; tail -2 $log.err ;;
-    benchfull) timeout 1500 python bench.py --workload ${a:-cfg3} > $log 2> $log.err; rc=$?; cat $log; tail -2 $log.err ;;
+    benchfull) timeout 1500 python bench.py --full --workload ${a:-cfg3} > $log 2> $log.err; rc=$?; cat $log; tail -2 $log.err ;;
     prof)     d=gpurun_out/${TAG}_prof; rm -rf $d
               timeout 1500 rocprofv3 --kernel-trace --stats -d $d -o prof --output-format csv -- python bench.py --workload ${a:-cfg3} --steps 2 --warmup 1 --no-cpu-baseline > $log 2>&1; rc=$?
               f=$(find $d -name '*kernel_stats.csv' | head -1); [ -n "$f" ] && cp $f gpurun_out/${TAG}_prof_kernel_stats.csv && head -25 $f
