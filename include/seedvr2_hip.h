@@ -189,7 +189,10 @@ int svr_ada_combine(const void* emb, const void* params, const int32_t* slot, fl
 /* In-place q/k RMSNorm(head_dim, affine) + 3-axis interleaved-pair RoPE on a packed qkv buffer.
  * mmattn.py:207-208 + rope.py:118-126,172-173.  qkv bf16 [rows, 3*heads*128]; pos int16 [rows,3];
  * cs fp32 [n_pos, 2, 63] = cos|sin(pos * freq) table per axis is folded on the host into one
- * table indexed by position; wq,wk fp32 [128]; t_offset is added to pos[:,0] (text length).     */
+ * table indexed by position; wq,wk fp32 [128]; t_offset is added to pos[:,0] (text length).
+ * Every table row index -- pos[:,0] + t_offset, pos[:,1], pos[:,2] -- is CLAMPED to [0, n_pos - 1]: a position outside
+ * the table takes the first / last row's cos | sin, it is never read out of bounds and never an error.
+ * Pairs 3 * n_freq .. 63 of a head vector are normalised and pass through unrotated.                 */
 int svr_qknorm_rope(void* qkv, int64_t rows, int32_t heads, const int16_t* pos, int32_t t_offset,
                     const float* cos_tab, const float* sin_tab, int32_t n_pos, int32_t n_freq,
                     const float* wq, const float* wk, float eps, void* stream);
@@ -229,7 +232,9 @@ int svr_groupnorm_stats(const void* x, double* stats, void* workspace, int32_t T
 /* stats[t][g] = fixed-order sum over the `nblk` block partials [T][nblk][groups] (fp64 pairs) written by
  * svr_groupnorm_stats' first stage or by a conv launch with gn_partial set.                           */
 int svr_groupnorm_reduce(const void* partial, double* stats, int32_t T, int32_t nblk, int32_t groups, void* stream);
-/* y = [silu](gamma * (x - mean) * rstd + beta); x bf16 (fp32 if x_f32), y bf16.  attn_video_vae.py:316-323,343-350. */
+/* y = [silu](gamma * (x - mean) * rstd + beta); x bf16 (fp32 if x_f32), y bf16.  attn_video_vae.py:316-323,343-350.
+ * Any C % 8 == 0, C <= 512 with groups dividing C -- a superset of what svr_groupnorm_stats serves (C / 8 dividing 256):
+ * for the other C (24, 192, 320, ...) the caller brings statistics of its own.                                          */
 int svr_groupnorm_apply(const void* x, void* y, const double* stats, const float* gamma, const float* beta,
                         int32_t T, int64_t HW, int32_t C, int32_t groups, float eps, int32_t apply_silu,
                         int32_t x_f32, void* stream);

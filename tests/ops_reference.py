@@ -30,6 +30,83 @@ def _st(values, like):
 EPI_BIAS, EPI_BIAS_SILU, EPI_RESID_GATE, EPI_SWIGLU, EPI_BIAS_GELU = 0, 1, 2, 3, 4
 
 
+def conv_padded_input(A, conv, dtype=torch.float32):
+    """The input a causal conv launch reads, as [1, Cin, T + pt, H + pads, W + pads] in ``dtype``: the carried halo frames (or
+    the first frame repeated) in front, zeros on the spatial borders.  Shared by the fp32 restatement below and the fp64
+    reference of tests/local_error.py, so the two cannot pad differently."""
+    g = conv
+    x = A.reshape(g.T, g.H, g.W, g.Cin).to(dtype)
+    pt, ph, pw = g.pad
+    kt, kh, kw = g.k
+    st, sh, sw = g.stride
+    if pt > 0:
+        head = g.halo.to(dtype)[-pt:] if g.halo is not None else x[:1].expand(pt, g.H, g.W, g.Cin)
+        x = torch.cat([head, x], dim=0)
+    xin = x.permute(3, 0, 1, 2).unsqueeze(0)                            # [1, C, T, H, W]
+    ph_hi = max(0, (g.Ho - 1) * sh + kh - g.H - ph)
+    pw_hi = max(0, (g.Wo - 1) * sw + kw - g.W - pw)
+    return F.pad(xin, (pw, pw_hi, ph, ph_hi))
+
+
+def gemm_acc(A, W, *, N, K, M=None, conv=None, dtype=torch.float32):
+    """A[M, K] @ W[:N, :K]^T (or the implicit-GEMM conv) before any epilogue, [M, N] in ``dtype``."""
+    Wf = W[:N, :K].to(dtype)
+    if conv is None:
+        if M is None:
+            M = A.shape[0]
+        return A.reshape(-1, A.shape[-1])[:M, :K].to(dtype) @ Wf.t()
+    g = conv
+    kt, kh, kw = g.k
+    xin = conv_padded_input(A, g, dtype)
+    w5 = Wf[:, :kt * kh * kw * g.Cin].reshape(N, kt, kh, kw, g.Cin).permute(0, 4, 1, 2, 3)   # (thin: K zero-padded)
+    try:
+        y = F.conv3d(xin, w5, stride=tuple(g.stride))[0]                   # [N, To', Ho', Wo']
+    except RuntimeError:
+        if dtype != torch.float64 or xin.device.type == "cpu":
+            raise
+        y = F.conv3d(xin.cpu(), w5.cpu(), stride=tuple(g.stride))[0].to(xin.device)   # (a device backend without fp64 convs)
+    y = y[:, :g.To, :g.Ho, :g.Wo]
+    assert y.shape[1:] == (g.To, g.Ho, g.Wo), (y.shape, g)
+    return y.permute(1, 2, 3, 0).reshape(-1, N)
+
+
+def gemm_bias_rows(bias, N, conv, phase, dtype, device):
+    """The bias each output row takes: [N], or [M, N] where a phase launch gives its border voxels their own bias vectors."""
+    b = bias[:N].to(dtype) if bias is not None else torch.zeros(N, dtype=dtype, device=device)
+    if phase is None or phase.bias_border is None:
+        return b
+    g = conv
+    b4 = b.expand(g.To, g.Ho, g.Wo, N).clone()
+    yb = g.Ho - 1 if phase.py else 0
+    xb = g.Wo - 1 if phase.px else 0
+    bb = phase.bias_border.to(dtype)
+    b4[:, yb, :, :] = bb[0]
+    b4[:, :, xb, :] = bb[1]
+    b4[:, yb, xb, :] = bb[2]
+    return b4.reshape(-1, N)
+
+
+def gemm_place(res, out, *, conv=None, ps=None, phase=None):
+    """Write the launch's [M, N'] results where the launch writes them in ``out`` (pure index maps: phase scatter, pixel
+    shuffle with drop_first, or the leading columns of the rows); every other element of ``out`` is left alone."""
+    M, n = res.shape
+    if phase is not None:
+        g = conv
+        ts = getattr(phase, "t_stride", 1)
+        o4 = out.reshape(-1, 2 * g.Ho, 2 * g.Wo, n)
+        o4[0:(g.To - 1) * ts + 1:ts, phase.py::2, phase.px::2, :] = res.reshape(g.To, g.Ho, g.Wo, n)
+    elif ps is not None:
+        r = res.reshape(ps.F, ps.H, ps.W, 2, 2, ps.rz, ps.C).permute(0, 5, 1, 3, 2, 4, 6)
+        r = r.reshape(ps.F * ps.rz, 2 * ps.H, 2 * ps.W, ps.C)
+        if ps.drop_first:
+            r = torch.cat([r[:1], r[2:]], dim=0)
+        out.copy_(r.reshape(out.shape))
+    else:
+        out.reshape(M, -1)[:, :n].copy_(res)
+    return out
+
+
+
 class TorchOps:
     name = "torch-reference"
     phase_quad = True
@@ -55,48 +132,15 @@ class TorchOps:
         if gn_groups > 0:
             return self.gemm(A, W, out, N=N, K=K, M=M, bias=bias, epilogue=epilogue, gate=gate, resid=resid,
                              out_f32=out_f32, conv=conv, ps=ps, lda=lda, ldc=ldc, ldr=ldr, phase=phase), None
-        Wf = W[:N, :K].float()
-        if conv is not None:
-            g = conv
-            x = A.reshape(g.T, g.H, g.W, g.Cin).float()
-            pt, ph, pw = g.pad
-            kt, kh, kw = g.k
-            st, sh, sw = g.stride
-            if pt > 0:
-                head = g.halo.float()[-pt:] if g.halo is not None else x[:1].expand(pt, g.H, g.W, g.Cin)
-                x = torch.cat([head, x], dim=0)
-            xin = x.permute(3, 0, 1, 2).unsqueeze(0)                            # [1, C, T, H, W]
-            ph_hi = max(0, (g.Ho - 1) * sh + kh - g.H - ph)
-            pw_hi = max(0, (g.Wo - 1) * sw + kw - g.W - pw)
-            xin = F.pad(xin, (pw, pw_hi, ph, ph_hi))
-            w5 = Wf[:, :kt * kh * kw * g.Cin].reshape(N, kt, kh, kw, g.Cin).permute(0, 4, 1, 2, 3)   # (thin: K zero-padded)
-            y = F.conv3d(xin, w5, stride=(st, sh, sw))[0]                       # [N, To', Ho', Wo']
-            y = y[:, :g.To, :g.Ho, :g.Wo]
-            assert y.shape[1:] == (g.To, g.Ho, g.Wo), (y.shape, g)
-            acc = y.permute(1, 2, 3, 0).reshape(-1, N)
-            M = acc.shape[0]
-        else:
-            if M is None:
-                M = A.shape[0]
-            acc = A.reshape(-1, A.shape[-1])[:M, :K].float() @ Wf.t()
+        acc = gemm_acc(A, W, N=N, K=K, M=M, conv=conv, dtype=torch.float32)
+        M = acc.shape[0]
         if epilogue == EPI_SWIGLU:
             a4 = acc.reshape(M, N // 32, 2, 16)
             res = (F.silu(a4[:, :, 0]) * a4[:, :, 1]).reshape(M, N // 2)
         else:
             res = acc
-            if bias is not None:
-                res = res + bias[:N].float()
-            if phase is not None and phase.bias_border is not None:      # border voxels take their own bias vector
-                g = conv
-                r4 = res.reshape(g.To, g.Ho, g.Wo, N).clone()
-                a4 = acc.reshape(g.To, g.Ho, g.Wo, N)
-                yb = g.Ho - 1 if phase.py else 0
-                xb = g.Wo - 1 if phase.px else 0
-                bb = phase.bias_border.float()
-                r4[:, yb, :, :] = a4[:, yb, :, :] + bb[0]
-                r4[:, :, xb, :] = a4[:, :, xb, :] + bb[1]
-                r4[:, yb, xb, :] = a4[:, yb, xb, :] + bb[2]
-                res = r4.reshape(-1, N)
+            if bias is not None or (phase is not None and phase.bias_border is not None):
+                res = res + gemm_bias_rows(bias, N, conv, phase, torch.float32, acc.device)
             if epilogue == EPI_BIAS_GELU:
                 res = F.gelu(res, approximate="tanh")
             elif epilogue == EPI_BIAS_SILU:
@@ -106,20 +150,7 @@ class TorchOps:
                     res = res * gate[:N].float()
                 if resid is not None:
                     res = res + _ld(resid.reshape(M, -1)[:, :N])
-        if phase is not None:
-            g = conv
-            ts = getattr(phase, "t_stride", 1)
-            o4 = out.reshape(-1, 2 * g.Ho, 2 * g.Wo, N)
-            o4[0:(g.To - 1) * ts + 1:ts, phase.py::2, phase.px::2, :] = _st(res.reshape(g.To, g.Ho, g.Wo, N), out)
-            return out
-        if ps is not None:
-            r = res.reshape(ps.F, ps.H, ps.W, 2, 2, ps.rz, ps.C).permute(0, 5, 1, 3, 2, 4, 6)
-            r = r.reshape(ps.F * ps.rz, 2 * ps.H, 2 * ps.W, ps.C)
-            if ps.drop_first:
-                r = torch.cat([r[:1], r[2:]], dim=0)
-            out.copy_(_st(r.reshape(out.shape), out))
-            return out
-        out.reshape(M, -1)[:, :res.shape[1]].copy_(_st(res, out))
+        gemm_place(_st(res, out), out, conv=conv, ps=ps, phase=phase)
         return out
 
     # ------------------------------------------------------------------ DiT side kernels

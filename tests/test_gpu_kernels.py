@@ -12,6 +12,7 @@ import math
 import pytest
 import torch
 
+import local_error as le
 from conftest import sub, rel_err
 from ops_reference import TorchOps, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_RESID_GATE, EPI_SWIGLU
 
@@ -67,6 +68,7 @@ def test_gemm_bias(hip, ref, gemm_epi, M, N, K, out_f32):
     hip.gemm(A, W, out, N=N, K=K, bias=bias, out_f32=out_f32)
     want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias)
     assert rel_err(out.float(), want) < (TOL_F32 if out_f32 else TOL_BF16)
+    le.check_gemm(out, A, W, N=N, K=K, bias=bias)
 
 
 def test_gemm_race_screen(hip, ref):
@@ -111,19 +113,22 @@ def test_gemm_epilogues(hip, ref, gemm_epi):
         hip.gemm(A, W, out, N=N, K=K, bias=bias, epilogue=epi, **kw)
         want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=epi, **kw)
         assert rel_err(out.float(), want) < TOL_BF16, epi
+        le.check_gemm(out, A, W, N=N, K=K, bias=bias, epilogue=epi, name=f"epilogue {epi} {sorted(kw)} bf16", **kw)
     # fp32-store test epilogue: the north star's 1e-3 bound, per fused epilogue (same inputs, no output rounding)
     for epi, kw in ((EPI_BIAS_SILU, {}), (EPI_BIAS_GELU, {}), (EPI_RESID_GATE, dict(gate=gate, resid=resid))):
         out = torch.empty(M, N, device="cuda", dtype=torch.float32)
         hip.gemm(A, W, out, N=N, K=K, bias=bias, epilogue=epi, out_f32=True, **kw)
         want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=epi, **kw)
         assert rel_err(out, want) < TOL_F32, epi
+        le.check_gemm(out, A, W, N=N, K=K, bias=bias, epilogue=epi, name=f"epilogue {epi} {sorted(kw)} fp32", **kw)
     # in-place residual (C aliases resid), row-sliced views as the DiT uses them
     buf = rnd(M + 58, N, seed=6)
     want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE,
                     gate=gate, resid=buf[:M].clone())
-    tail = buf[M:].clone()
+    tail, before = buf[M:].clone(), buf[:M].clone()
     hip.gemm(A, W, buf[:M], N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=buf[:M])
     assert rel_err(buf[:M].float(), want) < TOL_BF16
+    le.check_gemm(buf[:M], A, W, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=before, name="in-place residual")
     assert torch.equal(buf[M:], tail)
 
 
@@ -137,9 +142,11 @@ def test_gemm_swiglu(hip, ref, gemm_epi):
     hip.gemm(A, W, out, N=2 * Hd, K=K, epilogue=EPI_SWIGLU)
     want = torch.nn.functional.silu(A.float() @ wg.float().t()) * (A.float() @ wi.float().t())
     assert rel_err(out.float(), want) < TOL_BF16
+    le.check_gemm(out, A, W, N=2 * Hd, K=K, epilogue=EPI_SWIGLU, name="swiglu bf16")
     out32 = torch.empty(M, Hd, device="cuda", dtype=torch.float32)                 # fp32-store test epilogue: 1e-3
     hip.gemm(A, W, out32, N=2 * Hd, K=K, epilogue=EPI_SWIGLU, out_f32=True)
     assert rel_err(out32, want) < TOL_F32
+    le.check_gemm(out32, A, W, N=2 * Hd, K=K, epilogue=EPI_SWIGLU, name="swiglu fp32")
     # and the reference double agrees with the closed form (keeps the two test backends honest)
     w2 = ref.gemm(A, W, torch.empty(M, Hd, device="cuda"), N=2 * Hd, K=K, epilogue=EPI_SWIGLU)
     assert rel_err(w2, want) < 1e-5
@@ -181,6 +188,7 @@ def test_gemm_big_tiles_both_main_loops(hip, ref, gemm_big, M, N, K):
         assert not torch.isnan(outs[0].float()).any() and torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
         want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, **{k: v for k, v in kw.items() if k != "out_f32"})
         assert rel_err(outs[0].float(), want) < (TOL_F32 if kw.get("out_f32") else TOL_BF16), kw.get("epilogue", 0)
+        le.check_gemm(outs[0], A, W, N=N, K=K, name=f"big GEMM {sorted(kw)}", **kw)
         if gemm_big == 1:
             # gemm_w4r_kernel (ABI v7): the same launch with the fragment-ordered weight copy -- weights straight into registers,
             # only the activations through LDS; same MFMAs in the same k order, so the SAME BITS as gemm_w4q_kernel, launch after launch
@@ -198,6 +206,7 @@ def test_gemm_big_tiles_both_main_loops(hip, ref, gemm_big, M, N, K):
     hip.gemm(A, packing.pack_swiglu(wg, wi, "cuda"), o, N=N, K=K, epilogue=EPI_SWIGLU)
     want = torch.nn.functional.silu(A.float() @ wg.float().t()) * (A.float() @ wi.float().t())
     assert not torch.isnan(o.float()).any() and rel_err(o.float(), want) < TOL_BF16
+    le.check_gemm(o, A, packing.pack_swiglu(wg, wi, "cuda"), N=N, K=K, epilogue=EPI_SWIGLU, name="big GEMM swiglu")
     if gemm_big == 1:
         Wsw = packing.pack_swiglu(wg, wi, "cuda")
         o2 = torch.full((M, Hd), float("nan"), device="cuda", dtype=BF16)
@@ -329,6 +338,7 @@ def _conv_case(hip, ref, case, frag=False, out_f32=False):
     y = torch.nn.functional.conv3d(xin, w5.float(), bias, stride=stride)[0].permute(1, 2, 3, 0) + resid.float()
     assert rel_err(want, y) < 1e-5
     assert rel_err(out.float(), want) < (TOL_F32 if out_f32 else TOL_BF16)
+    le.check_gemm(out, x, Wp, N=Cout, K=Wp.shape[1], bias=bias, conv=geom, epilogue=EPI_RESID_GATE, resid=resid, name="conv")
 
 
 def test_conv3d_halo_kernel_race_screen_and_generic_agreement(hip):
@@ -397,12 +407,14 @@ def test_conv3d_thin_input_fused(hip, ref, kt, T, H, W, hf, resid_on):
     want = ref.gemm(x, Wp, torch.empty(To, H, W, Cout, device="cuda"), N=Cout, K=128, bias=bias, conv=geom,
                     epilogue=epi, resid=resid)
     assert rel_err(out.float(), want) < TOL_BF16
+    le.check_gemm(out, x, Wp, N=Cout, K=128, bias=bias, conv=geom, epilogue=epi, resid=resid, name="thin-input conv")
     # the older route: explicit im2col + plain GEMM
     cols = torch.empty(To * H * W, 128, device="cuda", dtype=BF16)
     hip.im2col_causal(x, cols, geom)
     out2 = torch.empty_like(out)
     hip.gemm(cols, Wp, out2, N=Cout, K=128, M=To * H * W, bias=bias, epilogue=epi, resid=resid, lda=128, ldc=Cout, ldr=Cout)
     assert rel_err(out.float(), out2.float()) < TOL_BF16
+    le.check_gemm(out2, x, Wp, N=Cout, K=128, bias=bias, conv=geom, epilogue=epi, resid=resid, name="im2col + GEMM")
     assert stats is not None
     o = out.double().reshape(To, H * W, 32, Cout // 32)
     want_stats = torch.stack([o.sum(dim=(1, 3)), (o * o).sum(dim=(1, 3))], dim=-1)
@@ -430,6 +442,7 @@ def test_upscale_pixel_shuffle_epilogue(hip, ref, gemm_epi, rz, drop):
     assert rel_err(want, y) < 1e-5
     assert not torch.isnan(out.float()).any()
     assert rel_err(out.float(), want) < TOL_BF16
+    le.check_gemm(out, x, Wp, N=4 * rz * Cc, K=Cc, M=F_ * H * W, bias=bias, ps=ps, name="pixel shuffle")
 
 
 def test_gemm_epilogue_paths_bit_identical(hip):
@@ -539,7 +552,9 @@ def test_conv_phase_scatter_subpixel(hip, ref, gemm_epi, frag, T, H, W, Cin, Cou
                 assert hip._quad_ok(x, q0[2], out_quad[tz:], Cout, q0[2].shape[1], g0, opsmod.PhaseScatter(0, 0, q0[4], ts, quad=quad), False)
                 hip.gemm(x, q0[2], out_quad[tz:], N=Cout, K=q0[2].shape[1], bias=q0[3], conv=g0, W_frag=q0[5],
                          phase=opsmod.PhaseScatter(0, 0, q0[4], ts, quad=quad))
+            before = out.clone()
             hip.gemm(x, Wp, out[tz:], W_frag=Wf, **kw)
+            le.check_gemm(out[tz:], x, Wp, before=before[tz:], name=f"phase ({py}, {px}) frame phase {tz}", **kw)   # (and no other voxel touched)
             ref.gemm(x, Wp, want[tz:], **kw)
             # independent check of the restatement on this phase: F.conv3d of the padded input + per-voxel bias
             head = halo.float() if hf else x[:1].float().expand(pt, H, W, Cin)
@@ -636,6 +651,7 @@ def test_conv_thin_output_kernel(hip, ref, Cin, Cout, kt, T, H, W, hf):
         assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
         want = ref.gemm(x, Wp, torch.empty(To, H, W, Cout, device="cuda"), **kw)
         assert not torch.isnan(outs[0].float()).any() and rel_err(outs[0].float(), want) < TOL_BF16
+        le.check_gemm(outs[0], x, Wp, name=f"thin-output conv {kw.get('epilogue', 0)}", **kw)
         hip.set_option("conv_impl", 1)                      # the generic implicit-GEMM kernel on the same launch
         try:
             old = torch.empty(To, H, W, Cout, device="cuda", dtype=BF16)
@@ -797,6 +813,7 @@ def test_rmsnorm_mod(hip, ref, rows, dim):
         hip.rmsnorm_mod(x, out, 1e-5, **kw)
         want = ref.rmsnorm_mod(x, torch.empty(rows, dim, device="cuda"), 1e-5, **kw)
         assert rel_err(out.float(), want) < TOL_BF16
+        le.check_rmsnorm_mod(out, x, 1e-5, **kw)
 
 
 def test_ada_combine(hip, ref):
@@ -828,6 +845,7 @@ def test_qknorm_rope(hip, ref):
     hip.qknorm_rope(got, heads, pos, 58, cos, sin, wq, wk, 1e-5)
     assert torch.equal(got[:, 2 * heads * 128:], qkv[:, 2 * heads * 128:])          # V untouched
     assert rel_err(got.float(), want) < TOL_BF16
+    le.check_qknorm_rope(got, qkv, heads, pos, 58, cos, sin, wq, wk, 1e-5)
 
 
 def _attn_case(lens, heads, D, n_rows, seed=0):
@@ -870,6 +888,7 @@ def test_attn_varlen(hip, ref, attn_impl, lens, heads, D, request):
     want = ref.attn_varlen(qkv, torch.zeros(total, heads * D, device="cuda"), seq_rows, out_rows, cu, max(lens),
                            heads, D, scale)
     assert rel_err(out.float(), want) < 4e-3       # P is rounded to bf16 before PV (as flash kernels do)
+    le.check_attn(out, qkv, seq_rows, out_rows, cu, heads, D, scale)
     # race screen: the double-buffered LDS pipeline must be deterministic
     for _ in range(3):
         again = torch.zeros_like(out)
@@ -903,6 +922,7 @@ def test_attn_varlen_scattered_output_rows(hip, ref, attn_impl):
     want = ref.attn_varlen(qkv, torch.full((total + 500, heads * D), 7.0, device="cuda"), seq_rows, out_rows, cu,
                            max(lens), heads, D, 1.0 / math.sqrt(D))
     assert rel_err(out.float(), want) < 4e-3
+    le.check_attn(out, qkv, seq_rows, out_rows, cu, heads, D, 1.0 / math.sqrt(D), before=torch.full_like(out, 7.0))
     untouched = torch.ones(total + 500, dtype=torch.bool, device="cuda")
     untouched[out_rows.long()] = False
     assert bool((out[untouched] == 7.0).all())
@@ -921,6 +941,7 @@ def test_attn_varlen_spiky_scores(hip, ref, attn_impl):
     want = ref.attn_varlen(qkv, torch.zeros(L, heads * D, device="cuda"), rows, rows, cu, L, heads, D, 1.0 / math.sqrt(D))
     assert rel_err(out.float(), want) < 4e-3
     assert rel_err(out[5].float(), want[5]) < 4e-3                      # the row whose max jumps at key 300
+    le.check_attn(out, qkv, rows, rows, cu, heads, D, 1.0 / math.sqrt(D), name="attn_varlen spiky")
 
 
 def test_attn_varlen_constant_scores_skip_rescale(hip, ref, attn_impl):
@@ -936,6 +957,7 @@ def test_attn_varlen_constant_scores_skip_rescale(hip, ref, attn_impl):
     hip.attn_varlen(qkv, out, rows, rows, cu, L, heads, D, 1.0 / math.sqrt(D))
     want = qkv[:, 2 * D:].float().mean(0, keepdim=True).expand(L, D)
     assert rel_err(out.float(), want) < 4e-3
+    le.check_attn(out, qkv, rows, rows, cu, heads, D, 1.0 / math.sqrt(D), name="attn_varlen constant scores")
 
 
 def test_rows_mean_patchify_unpatchify(hip, ref):
@@ -964,6 +986,7 @@ def test_groupnorm(hip, ref, C):
     hip.groupnorm_stats(x, stats, 32)
     want_stats = ref.groupnorm_stats(x, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)
     assert torch.allclose(stats, want_stats, rtol=1e-5)
+    le.check_groupnorm_stats(stats, x, 32)
     again = torch.empty_like(stats)
     hip.groupnorm_stats(x, again, 32)
     assert torch.equal(stats, again)                       # fixed-order reduction: bit-reproducible
@@ -977,6 +1000,7 @@ def test_groupnorm(hip, ref, C):
         gn = torch.nn.functional.group_norm(x.float().permute(0, 3, 1, 2), 32, gamma, beta, 1e-6).permute(0, 2, 3, 1)
         assert rel_err(want, torch.nn.functional.silu(gn) if silu else gn) < 1e-4
         assert rel_err(out.float(), want) < TOL_BF16
+        le.check_groupnorm_apply(out, x, stats, gamma, beta, 32, 1e-6, silu)    # (reference from the statistics the kernel was given)
 
 
 @pytest.mark.parametrize("Cin,kpad,hf", [(4, 128, 0), (4, 128, 2), (16, 448, 0)])
@@ -1134,6 +1158,7 @@ def test_conv_thin_output_4_cout_kernel(hip, ref, T, H, W, Cin, N, hf, kt, out_f
             hip.set_option("conv_thinout4", 1)
         assert not torch.isnan(out.float()).any() and torch.equal(out, again)          # every voxel written, reproducible
         assert rel_err(out.float(), want) < (1e-3 if out_f32 else TOL_BF16), new
+        le.check_gemm(out, x, Wp, name=f"thin-output conv, conv_thinout4 {new}", **kw)
         outs.append(out.float())
     assert rel_err(outs[0], outs[1]) < (2e-4 if out_f32 else 4e-3)
 

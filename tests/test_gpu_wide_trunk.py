@@ -12,6 +12,7 @@ import math
 import pytest
 import torch
 
+import local_error as le
 from conftest import sub, rel_err
 from ops_reference import TorchOps, EPI_BIAS, EPI_RESID_GATE, H16, H16_SCALE, _ld
 
@@ -63,6 +64,7 @@ def test_conv_halo_wide_trunk_epilogues(hip, ref, frag, out_dt, res_dt, Cin, Cou
     got, stats = hip.gemm(x, Wp, out, gn_groups=32, out_f32=out_dt in WIDE, **kw)
     assert got is out and stats is not None and not torch.isnan(out.float()).any()
     assert rel_err(_ld(out), want) < (TOL_F32 if out_dt in WIDE else TOL_BF16)
+    le.check_gemm(out, x, Wp, **kw)
     plain = torch.empty_like(out)
     hip.gemm(x, Wp, plain, out_f32=out_dt in WIDE, **kw)
     assert torch.equal(plain, out)                                   # the fused statistics do not change the output
@@ -112,8 +114,10 @@ def test_conv_subpixel_wide_output_and_statistics(hip, ref, kt, ts, hf, wide):
             kw = dict(N=Cout, K=Wp.shape[1], bias=rnd(Cout, dtype=F32, seed=30 + ph), conv=geom,
                       phase=opsmod.PhaseScatter(py, px, rnd(3, Cout, dtype=F32, seed=40 + ph), ts))
             shared["frame0"] = tz
+            before = out.clone()
             hip.gemm(x, Wp, out[tz:], W_frag=hip.pack_conv_frag(Wp, kt, Cin, Cout, taps=(2, 2)), gn_groups=G, gn_shared=shared,
                      out_f32=True, **kw)
+            le.check_gemm(out[tz:], x, Wp, before=before[tz:], name=f"wide phase ({py}, {px})", **kw)
             ref.gemm(x, Wp, want[tz:], **kw)
     assert not torch.isnan(out).any() and rel_err(_ld(out), want) < TOL_F32
     stats = hip.gn_shared_stats(shared)
@@ -140,8 +144,11 @@ def test_gemm_wide_residual_stream(hip, ref, epi, M, N, K):
         narrow = torch.empty(M, N, device="cuda", dtype=BF16)
         hip.gemm(A, W, narrow, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid[:M])
         assert rel_err(narrow.float(), want) < TOL_BF16
+        before = hid[:M].clone()
+        le.check_gemm(narrow, A, W, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=before, name="fp32 residual -> bf16")
         hip.gemm(A, W, hid[:M], N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid[:M], out_f32=True)
         assert rel_err(hid[:M], want) < TOL_F32 and torch.equal(hid[M:], tail)
+        le.check_gemm(hid[:M], A, W, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=before, name="fp32 stream in place")
     finally:
         hip.set_option("gemm_epi", 0)
 
@@ -162,12 +169,14 @@ def test_gemm_h16_trunk_epilogues(hip, ref, epi, M, N, K, gated):
         out = torch.full((M, N), float("nan"), device="cuda", dtype=H16)
         hip.gemm(A, W, out, N=N, K=K, bias=bias, out_f32=True)
         assert rel_err(_ld(out), ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias)) < TOL_F32
+        le.check_gemm(out, A, W, N=N, K=K, bias=bias, name="bias -> h16")
         for res_dt, out_dt in ((H16, H16), (H16, BF16), (BF16, H16)):
             res = rnd(M, N, seed=5, dtype=res_dt)
             want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=res)
             o = torch.full((M, N), float("nan"), device="cuda", dtype=out_dt)
             hip.gemm(A, W, o, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=res, out_f32=out_dt in WIDE)
             assert rel_err(_ld(o), want) < (TOL_F32 if out_dt in WIDE else TOL_BF16), (res_dt, out_dt)
+            le.check_gemm(o, A, W, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=res, name=f"{res_dt} residual -> {out_dt}")
             if res_dt == out_dt:                                       # in place on the trunk
                 hip.gemm(A, W, res, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=res, out_f32=True)
                 assert torch.equal(res, o)
@@ -189,6 +198,7 @@ def test_generic_conv_h16_output(hip, ref):
         out = torch.full((To, Ho, Wo, Cout), float("nan"), device="cuda", dtype=H16)
         hip.gemm(x, Wc, out, out_f32=True, **kw)
         assert rel_err(_ld(out), ref.gemm(x, Wc, torch.empty(To, Ho, Wo, Cout, device="cuda"), **kw)) < TOL_F32
+        le.check_gemm(out, x, Wc, name=f"generic conv {k} -> h16", **kw)
 
 
 @pytest.mark.parametrize("rows,dim", [(1000, 2560), (58, 2560), (7, 3072), (333, 256)])
@@ -199,6 +209,7 @@ def test_rmsnorm_mod_fp32_input(hip, ref, rows, dim):
         out = torch.empty(rows, dim, device="cuda", dtype=BF16)
         hip.rmsnorm_mod(x, out, 1e-5, **kw)
         assert rel_err(out.float(), ref.rmsnorm_mod(x, torch.empty(rows, dim, device="cuda"), 1e-5, **kw)) < TOL_BF16
+        le.check_rmsnorm_mod(out, x, 1e-5, **kw)
     # a bf16-representable fp32 input gives the bf16 kernel's bits
     xb = rnd(rows, dim, scale=2.0)
     a, b = torch.empty(rows, dim, device="cuda", dtype=BF16), torch.empty(rows, dim, device="cuda", dtype=BF16)
@@ -220,11 +231,13 @@ def test_groupnorm_h16_input(hip, ref, C):
     want_stats = ref.groupnorm_stats(x, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)
     assert torch.allclose(stats, want_stats, rtol=1e-5)
     assert torch.allclose(stats, ref.groupnorm_stats(_ld(x), torch.empty_like(stats), 32), rtol=1e-5)      # == the fp32 view's
+    le.check_groupnorm_stats(stats, x, 32)
     for silu in (True, False):
         out = torch.empty(T, H, W, C, device="cuda", dtype=BF16)
         hip.groupnorm_apply(x, out, stats, gamma, beta, 32, 1e-6, silu)
         want = ref.groupnorm_apply(x, torch.empty(T, H, W, C, device="cuda"), want_stats, gamma, beta, 32, 1e-6, silu)
         assert rel_err(out.float(), want) < TOL_BF16
+        le.check_groupnorm_apply(out, x, stats, gamma, beta, 32, 1e-6, silu)
     # the h16 kernels on an exactly representable tensor == the fp32 kernels on its fp32 view, bit for bit
     sf = torch.empty_like(stats)
     hip.groupnorm_stats(_ld(x), sf, 32)
@@ -244,11 +257,13 @@ def test_groupnorm_fp32_input(hip, ref, C):
     hip.groupnorm_stats(x, stats, 32)
     want_stats = ref.groupnorm_stats(x, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)
     assert torch.allclose(stats, want_stats, rtol=1e-5)
+    le.check_groupnorm_stats(stats, x, 32)
     for silu in (True, False):
         out = torch.empty(T, H, W, C, device="cuda", dtype=BF16)
         hip.groupnorm_apply(x, out, stats, gamma, beta, 32, 1e-6, silu)
         want = ref.groupnorm_apply(x, torch.empty(T, H, W, C, device="cuda"), want_stats, gamma, beta, 32, 1e-6, silu)
         assert rel_err(out.float(), want) < TOL_BF16
+        le.check_groupnorm_apply(out, x, stats, gamma, beta, 32, 1e-6, silu)
     xb = rnd(T, H, W, C, scale=1.5)                               # bf16-representable fp32 input == the bf16 kernel, bit for bit
     sb, sf = torch.empty_like(stats), torch.empty_like(stats)
     hip.groupnorm_stats(xb, sb, 32)
@@ -274,6 +289,7 @@ def test_conv_thin_input_wide_output(hip, ref, wide):
     _, stats = hip.gemm(x, Wp, out, gn_groups=32, out_f32=True, **kw)
     want = ref.gemm(x, Wp, torch.empty(T, H, W, Cout, device="cuda"), **kw)
     assert rel_err(_ld(out), want) < TOL_F32 and stats is not None
+    le.check_gemm(out, x, Wp, name="thin-input conv wide output", **kw)
     ws = ref.groupnorm_stats(out, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)
     assert rel_err(stats[..., 0], ws[..., 0]) < 1e-5 and rel_err(stats[..., 1], ws[..., 1]) < 1e-6
 
@@ -317,6 +333,7 @@ def test_rmsnorm_mod_h16_input(hip, ref, rows, dim):
         out = torch.empty(rows, dim, device="cuda", dtype=BF16)
         hip.rmsnorm_mod(x, out, 1e-5, **kw)
         assert rel_err(out.float(), ref.rmsnorm_mod(x, torch.empty(rows, dim, device="cuda"), 1e-5, **kw)) < TOL_BF16
+        le.check_rmsnorm_mod(out, x, 1e-5, **kw)
         same = torch.empty_like(out)
         hip.rmsnorm_mod(_ld(x), same, 1e-5, **kw)                 # == the fp32 kernel on the values the halves stand for
         assert torch.equal(out, same)
@@ -339,6 +356,7 @@ def test_gemm_persistent_h16_stream_epilogues(hip, ref, M, N, K):
         hip.gemm(A, W, out, N=N, K=K, bias=bias, out_f32=True, W_frag=Wf)
         assert hip.last_kernel_class == "gemm_persistent"
         assert rel_err(_ld(out), ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias)) < TOL_F32
+        le.check_gemm(out, A, W, N=N, K=K, bias=bias, name="persistent bias -> h16")
         want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid0)
         outs = []
         for frag in (Wf, None, Wf):
@@ -347,6 +365,7 @@ def test_gemm_persistent_h16_stream_epilogues(hip, ref, M, N, K):
             assert hip.last_kernel_class == "gemm_persistent"
             outs.append(hid)
         assert rel_err(_ld(outs[0]), want) < TOL_F32
+        le.check_gemm(outs[0], A, W, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid0, name="persistent h16 stream")
         assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
     finally:
         hip.record_kernel_class = False

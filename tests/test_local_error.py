@@ -1,0 +1,338 @@
+"""-m "not gpu": the per-element checker of tests/local_error.py, proven on the CPU.
+
+  * No false alarms: a correct implementation -- the fp32 restatement of tests/ops_reference.py with one rounding into the output's
+    storage format -- stays inside every bound, for every op family, at the launch-geometry shapes of tests/test_gpu_side_kernels.py
+    scaled to CPU size and at the small GEMM / conv / attention cases of tests/test_gpu_kernels.py.
+  * Fault injection: a local fault put into a correct result fails the checker while the global metric the kernel tests used alone so
+    far (||got - want|| / ||want|| < 2.5e-3, 4e-3 for attention) still passes -- the gap this checker closes."""
+import math
+
+import pytest
+import torch
+
+import local_error as le
+from conftest import sub, rel_err
+from ops_reference import TorchOps, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_RESID_GATE, EPI_SWIGLU, H16, H16_SCALE, _ld, _st
+
+BF16, F32 = torch.bfloat16, torch.float32
+TOL_BF16, TOL_ATTN = 2.5e-3, 4e-3
+STORES = [BF16, H16, F32]
+ref = TorchOps("cpu", act_dtype=F32)
+
+
+def rnd(*shape, scale=1.0, seed=0, dtype=BF16):
+    g = torch.Generator().manual_seed(seed + sum(shape))
+    v = torch.randn(*shape, generator=g) * scale
+    return (v * H16_SCALE).to(H16) if dtype == H16 else v.to(dtype)
+
+
+def must_fail(fn):
+    with pytest.raises(AssertionError) as e:
+        fn()
+    msg = str(e.value)
+    assert "mod 256" in msg and "mod 16" in msg and "row-relative" in msg, msg
+    return msg
+
+
+def conv_weight(Cout, Cin, k, seed=2):
+    w5 = rnd(Cout, Cin, *k, scale=1.0 / math.sqrt(Cin * k[0] * k[1] * k[2]), seed=seed)
+    return w5, w5.permute(0, 2, 3, 4, 1).reshape(Cout, -1).contiguous()        # [N, (kt, kh, kw, Cin)]: the packed K order
+
+
+# ------------------------------------------------------------------------------------------------ no false alarms
+@pytest.mark.parametrize("out_dt", STORES, ids=["bf16", "h16", "fp32"])
+@pytest.mark.parametrize("M,N,K", [(300, 256, 128), (257, 64, 192), (1, 2560, 256), (513, 384, 64), (257, 64, 2560), (58, 256, 6912)])
+def test_gemm_bias_is_inside_its_bounds(M, N, K, out_dt):
+    A, W, bias = rnd(M, K), rnd(N, K, scale=1.0 / math.sqrt(K), seed=1), rnd(N, dtype=F32, seed=3)
+    out = ref.gemm(A, W, torch.empty(M, N, dtype=out_dt), N=N, K=K, bias=bias)
+    assert le.check_gemm(out, A, W, N=N, K=K, bias=bias) <= 1.0
+
+
+@pytest.mark.parametrize("out_dt", STORES, ids=["bf16", "h16", "fp32"])
+def test_gemm_epilogues_are_inside_their_bounds(out_dt):
+    M, N, K = 777, 512, 320
+    A, W = rnd(M, K), rnd(N, K, scale=1.0 / math.sqrt(K), seed=1)
+    bias, gate = rnd(N, dtype=F32, seed=3), rnd(N, dtype=F32, seed=4)
+    for res_dt in STORES:
+        resid = rnd(M, N, seed=5, dtype=res_dt)
+        for epi, kw in ((EPI_BIAS_SILU, {}), (EPI_BIAS_GELU, {}), (EPI_RESID_GATE, dict(gate=gate, resid=resid)),
+                        (EPI_RESID_GATE, dict(resid=resid)), (EPI_RESID_GATE, dict(gate=gate))):
+            kw = dict(N=N, K=K, bias=bias, epilogue=epi, **kw)
+            out = ref.gemm(A, W, torch.empty(M, N, dtype=out_dt), **kw)
+            le.check_gemm(out, A, W, name=f"epilogue {epi}", **kw)
+    Hd = 768                                                              # SwiGLU: 16 gate | 16 in columns interleaved
+    wg, wi = rnd(Hd, K, scale=1 / 16, seed=7), rnd(Hd, K, scale=1 / 16, seed=8)
+    Wsw = torch.stack([wg.reshape(Hd // 16, 16, K), wi.reshape(Hd // 16, 16, K)], dim=1).reshape(2 * Hd, K)
+    out = ref.gemm(A, Wsw, torch.empty(M, Hd, dtype=out_dt), N=2 * Hd, K=K, epilogue=EPI_SWIGLU)
+    le.check_gemm(out, A, Wsw, N=2 * Hd, K=K, epilogue=EPI_SWIGLU, name="swiglu")
+    closed = torch.nn.functional.silu(A.double() @ wg.double().t()) * (A.double() @ wi.double().t())
+    assert rel_err(le.gemm_reference(A, Wsw, out, N=2 * Hd, K=K, epilogue=EPI_SWIGLU)[0], closed) < 1e-12
+
+
+CONVS = [  # Cin, Cout, k, stride, pad(lo, hi), T, H, W, halo frames  (the small rows of CONV_CASES in tests/test_gpu_kernels.py)
+    (128, 128, (3, 3, 3), (1, 1, 1), (1, 1), 3, 10, 12, 0),
+    (128, 128, (3, 3, 3), (1, 1, 1), (1, 1), 2, 9, 7, 2),
+    (256, 256, (3, 3, 3), (2, 2, 2), (0, 1), 4, 12, 10, 1),
+    (128, 128, (1, 3, 3), (1, 2, 2), (0, 1), 3, 14, 16, 0),
+    (512, 256, (1, 1, 1), (1, 1, 1), (0, 0), 3, 6, 5, 0),
+    (128, 3, (3, 3, 3), (1, 1, 1), (1, 1), 3, 9, 11, 2),
+    (4, 128, (3, 3, 3), (1, 1, 1), (1, 1), 3, 21, 30, 0),
+]
+
+
+def conv_problem(case, res_dt=BF16):
+    ops = sub("ops")
+    Cin, Cout, k, stride, (plo, phi), T, H, W, hf = case
+    x = rnd(T, H, W, Cin)
+    halo = rnd(hf, H, W, Cin, seed=9) if hf else None
+    w5, Wp = conv_weight(Cout, Cin, k)
+    pt = hf if hf else k[0] - 1
+    To, Ho, Wo = (T + pt - k[0]) // stride[0] + 1, (H + plo + phi - k[1]) // stride[1] + 1, (W + plo + phi - k[2]) // stride[2] + 1
+    geom = ops.Conv3dGeom(T, H, W, Cin, To, Ho, Wo, k, stride, (pt, plo, plo), halo)
+    kw = dict(N=Cout, K=Wp.shape[1], bias=rnd(Cout, dtype=F32, seed=3), conv=geom, epilogue=EPI_RESID_GATE,
+              resid=rnd(To, Ho, Wo, Cout, seed=11, dtype=res_dt))
+    return x, w5, Wp, kw, (To, Ho, Wo, Cout)
+
+
+@pytest.mark.parametrize("out_dt", STORES, ids=["bf16", "h16", "fp32"])
+@pytest.mark.parametrize("case", CONVS)
+def test_conv_is_inside_its_bounds(case, out_dt):
+    x, w5, Wp, kw, shape = conv_problem(case, res_dt=out_dt)
+    out = ref.gemm(x, Wp, torch.empty(shape, dtype=out_dt), **kw)
+    assert le.check_gemm(out, x, Wp, **kw) <= 1.0
+    # the fp64 reference is F.conv3d in double on the padded input the fp32 restatement builds: restated here from the 5-d weights
+    g = kw["conv"]
+    head = g.halo.double() if g.halo is not None else x[:1].double().expand(g.pad[0], *x.shape[1:])
+    xin = torch.cat([head, x.double()], 0).permute(3, 0, 1, 2)[None] if g.pad[0] else x.double().permute(3, 0, 1, 2)[None]
+    xin = torch.nn.functional.pad(xin, (case[4][0], case[4][1], case[4][0], case[4][1]))
+    y = torch.nn.functional.conv3d(xin, w5.double(), kw["bias"].double(), stride=case[3])[0].permute(1, 2, 3, 0) + le.values(kw["resid"])
+    assert rel_err(le.gemm_reference(x, Wp, out, **kw)[0], y) < 1e-12
+
+
+@pytest.mark.parametrize("rz,drop", [(1, False), (2, False), (2, True)])
+def test_pixel_shuffle_index_map_is_inside_its_bounds(rz, drop):
+    ops = sub("ops")
+    F_, H, W, Cc = 3, 5, 6, 64
+    x, Wp = rnd(F_ * H * W, Cc), rnd(4 * rz * Cc, Cc, scale=1 / 8, seed=1)
+    kw = dict(N=4 * rz * Cc, K=Cc, M=F_ * H * W, bias=rnd(4 * rz * Cc, dtype=F32, seed=3), ps=ops.PixelShuffleGeom(F_, H, W, rz, Cc, drop))
+    out = ref.gemm(x, Wp, torch.empty(F_ * rz - (1 if drop else 0), 2 * H, 2 * W, Cc, dtype=BF16), **kw)
+    le.check_gemm(out, x, Wp, **kw)
+    must_fail(lambda: le.check_gemm(out.roll(1, dims=2), x, Wp, **kw))             # a wrong index map is not inside them
+
+
+@pytest.mark.parametrize("kt,ts,hf", [(3, 1, 0), (2, 2, 1)])
+def test_phase_scatter_writes_its_phase_only(kt, ts, hf):
+    ops = sub("ops")
+    T, H, W, Cin, Cout = 3, 7, 9, 64, 128
+    x = rnd(T, H, W, Cin)
+    halo = rnd(hf, H, W, Cin, seed=9) if hf else None
+    pt = hf if hf else kt - 1
+    To = T + pt - kt + 1
+    out = torch.full((To * ts, 2 * H, 2 * W, Cout), float("nan"), dtype=BF16)
+    for ph, (py, px) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+        _, Wp = conv_weight(Cout, Cin, (kt, 2, 2), seed=20 + ph)
+        geom = ops.Conv3dGeom(T, H, W, Cin, To, H, W, (kt, 2, 2), (1, 1, 1), (pt, 1 - py, 1 - px), halo)
+        kw = dict(N=Cout, K=Wp.shape[1], bias=rnd(Cout, dtype=F32, seed=30 + ph), conv=geom,
+                  phase=ops.PhaseScatter(py, px, rnd(3, Cout, dtype=F32, seed=40 + ph), ts))
+        before = out.clone()
+        ref.gemm(x, Wp, out, **kw)
+        le.check_gemm(out, x, Wp, before=before, **kw)
+        if ph == 0:                                                                # a launch that also touches another phase's voxel
+            stray = out.clone()
+            stray[0, 0, 1, 5] = 1.0
+            with pytest.raises(AssertionError, match="not its own"):
+                le.check_gemm(stray, x, Wp, before=before, **kw)
+
+
+@pytest.mark.parametrize("lens,heads,D", [([135, 64, 1, 200, 129], 3, 128), ([64, 128, 192, 63, 65, 2, 1], 2, 128), ([100, 33, 257], 1, 512),
+                                          ([640], 1, 128), ([300, 300, 77], 5, 128)])
+def test_attention_is_inside_its_bounds(lens, heads, D):
+    n_rows = 700
+    qkv = rnd(n_rows, 3 * heads * D)
+    g = torch.Generator().manual_seed(0)
+    seq_rows = torch.cat([torch.randint(0, n_rows, (L,), generator=g) for L in lens]).int()
+    total = sum(lens)
+    out_rows = torch.randperm(total + 9, generator=g)[:total].int()
+    cu = torch.tensor([0] + list(torch.tensor(lens).cumsum(0)), dtype=torch.int32)
+    out = torch.full((total + 9, heads * D), 7.0, dtype=BF16)
+    before = out.clone()
+    ref.attn_varlen(qkv, out, seq_rows, out_rows, cu, max(lens), heads, D, 1.0 / math.sqrt(D))
+    assert le.check_attn(out, qkv, seq_rows, out_rows, cu, heads, D, 1.0 / math.sqrt(D), before=before) <= 1.0
+
+
+@pytest.mark.parametrize("kind", STORES, ids=["bf16", "h16", "fp32"])
+@pytest.mark.parametrize("rows,dim", [(37, 8), (33, 520), (1000, 2560), (19, 3072), (21, 4096)])
+def test_rmsnorm_mod_is_inside_its_bounds(rows, dim, kind):
+    ramp = torch.logspace(-2, 2, rows)[:, None]                                    # per-row magnitudes 0.01 .. 100
+    x = _st(rnd(rows, dim, dtype=F32) * ramp, torch.empty(0, dtype=kind))
+    w, sc, sh = (rnd(dim, dtype=F32, seed=s) for s in (1, 2, 3))
+    for kw in (dict(), dict(scale=sc, shift=sh), dict(w=w, scale=sc, shift=sh)):
+        out = ref.rmsnorm_mod(x, torch.empty(rows, dim, dtype=BF16), 1e-5, **kw)
+        assert le.check_rmsnorm_mod(out, x, 1e-5, **kw) <= 1.0
+
+
+def rope_tables(n_pos, n_freq):
+    ang = torch.arange(n_pos, dtype=F32)[:, None] * (10000.0 ** (-torch.arange(n_freq, dtype=F32) / n_freq))[None, :]
+    return ang.cos().contiguous(), ang.sin().contiguous()
+
+
+@pytest.mark.parametrize("heads,n_freq", [(1, 21), (3, 10), (5, 1), (20, 21), (24, 10)])
+def test_qknorm_rope_is_inside_its_bounds(heads, n_freq):
+    rows, n_pos = 211, 40
+    qkv = rnd(rows, 3 * heads * 128, scale=3.0)
+    pos = torch.stack([torch.arange(rows) % 7, torch.arange(rows) % 31, torch.arange(rows) % n_pos], -1).to(torch.int16)
+    cos, sin = rope_tables(n_pos, n_freq)
+    wq, wk = rnd(128, dtype=F32, seed=1) + 1, rnd(128, dtype=F32, seed=2) + 1
+    got = ref.qknorm_rope(qkv.clone(), heads, pos, 5, cos, sin, wq, wk, 1e-5)
+    assert le.check_qknorm_rope(got, qkv, heads, pos, 5, cos, sin, wq, wk, 1e-5) <= 1.0
+    # positions that leave the table are clamped by the kernel: the reference takes the clamped rows (the fp32 restatement would
+    # wrap or raise, so the clamped positions are handed to it)
+    far = pos.clone()
+    far[::3, 0] -= 9
+    far[1::3, 0] += n_pos
+    clamped = far.clone()
+    clamped[:, 0] = (far[:, 0].long() + 5).clamp(0, n_pos - 1).to(torch.int16) - 5
+    got = ref.qknorm_rope(qkv.clone(), heads, clamped, 5, cos, sin, wq, wk, 1e-5)
+    le.check_qknorm_rope(got, qkv, heads, far, 5, cos, sin, wq, wk, 1e-5, name="qknorm_rope clamped")
+    touched = got.clone()
+    touched[7, 2 * heads * 128 + 3] += 1
+    with pytest.raises(AssertionError, match="V columns"):
+        le.check_qknorm_rope(touched, qkv, heads, pos, 5, cos, sin, wq, wk, 1e-5)
+
+
+@pytest.mark.parametrize("kind", STORES, ids=["bf16", "h16", "fp32"])
+@pytest.mark.parametrize("HW,C,groups", [((1, 2047), 128, 32), ((1, 2049), 256, 32), ((3, 1367), 512, 32), ((1, 4097), 128, 16),
+                                         ((1, 2048), 128, 8), ((13, 17), 192, 32), ((9, 11), 320, 32), ((7, 5), 24, 3)])
+def test_groupnorm_is_inside_its_bounds(HW, C, groups, kind):
+    T = 2
+    x = _st(rnd(T, *HW, C, scale=1.5, dtype=F32) + 0.7, torch.empty(0, dtype=kind))
+    gamma, beta = rnd(C, dtype=F32, seed=1) + 1, rnd(C, dtype=F32, seed=2)
+    stats = ref.groupnorm_stats(x, torch.empty(T, groups, 2, dtype=torch.float64), groups)
+    if 256 % (C // 8) == 0:                                                        # (the C svr_groupnorm_stats accepts)
+        assert le.check_groupnorm_stats(stats, x, groups) <= 1.0
+        xg = _ld(x).reshape(T, -1, groups, C // groups)                            # fp32 sums, as the kernel's threads form them
+        f32 = torch.stack([xg.sum(dim=(1, 3)), (xg * xg).sum(dim=(1, 3))], -1)
+        assert le.check_groupnorm_stats(f32.double(), x, groups, name="groupnorm_stats fp32 sums") <= 1.0
+    for silu in (True, False):
+        out = ref.groupnorm_apply(x, torch.empty(T, *HW, C, dtype=BF16), stats, gamma, beta, groups, 1e-6, silu)
+        assert le.check_groupnorm_apply(out, x, stats, gamma, beta, groups, 1e-6, silu) <= 1.0
+        assert le.check_groupnorm_apply(out, x, stats, gamma, beta, groups, 1e-6, silu, slab_rows=1, name="slabs") <= 1.0
+
+
+@pytest.mark.parametrize("cols", [4, 260, 16384, 16388])
+def test_softmax_rows_is_inside_its_bounds(cols):
+    S = torch.randn(6, cols, generator=torch.Generator().manual_seed(cols)) * 30.0
+    S[1, -1] = 400.0                                                               # the maximum is the last element
+    S[2] = 3.25                                                                    # a row of equal values
+    P = ref.softmax_rows(S, torch.empty(6, cols, dtype=BF16), 0.044)
+    assert le.check_softmax_rows(P, S, 0.044) <= 1.0
+
+
+def test_rows_mean_and_unpatchify_are_inside_their_bounds():
+    for n_groups, dim in ((7, 2560), (1, 520)):
+        src = rnd(n_groups * 58, dim)
+        dst = ref.rows_mean(src, torch.empty(58, dim, dtype=BF16), n_groups, 58)
+        le.check("rows_mean", dst, *le.rows_mean_reference(src, n_groups, 58))
+    pred, x_t = rnd(3 * 4 * 6, 96), rnd(3, 8, 12, 16, seed=4)                      # a padded prediction: stride(0) > 4C
+    for xt in (x_t, None):
+        o = ref.unpatchify_euler(pred, xt, torch.empty(3, 8, 12, 16, dtype=BF16))
+        le.check("unpatchify_euler", o, *le.unpatchify_euler_reference(pred, xt, o.shape))
+
+
+# ------------------------------------------------------------------------------------------------ fault injection
+def test_fault_fragment_from_the_row_above():
+    """One 16-byte store (8 bf16) of the last row holds the row above's values: 8 of 768 000 elements."""
+    M, N, K = 1000, 768, 256
+    A, W, bias = rnd(M, K), rnd(N, K, scale=1.0 / math.sqrt(K), seed=1), rnd(N, dtype=F32, seed=3)
+    out = ref.gemm(A, W, torch.empty(M, N, dtype=BF16), N=N, K=K, bias=bias)
+    want32 = ref.gemm(A, W, torch.empty(M, N), N=N, K=K, bias=bias)
+    le.check_gemm(out, A, W, N=N, K=K, bias=bias)
+    out[M - 1, N - 8:] = out[M - 2, N - 8:]
+    assert rel_err(out.float(), want32) < TOL_BF16                                 # the global metric does not see it
+    msg = must_fail(lambda: le.check_gemm(out, A, W, N=N, K=K, bias=bias))
+    assert "in 1 rows" in msg and f"row {M - 1} " in msg
+
+
+def test_fault_one_row_scaled():
+    """One row 3 % too large (a stale 1 / rms): worst row error 3e-2 against 1.7e-3 clean, global metric 1.9e-3."""
+    rows, dim = 1000, 2560
+    x = rnd(rows, dim, scale=2.0)
+    sc, sh = rnd(dim, dtype=F32, seed=2), rnd(dim, dtype=F32, seed=3)
+    out = ref.rmsnorm_mod(x, torch.empty(rows, dim, dtype=BF16), 1e-5, scale=sc)
+    want32 = ref.rmsnorm_mod(x, torch.empty(rows, dim), 1e-5, scale=sc)
+    le.check_rmsnorm_mod(out, x, 1e-5, scale=sc)
+    out[617] = (out[617].float() * 1.03).to(BF16)
+    assert rel_err(out.float(), want32) < TOL_BF16
+    msg = must_fail(lambda: le.check_rmsnorm_mod(out, x, 1e-5, scale=sc))
+    assert "in 1 rows" in msg and "row 617 " in msg
+
+
+def test_fault_two_rows_swapped():
+    """Two rows of a row-normalised output exchanged (a wave serving the wrong slot of its pipeline).  RMSNorm removes a row's
+    magnitude, so the two rows are made alike up to 2 % noise and a factor 1.5: after the norm they differ by 2 % per element -- five
+    times the bf16 rounding, and still invisible in the global metric."""
+    rows, dim = 1000, 2560
+    x = rnd(rows, dim, scale=2.0, dtype=F32)
+    x[401] = 1.5 * x[400] + 0.02 * 2.0 * rnd(dim, dtype=F32, seed=5)
+    x = x.to(BF16)
+    out = ref.rmsnorm_mod(x, torch.empty(rows, dim, dtype=BF16), 1e-5)
+    want32 = ref.rmsnorm_mod(x, torch.empty(rows, dim), 1e-5)
+    le.check_rmsnorm_mod(out, x, 1e-5)
+    out[[400, 401]] = out[[401, 400]]
+    assert rel_err(out.float(), want32) < TOL_BF16
+    msg = must_fail(lambda: le.check_rmsnorm_mod(out, x, 1e-5))
+    assert "in 2 rows" in msg
+
+
+def test_fault_corner_voxel_missing_one_tap():
+    """The corner voxel (0, 0, 0) of a 3x3x3 conv output lacks its centre tap in all 128 channels (a halo predicate off by one)."""
+    case = (128, 128, (3, 3, 3), (1, 1, 1), (1, 1), 3, 32, 80, 0)
+    x, w5, Wp, kw, shape = conv_problem(case)
+    want32 = ref.gemm(x, Wp, torch.empty(shape), **kw)
+    out = want32.to(BF16)
+    le.check_gemm(out, x, Wp, **kw)
+    faulty = want32.clone()
+    faulty[0, 0, 0] -= x[0, 0, 0].float() @ w5[:, :, 2, 1, 1].float().t()
+    out = faulty.to(BF16)
+    assert rel_err(out.float(), want32) < TOL_BF16
+    msg = must_fail(lambda: le.check_gemm(out, x, Wp, **kw))
+    assert "in 1 rows" in msg and "row 0 " in msg
+
+
+def test_fault_groupnorm_sum_missing_one_block():
+    """One group's sums lack the contribution of one 2048-row block of 128 (a partial that was never added).  The statistics check
+    sees it; so does the apply output per element, while the global metric of the apply output -- all that sees fused statistics
+    that are only ever consumed -- stays under its limit."""
+    T, H, W, C, G = 1, 128, 2048, 32, 8
+    x = (rnd(T, H, W, C, scale=1.5, dtype=F32) + 0.1).to(BF16)
+    gamma, beta = rnd(C, dtype=F32, seed=1) + 1, rnd(C, dtype=F32, seed=2)
+    stats = ref.groupnorm_stats(x, torch.empty(T, G, 2, dtype=torch.float64), G)
+    le.check_groupnorm_stats(stats, x, G)
+    blk = x[:, 17].double().reshape(T, W, G, C // G)                               # block 17 = rows 17 * 2048 ..
+    bad = stats.clone()
+    bad[:, 5, 0] -= blk[:, :, 5].sum(dim=(1, 2))
+    bad[:, 5, 1] -= blk[:, :, 5].pow(2).sum(dim=(1, 2))
+    must_fail(lambda: le.check_groupnorm_stats(bad, x, G))
+    want32 = ref.groupnorm_apply(x, torch.empty(T, H, W, C), stats, gamma, beta, G, 1e-6, False)
+    out = ref.groupnorm_apply(x, torch.empty(T, H, W, C, dtype=BF16), bad, gamma, beta, G, 1e-6, False)
+    assert rel_err(out.float(), want32) < TOL_BF16
+    must_fail(lambda: le.check_groupnorm_apply(out, x, stats, gamma, beta, G, 1e-6, False))
+
+
+def test_fault_attention_row_without_its_last_key_tile():
+    """One query row of one head computed over the first 576 of its 640 keys (the last 64-key tile skipped)."""
+    heads, D, L = 16, 128, 640
+    qkv = rnd(2 * L, 3 * heads * D)
+    rows = torch.arange(2 * L, dtype=torch.int32)
+    cu = torch.tensor([0, L, 2 * L], dtype=torch.int32)
+    scale = 1.0 / math.sqrt(D)
+    want32 = ref.attn_varlen(qkv, torch.zeros(2 * L, heads * D), rows, rows, cu, L, heads, D, scale)
+    out = want32.to(BF16)
+    le.check_attn(out, qkv, rows, rows, cu, heads, D, scale)
+    q3 = qkv.float().reshape(2 * L, 3, heads, D)
+    r, h = L + 321, 9
+    p = torch.softmax((q3[r, 0, h] @ q3[L:2 * L - 64, 1, h].t()) * scale, dim=-1)
+    out[r, h * D:(h + 1) * D] = (p @ q3[L:2 * L - 64, 2, h]).to(BF16)
+    assert rel_err(out.float(), want32) < TOL_ATTN
+    msg = must_fail(lambda: le.check_attn(out, qkv, rows, rows, cu, heads, D, scale))
+    assert "in 1 rows" in msg and f"row {r} " in msg
