@@ -94,6 +94,16 @@ template <int KIND> SVR_DEVICE void load8(const void* base, int64_t e8, float* o
     }
 }
 
+// GroupNorm statistics (svr_elementwise.hip, the fused statistics of the conv epilogues): (sum, sum of squares) of four stored
+// values added to fp64 accumulators in a fixed order.  A stored value and its square are exact in fp64, so the only roundings
+// are fp64 adds: var = E[x^2] - mean^2 then survives mean / std far beyond what an fp32 stage allows (include/seedvr2_hip.h,
+// svr_groupnorm_stats).
+SVR_DEVICE void gn_accumulate4(double& s, double& q, float f0, float f1, float f2, float f3) {
+    const double d0 = (double)f0, d1 = (double)f1, d2 = (double)f2, d3 = (double)f3;
+    s += ((d0 + d1) + d2) + d3;
+    q += ((d0 * d0 + d1 * d1) + d2 * d2) + d3 * d3;
+}
+
 SVR_DEVICE uint4 pack8(const float* o) {
     uint4 v;
     v.x = pack2bf(o[0], o[1]); v.y = pack2bf(o[2], o[3]);

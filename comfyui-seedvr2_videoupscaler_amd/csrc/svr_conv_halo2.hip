@@ -731,7 +731,7 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
     const bool resid_gate = a.epilogue == SVR_EPI_RESID_GATE;
     // fused GroupNorm statistics of the stored (bf16-rounded, or fp32) output: this thread always stores the same
     // 8-cout chunk (tid & 15), so it keeps two quad sums over its 16 voxels
-    float gs0 = 0.f, gq0 = 0.f, gs1 = 0.f, gq1 = 0.f;
+    double gs0 = 0.0, gq0 = 0.0, gs1 = 0.0, gq1 = 0.0;         // (fp64 from the first add on: svr_common.h, gn_accumulate4)
     constexpr int EP_ROWS = G::EP_ROWS;                             // patch rows per pass
     constexpr int NPASS = MTW / 2;                                  // every wave parks two of its MTW rows per pass
     static_assert(TY / EP_ROWS == NPASS && EP_ROWS * 32 * 16 == 8 * NT, "MTW / 2 passes, eight store iterations each");
@@ -880,10 +880,8 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
                         *(float4*)cp = make_float4(f[0], f[1], f[2], f[3]);
                         *(float4*)(cp + 4) = make_float4(f[4], f[5], f[6], f[7]);
                         if (with_gn) {
-                            gs0 += f[0] + f[1] + f[2] + f[3];
-                            gq0 += f[0] * f[0] + f[1] * f[1] + f[2] * f[2] + f[3] * f[3];
-                            gs1 += f[4] + f[5] + f[6] + f[7];
-                            gq1 += f[4] * f[4] + f[5] * f[5] + f[6] * f[6] + f[7] * f[7];
+                            gn_accumulate4(gs0, gq0, f[0], f[1], f[2], f[3]);
+                            gn_accumulate4(gs1, gq1, f[4], f[5], f[6], f[7]);
                         }
                     }
                 } else {
@@ -892,10 +890,8 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
                     if (with_gn && ok[it]) {
                         float r[8];
                         if (ko == SVR_STORE_H16) unpack8h(pk, r); else unpack8(pk, r);
-                        gs0 += r[0] + r[1] + r[2] + r[3];
-                        gq0 += r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3];
-                        gs1 += r[4] + r[5] + r[6] + r[7];
-                        gq1 += r[4] * r[4] + r[5] * r[5] + r[6] * r[6] + r[7] * r[7];
+                        gn_accumulate4(gs0, gq0, r[0], r[1], r[2], r[3]);
+                        gn_accumulate4(gs1, gq1, r[4], r[5], r[6], r[7]);
                     }
                 }
             }
@@ -926,17 +922,18 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
     }
     if (a.gn_partial) {                                   // fixed-order reduction: thread -> quad -> group
         __syncthreads();
-        float4* red = (float4*)smem;                      // [NT]
-        double2* qsum = (double2*)(smem + 8192);          // [32 quads]
-        red[tid] = make_float4(gs0, gq0, gs1, gq1);
+        static_assert(NT * 32 + 32 * 16 <= G::LDS, "statistics staging fits the kernel's LDS");
+        double4* red = (double4*)smem;                    // [NT]
+        double2* qsum = (double2*)(smem + NT * 32);       // [32 quads]
+        red[tid] = make_double4(gs0, gq0, gs1, gq1);
         __syncthreads();
         if (tid < 32) {                                   // quad = 2 * chunk + half; rows tid' with tid' & 15 == chunk
             const int c = tid >> 1, h = tid & 1;
             double s = 0.0, q = 0.0;
             for (int j = 0; j < NT / 16; ++j) {
-                const float4 v = red[(j << 4) | c];
-                s += (double)(h ? v.z : v.x);
-                q += (double)(h ? v.w : v.y);
+                const double4 v = red[(j << 4) | c];
+                s += h ? v.z : v.x;
+                q += h ? v.w : v.y;
             }
             qsum[tid] = make_double2(s, q);
         }
@@ -988,8 +985,8 @@ static bool conv_thin_eligible(const svr_gemm_args& a) {
     const svr_conv_geom& g = a.conv;
     return g.enabled && g.Cin == 4 && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 && g.st == 1 &&
            g.ph == 1 && g.pw == 1 && g.Ho == g.H && g.Wo == g.W && g.kt >= 1 && g.kt <= 3 && a.K == 128 &&
-           g.To == g.T + g.pt - g.kt + 1 && !a.ps.enabled && a.epilogue != SVR_EPI_SWIGLU && (a.N % 128) == 0 &&
-           (a.ldc % 8) == 0 && (!a.resid || (a.ldr % 8) == 0);
+           g.To == g.T + g.pt - g.kt + 1 && !a.ps.enabled && a.epilogue != SVR_EPI_SWIGLU && a.epilogue != SVR_EPI_BIAS_GELU &&
+           (a.N % 128) == 0 && (a.ldc % 8) == 0 && (!a.resid || (a.ldr % 8) == 0);
 }
 static int launch_conv_thin(const svr_gemm_args& a, hipStream_t s) { return launch_conv_halo2_t<8, 2>(a, s); }
 
@@ -1019,8 +1016,9 @@ static bool conv_halo_eligible(const svr_gemm_args& a) {
 }
 
 // what conv_halo_eligible() accepts with 128-cout tiles and channels in 32-slices
+// (its epilogue has no tanh-GELU: such a launch -- no production call -- takes the generic kernel; before, it got the bias only)
 static bool conv_halo2_eligible(const svr_gemm_args& a) {
-    return conv_halo_eligible(a) && (a.N % 128) == 0 && a.conv.Cin % 32 == 0;
+    return conv_halo_eligible(a) && (a.N % 128) == 0 && a.conv.Cin % 32 == 0 && a.epilogue != SVR_EPI_BIAS_GELU;
 }
 
 // ------------------------------------------------------------------------------------------------

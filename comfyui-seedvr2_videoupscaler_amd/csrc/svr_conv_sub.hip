@@ -312,7 +312,7 @@ __global__ __launch_bounds__(CS_NT, 1) void conv_sub_kernel(const svr_gemm_args 
     const int up = a.phase.enabled ? 2 : 1, ts = a.phase.enabled ? a.phase.t_stride : 1;
     const int yb = py ? g.H - 1 : 0, xb = px ? g.W - 1 : 0;
     const float* btab = a.phase.enabled ? bias_border_p : nullptr;
-    float gs0 = 0.f, gq0 = 0.f, gs1 = 0.f, gq1 = 0.f;      // fused GroupNorm statistics of the stored values (columns n .. n + 3, n + 4 .. n + 7)
+    double gs0 = 0.0, gq0 = 0.0, gs1 = 0.0, gq1 = 0.0;     // fused GroupNorm statistics of the stored values (columns n .. n + 3, n + 4 .. n + 7)
     // (the body is instantiated per output kind -- bf16 | fp32 | h16, the wide residual trunk -- so its loops carry no option branches)
     auto ep_body = [&](auto o32c) {
     constexpr int OKIND = decltype(o32c)::value;
@@ -377,10 +377,8 @@ __global__ __launch_bounds__(CS_NT, 1) void conv_sub_kernel(const svr_gemm_args 
                     if constexpr (OKIND == SVR_STORE_H16) unpack8h(pk, r); else unpack8(pk, r);
                 }
                 if (a.gn_partial != nullptr && ok[it]) {
-                    gs0 += r[0] + r[1] + r[2] + r[3];
-                    gq0 += r[0] * r[0] + r[1] * r[1] + r[2] * r[2] + r[3] * r[3];
-                    gs1 += r[4] + r[5] + r[6] + r[7];
-                    gq1 += r[4] * r[4] + r[5] * r[5] + r[6] * r[6] + r[7] * r[7];
+                    gn_accumulate4(gs0, gq0, r[0], r[1], r[2], r[3]);
+                    gn_accumulate4(gs1, gq1, r[4], r[5], r[6], r[7]);
                 }
             }
         }
@@ -395,17 +393,17 @@ __global__ __launch_bounds__(CS_NT, 1) void conv_sub_kernel(const svr_gemm_args 
         // gn_partial[output frame][phase (py, px)][block][group]: the four phase launches of an upsampled frame fill one row of
         // 4 x blocks entries, which svr_groupnorm_reduce() adds up (a dense launch: [frame][block][group])
         __syncthreads();
-        float4* red = (float4*)smem;                      // [NT]
-        double2* qsum = (double2*)(smem + 8192);          // [32 quads]
-        red[tid] = make_float4(gs0, gq0, gs1, gq1);
+        double4* red = (double4*)smem;                    // [NT]
+        double2* qsum = (double2*)(smem + NT * 32);       // [32 quads]
+        red[tid] = make_double4(gs0, gq0, gs1, gq1);
         __syncthreads();
         if (tid < 32) {                                   // quad = 2 * chunk + half; rows tid' with tid' & 15 == chunk
             const int c = tid >> 1, h = tid & 1;
             double s_ = 0.0, q_ = 0.0;
             for (int j = 0; j < NT / 16; ++j) {
-                const float4 v = red[(j << 4) | c];
-                s_ += (double)(h ? v.z : v.x);
-                q_ += (double)(h ? v.w : v.y);
+                const double4 v = red[(j << 4) | c];
+                s_ += h ? v.z : v.x;
+                q_ += h ? v.w : v.y;
             }
             qsum[tid] = make_double2(s_, q_);
         }

@@ -270,9 +270,13 @@ __global__ void unpatchify_euler_kernel(const bf16_t* __restrict__ pred, int64_t
 }
 
 // ------------------------------------------------------------------------------------------------
-// Per-frame GroupNorm over NDHWC.  Statistics: fp32 per thread over a fixed row set, then fixed-order
-// fp64 reductions (inside the block through LDS, across blocks by a second kernel) -- no atomics, so
+// Per-frame GroupNorm over NDHWC.  Statistics: fp64 from the first add on -- per thread over a fixed row set, then
+// fixed-order reductions (inside the block through LDS, across blocks by a second kernel) -- no atomics, so
 // the result is bit-reproducible and independent of how the clip is cut into temporal slices.
+// The apply pass forms var = E[x^2] - mean^2: the sums must carry (mean / std)^2 more digits than the variance needs.
+// A stored value (bf16 / h16 / fp32) and its square are EXACT in fp64, so every rounding here is one fp64 add: the
+// variance is good to ~n 2^-53 (mean / std)^2 relative, n the number of adds in the longest chain (<= 512 + 16 + 16 +
+// blocks).  The fp32 per-thread stage this replaces lost the variance at mean / std ~ 256 (tests/test_gpu_conditioning.py).
 // ------------------------------------------------------------------------------------------------
 constexpr int GN_ROWS_PER_BLOCK = 2048;
 
@@ -280,7 +284,7 @@ constexpr int GN_ROWS_PER_BLOCK = 2048;
 template <int XF32>   // storage kind of x (SVR_STORE_*: 0 bf16, 1 fp32, 2 h16)
 __global__ __launch_bounds__(256) void groupnorm_stats_kernel(const void* __restrict__ x, double2* __restrict__ partial,
                                                               int64_t HW, int C, int groups) {
-    __shared__ float red[256][4];
+    __shared__ double red[256][4];
     __shared__ double qsum[128][2];                 // per 4-channel quad (C/4 <= 128)
     const int t = blockIdx.y;
     const int cchunks = C >> 3;                     // 16-byte chunks per row
@@ -289,15 +293,13 @@ __global__ __launch_bounds__(256) void groupnorm_stats_kernel(const void* __rest
     const int rstep = 256 / cchunks;
     const int64_t r0 = (int64_t)blockIdx.x * GN_ROWS_PER_BLOCK;
     const int64_t r1 = min(r0 + GN_ROWS_PER_BLOCK, HW);
-    float s0 = 0.f, s1 = 0.f, q0 = 0.f, q1 = 0.f;
+    double s0 = 0.0, s1 = 0.0, q0 = 0.0, q1 = 0.0;
     const int64_t base = ((int64_t)t * HW) * C + cc * 8;
     for (int64_t r = r0 + tid / cchunks; r < r1; r += rstep) {
         float f[8];
         load8<XF32>(x, base + r * C, f);
-        s0 += f[0] + f[1] + f[2] + f[3];
-        q0 += f[0] * f[0] + f[1] * f[1] + f[2] * f[2] + f[3] * f[3];
-        s1 += f[4] + f[5] + f[6] + f[7];
-        q1 += f[4] * f[4] + f[5] * f[5] + f[6] * f[6] + f[7] * f[7];
+        gn_accumulate4(s0, q0, f[0], f[1], f[2], f[3]);
+        gn_accumulate4(s1, q1, f[4], f[5], f[6], f[7]);
     }
     red[tid][0] = s0; red[tid][1] = q0; red[tid][2] = s1; red[tid][3] = q1;
     __syncthreads();
@@ -305,8 +307,8 @@ __global__ __launch_bounds__(256) void groupnorm_stats_kernel(const void* __rest
         const int c = tid >> 1, h = tid & 1;
         double s = 0.0, q = 0.0;
         for (int j = 0; j < rstep; ++j) {
-            s += (double)red[j * cchunks + c][2 * h];
-            q += (double)red[j * cchunks + c][2 * h + 1];
+            s += red[j * cchunks + c][2 * h];
+            q += red[j * cchunks + c][2 * h + 1];
         }
         qsum[tid][0] = s; qsum[tid][1] = q;
     }

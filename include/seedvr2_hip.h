@@ -112,7 +112,8 @@ typedef struct svr_gemm_args {
      * launch is served by the LDS-halo conv kernel (svr_gemm_gn_blocks(args) > 0) every workgroup writes
      * the (sum, sum of squares) of its patch per group to gn_partial[frame][block][group] (fp64 pairs,
      * svr_gemm_gn_blocks() blocks per frame); svr_groupnorm_reduce() turns them into `stats`.  Fixed
-     * reduction order, like svr_groupnorm_stats.  NULL / 0: off.                                          */
+     * reduction order and fp64 accumulation from the first add on, like svr_groupnorm_stats (same accuracy
+     * guarantee).  NULL / 0: off.                                                                         */
     void* gn_partial;
     int32_t gn_groups;
     /* Optional (conv mode, 3x3 spatial taps, stride 1, Cin % 32 == 0, N % 128 == 0): the same weights in
@@ -225,7 +226,14 @@ int svr_unpatchify_euler(const void* pred, int64_t ldp, const void* x_t, void* o
 /* Per-frame GroupNorm statistics over NDHWC.  causal_inflation_lib.py:366-408.
  * x bf16 (fp32 if x_f32) [T, HW, C]; stats fp64 [T, groups, 2] (sum, sumsq), fully overwritten.  Reductions run in a
  * fixed order (no atomics): bit-reproducible, independent of temporal slicing.  `workspace` is a
- * caller-provided scratch of svr_groupnorm_workspace_bytes(T, HW, groups) bytes.                    */
+ * caller-provided scratch of svr_groupnorm_workspace_bytes(T, HW, groups) bytes.
+ * Accuracy: svr_groupnorm_apply forms var = sumsq / n - (sum / n)^2, which cancels rho^2 = (mean / std)^2 of the
+ * sums' digits.  The sums are therefore accumulated in fp64 from the first add on (a stored value and its square are
+ * exact in fp64; here and in the statistics fused into the conv epilogues, svr_gemm_args.gn_partial), so that
+ *     |var - var_exact| <= 2^-9 (var_exact + eps)   -- rstd to 2^-10, a quarter of one bf16 store roundoff --
+ * holds for every group with |mean| / std <= 1024 (and far beyond: the error is ~ n_chain 2^-53 rho^2), var_exact the
+ * two-pass variance of the stored values; a constant group gives var = 0, never a negative value.
+ * tests/test_gpu_conditioning.py holds both paths to it.                                            */
 int64_t svr_groupnorm_workspace_bytes(int32_t T, int64_t HW, int32_t groups);
 int svr_groupnorm_stats(const void* x, double* stats, void* workspace, int32_t T, int64_t HW, int32_t C,
                         int32_t groups, int32_t x_f32, void* stream);

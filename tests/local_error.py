@@ -126,7 +126,7 @@ def check(name, got, want, bound, mask=None, before=None):
 
 # ------------------------------------------------------------------------------------------------ GEMM / implicit-GEMM conv
 def gemm_reference(A, W, out, *, N, K, M=None, bias=None, epilogue=EPI_BIAS, gate=None, resid=None, conv=None, ps=None,
-                   phase=None, **_launch_only):
+                   phase=None, abs_err=0.0, **_launch_only):
     """fp64 result and bound of one ``gemm`` launch (same keywords as HipOps.gemm), laid out like ``out``:
     -> (want, bound, mask); mask = the elements the launch writes (the index maps -- pixel shuffle, drop_first, phase scatter --
     are applied to the fp64 result exactly as tests/ops_reference.py applies them to the fp32 one).
@@ -136,7 +136,9 @@ def gemm_reference(A, W, out, *, N, K, M=None, bias=None, epilogue=EPI_BIAS, gat
     K = kt kh kw Cin for a conv.  gamma_K = K u32 is the textbook bound of a K-term fp32 dot product; the factor 2 covers an MFMA
     block, whose internal adds are not individually rounded to nearest.  Through SiLU / tanh-GELU the pre-activation bound is
     multiplied by the activation's Lipschitz constant and 8 u32 |want| is added for fast_exp2 / v_rcp; SwiGLU = silu(g) * i takes
-    the product rule |i| L b_g + |silu(g)| b_i + L b_g b_i."""
+    the product rule |i| L b_g + |silu(g)| b_i + L b_g b_i.
+    ``abs_err``: an absolute term on the value before the store -- 2^-126 where a test drives results into fp32's denormal range,
+    which the hardware may flush to zero (SwiGLU: times 1 + |i|, a flushed gate is multiplied by i)."""
     if phase is not None and getattr(phase, "quad", None) is not None:
         want = torch.full(out.shape, float("nan"), dtype=F64, device=out.device)
         bound = torch.zeros(out.shape, dtype=F64, device=out.device)
@@ -160,7 +162,7 @@ def gemm_reference(A, W, out, *, N, K, M=None, bias=None, epilogue=EPI_BIAS, gat
         g, i, bg, bi = a4[:, :, 0], a4[:, :, 1], c * s4[:, :, 0], c * s4[:, :, 1]
         sg = F.silu(g)
         want = (sg * i).reshape(M, N // 2)
-        b = (i.abs() * LIP_SILU * bg + sg.abs() * bi + LIP_SILU * bg * bi).reshape(M, N // 2) + APPROX * want.abs()
+        b = (i.abs() * LIP_SILU * bg + sg.abs() * bi + LIP_SILU * bg * bi + abs_err * (1.0 + i.abs())).reshape(M, N // 2) + APPROX * want.abs()
     else:
         brow = gemm_bias_rows(bias, N, conv, phase, F64, acc.device)
         want = acc + brow
@@ -179,6 +181,7 @@ def gemm_reference(A, W, out, *, N, K, M=None, bias=None, epilogue=EPI_BIAS, gat
                 r = values(resid.reshape(M, -1)[:, :N])
                 want = want + r
                 b = b + c * r.abs()
+        b = b + abs_err
     b = store_bound(want, b, out.dtype)
     full_w = torch.full(out.shape, float("nan"), dtype=F64, device=out.device)
     full_b = torch.zeros(out.shape, dtype=F64, device=out.device)
@@ -314,6 +317,23 @@ def check_groupnorm_stats(got, x, groups, *, name="groupnorm_stats", slab_rows=N
     return check(name, got, want, bound)
 
 
+def _groupnorm_apply_from(x, mean, rstd, gamma, beta, silu, out_dtype):
+    """want and bound of the apply pass for fp64 ``mean`` / ``rstd`` [T, groups] (groupnorm_apply_reference states the bound);
+    also the normalised value (x - mean) rstd gamma before beta."""
+    T, H, W, C = x.shape
+    cpg = C // mean.shape[1]
+    mean_c = mean.repeat_interleave(cpg, dim=1)[:, None, None, :]
+    rstd_c = rstd.repeat_interleave(cpg, dim=1)[:, None, None, :]
+    xf, g, b = values(x), gamma.to(F64), beta.to(F64)
+    norm = (xf - mean_c) * rstd_c * g
+    y = norm + b
+    acc = _row_bound(1, (xf.abs() + mean_c.abs()) * rstd_c * g.abs() + b.abs())
+    if silu:
+        y = F.silu(y)
+        acc = LIP_SILU * acc + APPROX * y.abs()
+    return y, store_bound(y, acc, out_dtype), norm
+
+
 def groupnorm_apply_reference(x, stats, gamma, beta, groups, eps, silu, out_dtype=torch.bfloat16, hw_total=None):
     """y = act((x - mean) rstd gamma + beta) from the GIVEN fp64 statistics (``hw_total``: rows of the whole frame when ``x`` is
     a slab of it).  The kernel evaluates x a + b with a = gamma rstd, b = beta - mean a in fp32, no reduction (n = 1):
@@ -325,15 +345,7 @@ def groupnorm_apply_reference(x, stats, gamma, beta, groups, eps, silu, out_dtyp
     mean = stats[..., 0].to(F64) / n
     var = (stats[..., 1].to(F64) / n - mean * mean).clamp_min(0)
     rstd = 1.0 / torch.sqrt(var + float(torch.tensor(eps, dtype=torch.float32)))
-    mean_c = mean.repeat_interleave(cpg, dim=1)[:, None, None, :]
-    rstd_c = rstd.repeat_interleave(cpg, dim=1)[:, None, None, :]
-    xf, g, b = values(x), gamma.to(F64), beta.to(F64)
-    y = (xf - mean_c) * rstd_c * g + b
-    acc = _row_bound(1, (xf.abs() + mean_c.abs()) * rstd_c * g.abs() + b.abs())
-    if silu:
-        y = F.silu(y)
-        acc = LIP_SILU * acc + APPROX * y.abs()
-    return y, store_bound(y, acc, out_dtype)
+    return _groupnorm_apply_from(x, mean, rstd, gamma, beta, silu, out_dtype)[:2]
 
 
 def check_groupnorm_apply(got, x, stats, gamma, beta, groups, eps, silu, *, name="groupnorm_apply", slab_rows=None):
@@ -347,6 +359,67 @@ def check_groupnorm_apply(got, x, stats, gamma, beta, groups, eps, silu, *, name
             want, bound = groupnorm_apply_reference(x[ts, y0:y0 + step], stats[ts], gamma, beta, groups, eps, silu, got.dtype, H * W)
             tag = name if not slab_rows else f"{name}[frame {t}, rows {y0}..]"
             worst = max(worst, check(tag, got.reshape(x.shape)[ts, y0:y0 + step], want, bound))
+    return worst
+
+
+GN_STATS_REL = 2.0 ** -10             # what the statistics may add to a normalised value: a quarter of one bf16 store roundoff
+
+
+def two_pass_moments(x, groups):
+    """fp64 mean and TWO-PASS variance per (frame, group) of the stored values: mean first (with one correction step: a device
+    reduction may form it as sum * (1 / n), one ulp off), then mean((x - mean)^2) -- no cancellation, whatever mean / std is.
+    -> (mean, var) [T, groups]."""
+    T, H, W, C = x.shape
+    xg = values(x).reshape(T, H * W, groups, C // groups)
+    mean = xg.mean(dim=(1, 3))
+    mean = mean + (xg - mean[:, None, :, None]).mean(dim=(1, 3))                   # (the fp64 mean's own rounding, taken out: a
+    var = (xg - mean[:, None, :, None]).pow(2).mean(dim=(1, 3))                    # constant group has variance 0 EXACTLY)
+    return mean, var
+
+
+def groupnorm_reference(x, gamma, beta, groups, eps, silu, out_dtype=torch.bfloat16):
+    """The COMPOSED GroupNorm (statistics pass + apply pass) against statistics the kernels had no part in: mean and two-pass
+    variance in fp64 from the stored values.  Bound: groupnorm_apply_reference's, evaluated with these exact statistics, plus
+
+        2^-10 |(x - mean) rstd gamma|        (times LIP_SILU under SiLU)
+
+    for the statistics pass.  2^-10 is a REQUIREMENT, not a fit: the statistics may move a normalised value by a quarter of one
+    bf16 store roundoff (2^-8), i.e. rstd by 2^-10 relative, i.e. var + eps by 2^-9 relative -- which check_groupnorm_variance
+    states on the statistics themselves.  -> (want, bound)."""
+    mean, var = two_pass_moments(x, groups)
+    rstd = 1.0 / torch.sqrt(var + float(torch.tensor(eps, dtype=torch.float32)))
+    want, bound, norm = _groupnorm_apply_from(x, mean, rstd, gamma, beta, silu, out_dtype)
+    return want, bound + (LIP_SILU if silu else 1.0) * GN_STATS_REL * norm.abs()
+
+
+def check_groupnorm(got, x, gamma, beta, groups, eps, silu, *, name="groupnorm composed"):
+    want, bound = groupnorm_reference(x, gamma, beta, groups, eps, silu, got.dtype)
+    return check(name, got.reshape(x.shape), want, bound)
+
+
+def check_groupnorm_variance(stats, x, groups, eps, *, name="groupnorm variance"):
+    """The variance the apply pass derives from ``stats`` [T, groups, 2] (E[x^2] - mean^2 in fp64, clamped at 0, as
+    groupnorm_apply_kernel forms it) against the two-pass variance of the stored values:
+
+        |var_stats - var| <= 2^-9 (var + eps)        per (frame, group)
+
+    -> worst |error| / bound.  A failure names the group, its rho = |mean| / std and both variances."""
+    T, H, W, C = x.shape
+    n = float(H * W * (C // groups))
+    mean, var = two_pass_moments(x, groups)
+    eps = float(torch.tensor(eps, dtype=torch.float32))
+    m_s = stats[..., 0].to(F64) / n
+    var_s = (stats[..., 1].to(F64) / n - m_s * m_s).clamp_min(0)
+    bound = 2.0 * GN_STATS_REL * (var + eps)
+    worst, ratio = worst_ratio(var_s, var, bound)
+    _record(name, worst)
+    if worst > 1.0:
+        t, g = divmod(int(ratio.reshape(-1).argmax()), groups)
+        rho = float(mean[t, g].abs() / var[t, g].sqrt().clamp_min(1e-300))
+        raise AssertionError(
+            f"{name}: {int((ratio > 1.0).sum())} of {ratio.numel()} (frame, group) variances exceed 2^-9 (var + eps); worst "
+            f"err/bound {worst:.3g} in frame {t}, group {g} (rho = |mean| / std = {rho:.4g}, mean {float(mean[t, g]):.9g}): variance "
+            f"from the statistics {float(var_s[t, g]):.9g}, two-pass variance {float(var[t, g]):.9g}")
     return worst
 
 

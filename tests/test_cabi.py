@@ -162,6 +162,48 @@ def test_kernel_classifier_on_the_launches_a_vae_tile_issues():
     assert L.svr_gemm_kernel_class(ctypes.byref(a)) == -1 and b"RESID_GATE" in L.svr_last_error()
 
 
+@pytest.mark.skipif(not HAVE_HIPCC, reason="hipcc not available")
+def test_zero_operand_cases_route_to_the_kernel_classes_they_name():
+    """tests/conditioning_cases.py ZERO_OPERAND_CASES (the epilogue sweeps of tests/test_gpu_conditioning.py) name a kernel class per
+    geometry, the (output, residual) storage kinds it has a form for and who serves its activation epilogues: asked of the library's
+    own routing function on shape-only tensors, so that the GPU tests cannot drift onto another kernel unnoticed.  The LDS-halo
+    kernel's epilogue has no tanh-GELU: such a launch must NOT be routed to it (it would store bias-only values)."""
+    import ctypes
+    import conditioning_cases as cc
+    from ops_reference import EPI_RESID_GATE, EPI_SWIGLU
+    ops_mod, hip_lib = sub("ops"), sub("hip_lib")
+    L = hip_lib.lib()
+
+    def route(spec, out_kind, **epi):
+        for k, v in {**cc.OPTION_DEFAULTS, **spec.get("options", {})}.items():
+            assert L.svr_set_option(k.encode(), v) == 0
+        try:
+            A, W, kw, shape = cc.zero_operand_problem(spec, ops_mod, "meta", frag=lambda kind, W, s: torch.empty(W.numel(), dtype=torch.bfloat16, device="meta"))
+            out = torch.empty(shape, dtype=cc.STORE_KINDS[out_kind], device="meta")
+            if "resid" in epi:
+                epi["resid"] = torch.empty(shape, dtype=cc.STORE_KINDS[epi["resid"]], device="meta")
+            a, _ = ops_mod.fill_gemm_args(A, W, out, bias=torch.empty(kw["N"], dtype=torch.float32, device="meta"), out_f32=out_kind != "bf16",
+                                          ptr=lambda t: 0x100000, zeros_ptr=0x100000, **kw, **epi)
+            return hip_lib.KERNEL_CLASSES.get(L.svr_gemm_kernel_class(ctypes.byref(a)), "error")
+        finally:
+            for k, v in cc.OPTION_DEFAULTS.items():
+                L.svr_set_option(k.encode(), v)
+
+    for name, spec in cc.ZERO_OPERAND_CASES.items():
+        for kind in cc.STORE_KINDS:
+            assert route(spec, kind) == spec["cls"], (name, kind)
+        pairs = spec.get("pairs")
+        for o in cc.STORE_KINDS:
+            for r in cc.STORE_KINDS:
+                served = route(spec, o, epilogue=EPI_RESID_GATE, resid=r)
+                assert (served == spec["cls"]) == (pairs is None or (o, r) in pairs), (name, o, r, served)
+        for epi, cls in spec["acts"].items():
+            for kind in spec.get("act_kinds", cc.STORE_KINDS):
+                assert route(spec, kind, epilogue=epi) == cls, (name, epi, kind)
+        if "mnk" in spec:
+            assert route(spec, "bf16", epilogue=EPI_SWIGLU) == spec["cls"], name
+
+
 def test_product_package_never_touches_the_oracle():
     """oracle/ (incl. the byte-compiled reference under oracle/_ref) is test infrastructure: nothing in the product package or
     the CLI may import, open or execute it -- only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg do."""

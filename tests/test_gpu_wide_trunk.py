@@ -122,7 +122,7 @@ def test_conv_subpixel_wide_output_and_statistics(hip, ref, kt, ts, hf, wide):
     assert not torch.isnan(out).any() and rel_err(_ld(out), want) < TOL_F32
     stats = hip.gn_shared_stats(shared)
     ws = ref.groupnorm_stats(out, torch.empty(out.shape[0], G, 2, device="cuda", dtype=torch.float64), G)
-    # (per-thread fp32 partial sums of fp32 values, then fp64: compare as vectors, like the bf16 test of this kernel)
+    # (compare as vectors, like the bf16 test of this kernel)
     assert stats is not None and rel_err(stats[..., 0], ws[..., 0]) < 1e-5 and rel_err(stats[..., 1], ws[..., 1]) < 1e-6
 
 

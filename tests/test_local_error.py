@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import local_error as le
+from conditioning_cases import offset_groups, scaled_rows, act_sweep, ROW_KINDS
 from conftest import sub, rel_err
 from ops_reference import TorchOps, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_RESID_GATE, EPI_SWIGLU, H16, H16_SCALE, _ld, _st
 
@@ -171,6 +172,21 @@ def test_rmsnorm_mod_is_inside_its_bounds(rows, dim, kind):
         assert le.check_rmsnorm_mod(out, x, 1e-5, **kw) <= 1.0
 
 
+@pytest.mark.parametrize("kind", STORES, ids=["bf16", "h16", "fp32"])
+@pytest.mark.parametrize("dim", [2560, 8])
+def test_rmsnorm_mod_is_inside_its_bounds_at_the_magnitudes_of_the_wide_stream(dim, kind):
+    """Rows scaled by 2^-20 / 1 / 2^21, one channel x300, all zero, alone and mixed in a 4-row block (scaled_rows): the fp32
+    arithmetic of the restatement stays inside the (relative) bound at every magnitude -- the inputs of the GPU test are ones a
+    correct fp32 kernel survives."""
+    x, which = scaled_rows(dim, kind)
+    w, sc, sh = (rnd(dim, dtype=F32, seed=s) for s in (1, 2, 3))
+    for kw in (dict(), dict(scale=sc, shift=sh), dict(w=w, scale=sc, shift=sh)):
+        out = ref.rmsnorm_mod(x, torch.empty(x.shape[0], dim, dtype=BF16), 1e-5, **kw)
+        for k, name in enumerate(ROW_KINDS):
+            assert le.check_rmsnorm_mod(out[which == k], x[which == k], 1e-5, name=f"rmsnorm_mod rows {name}", **kw) <= 1.0
+        assert torch.equal(out[which == 4], (sh if "shift" in kw else torch.zeros(dim)).to(BF16).expand(int((which == 4).sum()), dim))
+
+
 def rope_tables(n_pos, n_freq):
     ang = torch.arange(n_pos, dtype=F32)[:, None] * (10000.0 ** (-torch.arange(n_freq, dtype=F32) / n_freq))[None, :]
     return ang.cos().contiguous(), ang.sin().contiguous()
@@ -200,6 +216,20 @@ def test_qknorm_rope_is_inside_its_bounds(heads, n_freq):
         le.check_qknorm_rope(touched, qkv, heads, pos, 5, cos, sin, wq, wk, 1e-5)
 
 
+def test_qknorm_rope_is_inside_its_bounds_at_the_magnitudes_of_the_wide_stream():
+    heads, n_pos, n_freq = 3, 64, 21
+    qkv, which = scaled_rows(3 * heads * 128, BF16)
+    r = torch.arange(qkv.shape[0])
+    pos = torch.stack([r % 7, (r * 7) % n_pos, (r * 13 + 5) % n_pos], -1).to(torch.int16)
+    cos, sin = rope_tables(n_pos, n_freq)
+    wq, wk = rnd(128, dtype=F32, seed=1) + 1, rnd(128, dtype=F32, seed=2) + 1
+    got = ref.qknorm_rope(qkv.clone(), heads, pos, 2, cos, sin, wq, wk, 1e-5)
+    assert bool((got[which == 4][:, :2 * heads * 128] == 0).all())
+    for k, name in enumerate(ROW_KINDS):
+        assert le.check_qknorm_rope(got[which == k], qkv[which == k], heads, pos[which == k], 2, cos, sin, wq, wk, 1e-5,
+                                    name=f"qknorm_rope rows {name}") <= 1.0
+
+
 @pytest.mark.parametrize("kind", STORES, ids=["bf16", "h16", "fp32"])
 @pytest.mark.parametrize("HW,C,groups", [((1, 2047), 128, 32), ((1, 2049), 256, 32), ((3, 1367), 512, 32), ((1, 4097), 128, 16),
                                          ((1, 2048), 128, 8), ((13, 17), 192, 32), ((9, 11), 320, 32), ((7, 5), 24, 3)])
@@ -219,6 +249,91 @@ def test_groupnorm_is_inside_its_bounds(HW, C, groups, kind):
         assert le.check_groupnorm_apply(out, x, stats, gamma, beta, groups, 1e-6, silu, slab_rows=1, name="slabs") <= 1.0
 
 
+def stats_in_kernel_order(x, groups, acc=F32):
+    """groupnorm_stats_kernel's summation order restated (csrc/svr_elementwise.hip): blocks of 2048 rows; thread (row lane j,
+    chunk c) of a block walks the rows r0 + j, r0 + j + rstep, ... (rstep = 256 / (C / 8)) and keeps, per 4-channel quad, a
+    running sum  s += ((f0 + f1) + f2) + f3  and  q += ((f0 f0 + f1 f1) + f2 f2) + f3 f3  in ``acc`` precision; everything behind
+    the thread (row lanes, quads of a group, blocks) is added in fp64.  acc = fp32: the arithmetic of the kernel as it was;
+    acc = fp64: the same order with fp64 accumulators.  -> stats [T, groups, 2] fp64."""
+    T, H, W, C = x.shape
+    HW, rstep = H * W, 256 // (C // 8)
+    f = _ld(x).reshape(T, HW, C // 4, 4).to(acc)
+    out = torch.zeros(T, C // 4, 2, dtype=torch.float64)
+    for r0 in range(0, HW, le.GN_ROWS_PER_BLOCK):
+        blk = f[:, r0:r0 + le.GN_ROWS_PER_BLOCK]
+        pad = -blk.shape[1] % rstep
+        blk = torch.nn.functional.pad(blk, (0, 0, 0, 0, 0, pad)).reshape(T, -1, rstep, C // 4, 4)        # [T, trip, row lane, quad, 4]
+        s = torch.zeros(T, rstep, C // 4, dtype=acc)
+        q = torch.zeros(T, rstep, C // 4, dtype=acc)
+        for trip in range(blk.shape[1]):
+            v = blk[:, trip]
+            s = s + (((v[..., 0] + v[..., 1]) + v[..., 2]) + v[..., 3])
+            q = q + (((v[..., 0] * v[..., 0] + v[..., 1] * v[..., 1]) + v[..., 2] * v[..., 2]) + v[..., 3] * v[..., 3])
+        out += torch.stack([s.double().sum(1), q.double().sum(1)], -1)
+    return out.reshape(T, groups, -1, 2).sum(2)
+
+
+@pytest.mark.parametrize("kind", STORES, ids=["bf16", "h16", "fp32"])
+@pytest.mark.parametrize("H,W", [(37, 41), (64, 64)])
+def test_groupnorm_variance_check_rejects_fp32_stage_on_offset_data(H, W, kind):
+    """check_groupnorm_variance on the statistics kernel's summation order, C = 128, 32 groups, x = std (rho + N(0, 1)):
+    with the fp32 per-thread stage (up to 512 terms) the variance E[x^2] - mean^2 is inside 2^-9 (var + eps) up to rho = 16 and
+    OUTSIDE it at rho = 256 and 1024 (the checker sees what the sums-relative bound of check_groupnorm_stats accepts -- that one
+    passes throughout); with fp64 accumulators in the same order it is inside at every rho.  What survives is therefore decided
+    by the accumulator format alone, not by the reference arithmetic."""
+    T, C, G = 2, 128, 32
+    for std in (1.0, 2.0 ** -6):
+        for rho in (0.5, 16.0, 256.0, 1024.0):
+            x = offset_groups(T, H, W, C, G, rho, std, kind)
+            tag = f"rho {rho} std {std}"
+            wide = stats_in_kernel_order(x, G, torch.float64)
+            assert le.check_groupnorm_variance(wide, x, G, 1e-6, name=f"fp64 accumulators {tag}") <= 1.0
+            narrow = stats_in_kernel_order(x, G, F32)
+            assert le.check_groupnorm_stats(narrow, x, G, name=f"fp32 stage, sums {tag}") <= 1.0
+            if rho <= 16:
+                assert le.check_groupnorm_variance(narrow, x, G, 1e-6, name=f"fp32 stage {tag}") <= 1.0
+            else:
+                with pytest.raises(AssertionError, match="rho = ") as e:
+                    le.check_groupnorm_variance(narrow, x, G, 1e-6, name=f"fp32 stage {tag}")
+                assert "two-pass variance" in str(e.value) and "group" in str(e.value)
+
+
+@pytest.mark.parametrize("kind", STORES, ids=["bf16", "h16", "fp32"])
+def test_groupnorm_composed_reference_on_offset_and_constant_groups(kind):
+    """groupnorm_reference (two-pass statistics) accepts the fp32 restatement of the apply pass fed with exact fp64 sums, at
+    every rho, and rejects it when fed with the fp32-stage statistics at rho = 1024; groups constant at 0 / 1000 / -3e5 have
+    variance 0 exactly and normalise to act(beta)."""
+    T, H, W, C, G = 2, 37, 41, 128, 32
+    gamma, beta = rnd(C, dtype=F32, seed=1) + 1, rnd(C, dtype=F32, seed=2)
+    for rho in (0.5, 16.0, 256.0, 1024.0):
+        x = offset_groups(T, H, W, C, G, rho, 1.0, kind)
+        stats = ref.groupnorm_stats(x, torch.empty(T, G, 2, dtype=torch.float64), G)
+        assert le.check_groupnorm_variance(stats, x, G, 1e-6) <= 1.0
+        for silu in (True, False):
+            out = ref.groupnorm_apply(x, torch.empty(T, H, W, C, dtype=BF16), stats, gamma, beta, G, 1e-6, silu)
+            assert le.check_groupnorm(out, x, gamma, beta, G, 1e-6, silu) <= 1.0
+    bad = stats_in_kernel_order(x, G, F32)                                         # rho = 1024
+    out = ref.groupnorm_apply(x, torch.empty(T, H, W, C, dtype=BF16), bad, gamma, beta, G, 1e-6, False)
+    le.check_groupnorm_apply(out, x, bad, gamma, beta, G, 1e-6, False)            # the reference from the given statistics cannot see it
+    must_fail(lambda: le.check_groupnorm(out, x, gamma, beta, G, 1e-6, False))
+    x = offset_groups(T, H, W, C, G, 0.5, 1.0, F32)
+    for g, v in ((3, 0.0), (4, 1000.0), (17, -3e5)):
+        x[:, :, :, g * 4:g * 4 + 4] = v
+    x = _st(x, torch.empty(0, dtype=kind))
+    stats = ref.groupnorm_stats(x, torch.empty(T, G, 2, dtype=torch.float64), G)
+    assert le.check_groupnorm_variance(stats, x, G, 1e-6) <= 1.0
+    mean, var = le.two_pass_moments(x, G)
+    assert bool((var[:, [3, 4, 17]] == 0).all())
+    for silu in (True, False):
+        want, _ = le.groupnorm_reference(x, gamma, beta, G, 1e-6, silu)
+        b = beta.double()
+        for g in (3, 4, 17):
+            act_b = (torch.nn.functional.silu(b) if silu else b)[g * 4:g * 4 + 4].expand(T, H, W, 4)
+            assert torch.allclose(want[..., g * 4:g * 4 + 4], act_b, rtol=1e-14 if silu else 0.0, atol=0.0)
+        out = ref.groupnorm_apply(x, torch.empty(T, H, W, C, dtype=BF16), stats, gamma, beta, G, 1e-6, silu)
+        assert le.check_groupnorm(out, x, gamma, beta, G, 1e-6, silu) <= 1.0
+
+
 @pytest.mark.parametrize("cols", [4, 260, 16384, 16388])
 def test_softmax_rows_is_inside_its_bounds(cols):
     S = torch.randn(6, cols, generator=torch.Generator().manual_seed(cols)) * 30.0
@@ -226,6 +341,40 @@ def test_softmax_rows_is_inside_its_bounds(cols):
     S[2] = 3.25                                                                    # a row of equal values
     P = ref.softmax_rows(S, torch.empty(6, cols, dtype=BF16), 0.044)
     assert le.check_softmax_rows(P, S, 0.044) <= 1.0
+
+
+@pytest.mark.parametrize("cols", [64, 16388])
+def test_softmax_rows_is_inside_its_bounds_on_wide_score_ranges(cols):
+    scale = 0.044
+    S = torch.randn(5, cols, generator=torch.Generator().manual_seed(cols)) * 30.0
+    S[0] = torch.linspace(-1e4, 1e4, cols) / scale                                # scaled scores span +-1e4
+    S[1], S[2] = 1e4 / scale, -1e4 / scale                                         # rows of equal scores
+    S[3, -1] = 1e4 / scale                                                         # one dominant score in the last column
+    P = ref.softmax_rows(S, torch.empty(5, cols, dtype=BF16), scale)
+    assert le.check_softmax_rows(P, S, scale) <= 1.0
+
+
+@pytest.mark.parametrize("out_dt", STORES, ids=["bf16", "h16", "fp32"])
+def test_activation_sweep_restatement_is_inside_its_bounds(out_dt):
+    """The zero-operand activation launches of tests/test_gpu_conditioning.py, restated: A = 0, bias = the activation sweep.  The
+    fp32 restatement is inside check_gemm's bound with the 2^-126 absolute term wherever the exact result fits the output format;
+    a restatement that flushes results in fp32's denormal range is inside it too -- and outside it without the term."""
+    M, N, K = 5, 256, 64
+    A, W = torch.zeros(M, K, dtype=BF16), rnd(N, K, seed=1)
+    bias = act_sweep().repeat(N // 32)
+    for epi in (EPI_BIAS_SILU, EPI_BIAS_GELU):
+        kw = dict(N=N, K=K, bias=bias, epilogue=epi)
+        out = ref.gemm(A, W, torch.empty(M, N, dtype=out_dt), **kw)
+        want, bound, mask = le.gemm_reference(A, W, out, abs_err=2.0 ** -126, **kw)
+        fits = want.abs() < (65504.0 * 64 * (1 - 2.0 ** -11) if out_dt == H16 else 3.3e38)
+        assert not bool(torch.isnan(_ld(out)).any())
+        assert le.check(f"epilogue {epi}", out, want, bound, mask & fits) <= 1.0
+        if out_dt == F32:
+            flushed = torch.where(out.abs() < 2.0 ** -126, torch.zeros_like(out), out)
+            assert not torch.equal(flushed, out)
+            assert le.check(f"epilogue {epi}, flushed", flushed, want, bound, mask & fits) <= 1.0
+            want, bound, mask = le.gemm_reference(A, W, out, **kw)
+            must_fail(lambda: le.check(f"epilogue {epi}, flushed, no absolute term", flushed, want, bound, mask & fits))
 
 
 def test_rows_mean_and_unpatchify_are_inside_their_bounds():
