@@ -15,6 +15,7 @@
 #include "svr_attn.hip"
 #include "svr_elementwise.hip"
 #include "svr_calibrate.hip"
+#include "svr_alpha.hip"
 
 using namespace svr;
 
@@ -367,5 +368,73 @@ int svr_affine_slice(const void* in, void* out, int64_t rows, int32_t c_in, int3
                        (const bf16_t*)in, (bf16_t*)out, rows, c_in, c_out, scale, shift);
     return check(hipGetLastError(), "svr_affine_slice");
 }
+
+// ---- edge-guided alpha upscaling (svr_alpha.hip).  Workspace: [flags 4 | maxima T, padded to 4 | n map T*H*W] int32.
+static inline int64_t alpha_header_ints(int32_t T) { return 4 + ((int64_t)T + 3) / 4 * 4; }
+
+int64_t svr_alpha_workspace_bytes(int32_t T, int32_t H, int32_t W) {
+    if (T < 1 || H < 2 || W < 2) return 0;
+    return (alpha_header_ints(T) + (int64_t)T * H * W) * 4;
+}
+
+static const char* alpha_args_error(const void* rgb, int32_t T, int32_t H, int32_t W, int64_t ld_px, int32_t rgb_kind,
+                                    const void* workspace, int64_t workspace_bytes) {
+    if (!rgb || !workspace) return "null pointer";
+    if (T < 1 || T > 65535 || H < 2 || W < 2) return "need 1 <= T <= 65535, H >= 2, W >= 2";
+    if (ld_px < 3) return "ld_px (elements between pixels) must be >= 3";
+    if (rgb_kind != SVR_STORE_BF16 && rgb_kind != SVR_STORE_FP32) return "rgb_kind must be SVR_STORE_BF16 or SVR_STORE_FP32";
+    if (workspace_bytes < svr_alpha_workspace_bytes(T, H, W)) return "workspace shorter than svr_alpha_workspace_bytes()";
+    return nullptr;
+}
+#define SVR_ALPHA_REFUSE(name, why) do { snprintf(g_err, sizeof(g_err), "%s: %s", name, why); return -1; } while (0)
+
+int svr_alpha_stats(const float* alpha_lo, int64_t n_alpha, const void* rgb, int32_t T, int32_t H, int32_t W, int64_t ld_px,
+                    int32_t rgb_kind, void* workspace, int64_t workspace_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const char* why = alpha_args_error(rgb, T, H, W, ld_px, rgb_kind, workspace, workspace_bytes);
+    if (!why && !alpha_lo) why = "null pointer";
+    if (!why && (n_alpha < 1 || n_alpha > 0x7fffffff)) why = "need 1 <= n_alpha < 2^31 (the counts are int32)";
+    if (why) SVR_ALPHA_REFUSE("svr_alpha_stats", why);
+    int* flags = (int*)workspace;
+    if (int rc = check(hipMemsetAsync(flags, 0, (size_t)alpha_header_ints(T) * 4, (hipStream_t)stream), "svr_alpha_stats")) return rc;
+    const int64_t n_px = (int64_t)T * H * W;
+    const unsigned grid = std::min<unsigned>(blocks_for(std::max(n_px, n_alpha), 256 * 8), (unsigned)device_cu_count() * 8);
+    if (rgb_kind == SVR_STORE_FP32) hipLaunchKernelGGL(alpha_stats_kernel<SVR_STORE_FP32>, dim3(grid), dim3(256), 0, (hipStream_t)stream, alpha_lo, n_alpha, rgb, n_px, ld_px, flags);
+    else hipLaunchKernelGGL(alpha_stats_kernel<SVR_STORE_BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, alpha_lo, n_alpha, rgb, n_px, ld_px, flags);
+    return check(hipGetLastError(), "svr_alpha_stats");
+}
+
+int svr_alpha_edges(const void* rgb, int32_t T, int32_t H, int32_t W, int64_t ld_px, int32_t rgb_kind, void* workspace,
+                    int64_t workspace_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const char* why = alpha_args_error(rgb, T, H, W, ld_px, rgb_kind, workspace, workspace_bytes);
+    if (why) SVR_ALPHA_REFUSE("svr_alpha_edges", why);
+    int* flags = (int*)workspace;
+    int* maxima = flags + 4;
+    int* nmap = flags + alpha_header_ints(T);
+    const dim3 grid(blocks_for(W, ALPHA_TILE), blocks_for(H, ALPHA_TILE), T);
+    if (grid.y > 65535u) SVR_ALPHA_REFUSE("svr_alpha_edges", "H beyond 65535 tiles");
+    if (rgb_kind == SVR_STORE_FP32) hipLaunchKernelGGL(alpha_edges_kernel<SVR_STORE_FP32>, grid, dim3(256), 0, (hipStream_t)stream, rgb, ld_px, H, W, flags, nmap, maxima);
+    else hipLaunchKernelGGL(alpha_edges_kernel<SVR_STORE_BF16>, grid, dim3(256), 0, (hipStream_t)stream, rgb, ld_px, H, W, flags, nmap, maxima);
+    return check(hipGetLastError(), "svr_alpha_edges");
+}
+
+int svr_alpha_refine(const void* rgb, const float* base, float* out, uint8_t* edge_out, int32_t T, int32_t H, int32_t W,
+                     int64_t ld_px, int32_t rgb_kind, int64_t n_alpha, const void* workspace, int64_t workspace_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const char* why = alpha_args_error(rgb, T, H, W, ld_px, rgb_kind, workspace, workspace_bytes);
+    if (!why && (!base || !out)) why = "null pointer";
+    if (!why && (n_alpha < 1 || n_alpha > 0x7fffffff)) why = "need 1 <= n_alpha < 2^31 (the counts are int32)";
+    if (why) SVR_ALPHA_REFUSE("svr_alpha_refine", why);
+    const int* flags = (const int*)workspace;
+    const int* maxima = flags + 4;
+    const int* nmap = flags + alpha_header_ints(T);
+    const dim3 grid(blocks_for(W, ALPHA_TILE), blocks_for(H, ALPHA_TILE), T);
+    if (grid.y > 65535u) SVR_ALPHA_REFUSE("svr_alpha_refine", "H beyond 65535 tiles");
+    if (rgb_kind == SVR_STORE_FP32) hipLaunchKernelGGL(alpha_refine_kernel<SVR_STORE_FP32>, grid, dim3(256), 0, (hipStream_t)stream, rgb, ld_px, base, H, W, (float)n_alpha, flags, nmap, maxima, out, edge_out);
+    else hipLaunchKernelGGL(alpha_refine_kernel<SVR_STORE_BF16>, grid, dim3(256), 0, (hipStream_t)stream, rgb, ld_px, base, H, W, (float)n_alpha, flags, nmap, maxima, out, edge_out);
+    return check(hipGetLastError(), "svr_alpha_refine");
+}
+#undef SVR_ALPHA_REFUSE
 
 }  // extern "C"

@@ -88,6 +88,10 @@ SYMBOLS = {
     "svr_blend_accumulate": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp]),
     "svr_blend_finalize": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _f, _f, _vp]),
     "svr_affine_slice": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _f, _f, _vp]),
+    "svr_alpha_workspace_bytes": (C.c_int64, [_i32, _i32, _i32]),
+    "svr_alpha_stats": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i64, _i32, _vp, _i64, _vp]),
+    "svr_alpha_edges": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i32, _vp, _i64, _vp]),
+    "svr_alpha_refine": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _i64, _vp]),
     "svr_set_option": (C.c_int, [C.c_char_p, _i32]),
     "svr_mfma_calibrate_workspace_bytes": (C.c_int64, []),
     "svr_mfma_calibrate": (C.c_int, [_vp, _i32, C.POINTER(C.c_double), _vp]),

@@ -326,7 +326,8 @@ class SeedVR2VideoUpscaler(io.ComfyNode):
         """image [N, H, W, C] in [0, 1] -> upscaled [N, H', W', C] in [0, 1] (video_upscaler.py:227-260)."""
         from . import pipeline
         if image.shape[-1] == 4:
-            raise NotImplementedError("RGBA input: the alpha path is outside the MI355X hot path (DESIGN.md section 8); pass RGB frames")
+            raise NotImplementedError("RGBA input is not wired into this node yet: pipeline.upscale and inference_cli.py upscale "
+                                      "four-channel clips (edge-guided alpha, alpha.py); pass RGB frames here (INTEGRATION.md)")
         runner = get_runner(dit, vae)
         text = load_text_embedding(runner.dit.device)
         out = pipeline.upscale(image, runner, text, resolution=resolution, max_resolution=max_resolution,

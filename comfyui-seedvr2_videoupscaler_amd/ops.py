@@ -492,3 +492,47 @@ class HipOps:
         hip_lib.check(self.lib.svr_affine_slice(_ptr(inp), _ptr(out), rows, c_in, c_out, scale, shift, self._stream()),
                       "svr_affine_slice")
         return out
+
+    # ------------------------------------------------------------------ alpha channel
+    def alpha_upscale(self, rgb_thwc, alpha_lo, out=None, base=None, edge_out=None):
+        """Edge-guided alpha upscaling (alpha.py is the specification; csrc/svr_alpha.hip): rgb [T, H, W, >= 3] fp32 / bf16, the
+        upscaled frames of ONE batch as the decoder left them (pixel stride taken as is), alpha_lo [T, h, w] -> fp32 [T, H, W].
+        The bicubic base is torch glue on the device (``base``: a precomputed one); three launches on the current stream, no host
+        synchronisation.  ``edge_out``: optional uint8 [T, H, W] receiving the edge bytes."""
+        from . import alpha as alpha_mod
+        if rgb_thwc.dim() != 4 or rgb_thwc.shape[-1] < 3 or rgb_thwc.dtype not in (torch.float32, BF16):
+            raise ValueError("alpha_upscale: rgb must be [T, H, W, >= 3] in fp32 or bf16")
+        T, H, W, _ = rgb_thwc.shape
+        ld = rgb_thwc.stride(2)
+        if rgb_thwc.device.type != "cuda" or rgb_thwc.stride(3) != 1 or ld < 3 or rgb_thwc.stride(1) != W * ld or \
+                rgb_thwc.stride(0) != H * W * ld:
+            raise ValueError("alpha_upscale: rgb must live on the device with dense frames (channel-last, any pixel stride >= 3)")
+        if alpha_lo.dim() != 3 or alpha_lo.shape[0] != T:
+            raise ValueError("alpha_upscale: alpha_lo must be [T, h, w] with rgb's frame count")
+        alpha_lo = self._chk(alpha_lo.to(device=rgb_thwc.device, dtype=torch.float32).contiguous(), torch.float32, "alpha_lo")
+        if base is None:
+            base = alpha_mod.bicubic_base(alpha_lo, H, W)
+        base = self._chk(base.contiguous(), torch.float32, "base")
+        if tuple(base.shape) != (T, H, W):
+            raise ValueError("alpha_upscale: base must be [T, H, W]")
+        if out is None:
+            out = torch.empty(T, H, W, dtype=torch.float32, device=self.device)
+        self._chk(out, torch.float32, "out")
+        if tuple(out.shape) != (T, H, W):
+            raise ValueError("alpha_upscale: out must be [T, H, W]")
+        if edge_out is not None:
+            self._chk(edge_out, torch.uint8, "edge_out")
+            if tuple(edge_out.shape) != (T, H, W):
+                raise ValueError("alpha_upscale: edge_out must be [T, H, W]")
+        kind = 1 if rgb_thwc.dtype == torch.float32 else 0                   # SVR_STORE_FP32 / SVR_STORE_BF16
+        nbytes = int(self.lib.svr_alpha_workspace_bytes(T, H, W))
+        if nbytes <= 0:
+            raise ValueError("alpha_upscale: need T >= 1 and frames of at least 2 x 2 pixels")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        rgb_p, ws_p, n_alpha = _ptr(rgb_thwc), _ptr(ws), alpha_lo.numel()
+        hip_lib.check(self.lib.svr_alpha_stats(_ptr(alpha_lo), n_alpha, rgb_p, T, H, W, ld, kind, ws_p, nbytes, self._stream()),
+                      "svr_alpha_stats")
+        hip_lib.check(self.lib.svr_alpha_edges(rgb_p, T, H, W, ld, kind, ws_p, nbytes, self._stream()), "svr_alpha_edges")
+        hip_lib.check(self.lib.svr_alpha_refine(rgb_p, _ptr(base), _ptr(out), self._opt(edge_out, torch.uint8, "edge_out"), T, H, W, ld,
+                                                kind, n_alpha, ws_p, nbytes, self._stream()), "svr_alpha_refine")
+        return out

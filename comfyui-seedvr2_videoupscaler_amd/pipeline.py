@@ -10,6 +10,8 @@ Mirrors ``encode_all_batches -> upscale_all_batches -> decode_all_batches -> pos
     optional latent noise through the schedule (:680-697), ``get_condition(task="sr")``, one DiT step;
   * decode, trim to the original batch length and to ``true_target_dims`` (:953-968), Hann blend of the
     overlapping frames (:973-1000), write into the preallocated output;
+  * for RGBA input, the alpha of every written span from the decoded frames in their [-1, 1] state BEFORE colour correction
+    (:1143-1217 -> alpha.py), phases 1-3 and the colour fix seeing the RGB channels only;
   * colour correction against the re-transformed input (:1255-1320), ``[-1, 1] -> [0, 1]`` (:1348).
 
 Differences by design (MI355X-first, results unchanged): nothing leaves the GPU between phases (the reference
@@ -22,7 +24,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import colorfix, transforms
+from . import alpha as alpha_mod, colorfix, transforms
 
 
 @dataclass
@@ -98,6 +100,9 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
             exchange_heads: Optional[Callable[[dict, list, tuple, torch.dtype], dict]] = None,
             return_spans: bool = False, skip_trimmed_frames: bool = True, output_dtype: Optional[torch.dtype] = torch.float32):
     """images [T, H, W, 3] in [0, 1] (any float dtype, on the runner's device) -> upscaled [T, H', W', 3] in [0, 1].
+    [T, H, W, 4] (RGBA) -> [T, H', W', 4]: the RGB channels exactly as for the three-channel clip, the fourth the edge-guided
+    upscaled alpha (alpha.py) of each owned span, computed from the span's decoded frames and the input alpha of the same clip
+    frames; frames of spans this rank does not own stay zero in all four channels.
 
     ``batch_filter(i)`` restricts phases 1-3 to the temporal batches a rank owns (data parallelism over
     batches); frames of skipped batches are left at zero for the caller's all-gather/sum.
@@ -107,8 +112,8 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
     4K clip: 12.7 GB per rank, 1.6 GB per rank on the wire at 8 ranks -- sized for 288 GB of HBM); ``output_dtype=None`` keeps the
     engines' activation dtype (bf16) as the reference's phase code does, for clips where that matters more than the 0.7 dB.
     """
-    if images_thwc.shape[-1] != 3:
-        raise NotImplementedError("RGB input only (the alpha path is outside the hot path, DESIGN.md section 7)")
+    if images_thwc.dim() != 4 or images_thwc.shape[-1] not in (3, 4):
+        raise ValueError(f"images must be [T, H, W, 3] (RGB) or [T, H, W, 4] (RGBA), got {tuple(images_thwc.shape)}")
     # compute / storage dtype of the phases = the engines' activation dtype (bf16 on the HIP path, as the reference's
     # compute_dtype; fp32 when the CPU tests drive the engines with the fp32 torch double of the C ABI)
     dev, dt = runner.dit.device, getattr(getattr(runner.dit, "ops", None), "act_dtype", torch.bfloat16)
@@ -120,6 +125,10 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
     images = images_thwc.to(device=dev)
     if prepend_frames > 0:
         images = transforms.pad_video_temporal(images, count=prepend_frames, temporal_dim=0, prepend=True)
+    alpha_in = None
+    if images.shape[-1] == 4:
+        # (the RGB copy has the strides of a three-channel clip, so phases 1-3 and the colour fix compute the same bits)
+        alpha_in, images = images[..., 3], images[..., :3].contiguous()
     total = images.shape[0]
     true_h, true_w = transforms.true_target_dims(images.shape[1], images.shape[2], resolution, max_resolution)
     plans, overlap = plan_batches(total, batch_size, temporal_overlap, uniform_batch_size)
@@ -214,10 +223,15 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
                 w = starts[i]
                 final[w - overlap:w] = transforms.blend_overlapping_frames(final[w - overlap:w], head.to(final), overlap)
 
-    # ---- phase 4: colour correction against the re-transformed input, [-1, 1] -> [0, 1]
+    # ---- phase 4: alpha from the frames as decoded (before colour correction, the reference's order), then colour correction
+    # against the re-transformed input, [-1, 1] -> [0, 1].  A span's frames in ``final`` ARE clip frames w0..w1 (overlap heads are
+    # trimmed before the write), so its alpha is guided by the input alpha of exactly those frames.
+    alpha_out = torch.zeros(total, true_h, true_w, dtype=odt, device=dev) if alpha_in is not None else None
     for i, (w0, w1) in spans.items():
         if w1 <= w0:
             continue
+        if alpha_in is not None:
+            alpha_out[w0:w1] = alpha_mod.upscale_alpha(final[w0:w1], alpha_in[w0:w1], getattr(runner.dit, "ops", None)).to(odt)
         sample = final[w0:w1].permute(0, 3, 1, 2)
         if color_correction != "none":
             ref = prepare_batch(images, plans[i], resolution, max_resolution).to(odt).permute(1, 0, 2, 3)   # T C H W
@@ -228,6 +242,8 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
                 raise ValueError(f"Unknown color correction method: {color_correction}")
             sample = colorfix.METHODS[color_correction](sample, ref)
         final[w0:w1] = sample.permute(0, 2, 3, 1).clamp(-1, 1).mul(0.5).add(0.5).to(odt)
+    if alpha_out is not None:
+        final = torch.cat([final, alpha_out.unsqueeze(-1)], dim=-1)
     if prepend_frames > 0:
         final = final[prepend_frames:]
         spans = {i: (max(a - prepend_frames, 0), max(b - prepend_frames, 0)) for i, (a, b) in spans.items()}

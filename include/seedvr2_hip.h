@@ -24,7 +24,9 @@ extern "C" {
  * svr_set_option keys "gemm_asym", "gn_grid_cap", attn_variant 5..10 and gemm_w4r = 2 are gone (measured, deleted); "conv_thinout16" became "conv_thinout4" (1 default: N <= 4 thin-output
  * convs on conv_thinout4_kernel, 0: on the 32-cout kernel).  No signature changed.
  * v9 (round 6): + svr_mfma_calibrate() / svr_mfma_calibrate_workspace_bytes() (measurement aid, not on the data path); a thin-output
- * conv with N <= 4 couts accepts an exact [N, K] weight (the 4-row units take rows >= N from the zero page).  No signature changed. */
+ * conv with N <= 4 couts accepts an exact [N, K] weight (the 4-row units take rows >= N from the zero page).  No signature changed.
+ * v9, additive: + svr_alpha_workspace_bytes() / svr_alpha_stats() / svr_alpha_edges() / svr_alpha_refine() (edge-guided alpha
+ * upscaling).  New symbols only -- nothing that existed changed, so the version number stays 9. */
 #define SVR_ABI_VERSION 9
 
 /* ---- GEMM / implicit-GEMM convolution epilogues ------------------------------------------ */
@@ -264,6 +266,30 @@ int svr_blend_finalize(const float* acc, const float* cnt, void* out, int32_t T,
 /* out[r, :c_out] = (in[r, :c_out] - shift) * scale   (latent (de)scaling + mean slice, infer.py:188, 236). */
 int svr_affine_slice(const void* in, void* out, int64_t rows, int32_t c_in, int32_t c_out,
                      float scale, float shift, void* stream);
+
+/* ---- edge-guided alpha upscaling ----------------------------------------------------------- */
+/* alpha_upscaling.py:289-438 edge_guided_alpha_upscale(method='guided') for one batch of frames, after the bicubic base
+ * (F.interpolate, torch glue): rgb [T, H, W, >= 3] (fp32 or bf16: rgb_kind SVR_STORE_FP32 / SVR_STORE_BF16; ld_px elements from
+ * one pixel to the next, frames dense) is the UPSCALED clip in [-1, 1] or [0, 1], alpha_lo the n_alpha input-resolution alpha
+ * values (fp32), base the bicubic upsample [T, H, W] fp32, out [T, H, W] fp32.  Call the three in this order on one stream; no call
+ * synchronises with the host: what the data decides (binary matte or not = radius 2 + snapping or radius 3, whether the rgb is
+ * normalised (x + 1) / 2 once (min < 0) and, for the edge detector only, twice (min < -1), each frame's Sobel maximum) is left in
+ * `workspace` by one kernel and read there by the next.  Integer atomics only: same bits on every run.
+ * workspace: svr_alpha_workspace_bytes(T, H, W) bytes of device memory, [flags: int32 x 4 | maxima: int32 x T (padded to 4) |
+ * n map: int32 x T*H*W]; every call checks workspace_bytes against it.  1 <= T <= 65535, H >= 2, W >= 2 (BORDER_REFLECT_101).  */
+int64_t svr_alpha_workspace_bytes(int32_t T, int32_t H, int32_t W);
+/* flags = {count(alpha_lo < 0.1), count(alpha_lo > 0.9), min(rgb) < 0, min(rgb) < -1}; clears the maxima. */
+int svr_alpha_stats(const float* alpha_lo, int64_t n_alpha, const void* rgb, int32_t T, int32_t H, int32_t W, int64_t ld_px,
+                    int32_t rgb_kind, void* workspace, int64_t workspace_bytes, void* stream);
+/* detect_edges_batch (:125-188) up to the division: u8 = trunc(clip(x * 255, 0, 255)), OpenCV's 8-bit RGB2GRAY, 3x3 Sobel with
+ * BORDER_REFLECT_101, n = sx^2 + sy^2 -> n map; per-frame max(n) -> maxima. */
+int svr_alpha_edges(const void* rgb, int32_t T, int32_t H, int32_t W, int64_t ld_px, int32_t rgb_kind, void* workspace,
+                    int64_t workspace_bytes, void* stream);
+/* guided filter (:191-286; zero-padded box means, radius 2 / eps 0.002 for a binary matte, else radius 3) of `base` guided by the
+ * channel mean of the once-normalised rgb, then steps 3-8 (:370-408) for a binary matte, clamp(0, 1) -> out.  The edge byte
+ * trunc(sqrt(n) / sqrt(max n) * 255) (fp64; 0 on a constant frame) goes to edge_out [T, H, W] uint8 unless that is NULL. */
+int svr_alpha_refine(const void* rgb, const float* base, float* out, uint8_t* edge_out, int32_t T, int32_t H, int32_t W,
+                     int64_t ld_px, int32_t rgb_kind, int64_t n_alpha, const void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---- misc ------------------------------------------------------------------------------------ */
 /* Tuning / measurement knobs (no effect on results):

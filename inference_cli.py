@@ -106,7 +106,8 @@ def build_parser() -> argparse.ArgumentParser:
 
 # ---------------------------------------------------------------------------------------------------------
 def load_frames(path: str, skip: int = 0, cap: int = 0):
-    """-> (frames [T, H, W, 3] float32 in [0, 1], fps)."""
+    """-> (frames [T, H, W, 3] float32 in [0, 1], fps); [T, H, W, 4] where the input carries an alpha channel (an image with
+    transparency, a four-channel tensor): pipeline.upscale upscales it edge-guided next to the RGB."""
     import numpy as np
     import torch
     ext = os.path.splitext(path)[1].lower()
@@ -120,7 +121,9 @@ def load_frames(path: str, skip: int = 0, cap: int = 0):
             frames = frames[None]
     elif ext in IMAGE_EXT:
         from PIL import Image
-        frames = torch.from_numpy(np.asarray(Image.open(path).convert("RGB"), dtype=np.float32) / 255.0)[None]
+        img = Image.open(path)
+        has_alpha = img.mode in ("RGBA", "LA", "PA") or "transparency" in img.info
+        frames = torch.from_numpy(np.asarray(img.convert("RGBA" if has_alpha else "RGB"), dtype=np.float32) / 255.0)[None]
     elif ext in VIDEO_EXT:
         try:
             import cv2  # type: ignore
@@ -144,10 +147,11 @@ def load_frames(path: str, skip: int = 0, cap: int = 0):
         frames = frames[:cap]
     if frames.shape[0] == 0:
         raise ValueError("No frames to process")
-    return frames[..., :3].contiguous(), fps
+    return frames[..., :4 if frames.shape[-1] == 4 else 3].contiguous(), fps
 
 
 def save_frames(frames, path: str, fmt: str, fps: float = 30.0):
+    """pt: the tensor as it is; png: RGB or, for four-channel frames, RGBA files; mp4 has no alpha: it is dropped with a warning."""
     import numpy as np
     import torch
     arr = (frames.float().clamp(0, 1) * 255.0).round().to(torch.uint8).cpu().numpy()
@@ -164,6 +168,9 @@ def save_frames(frames, path: str, fmt: str, fps: float = 30.0):
                 Image.fromarray(a).save(os.path.join(path, f"frame_{i:06d}.png"))
     else:
         import cv2  # type: ignore
+        if arr.shape[-1] == 4:
+            print(f"Warning: {fmt} output has no alpha channel; writing RGB only (use --output_format png to keep it)", file=sys.stderr)
+            arr = arr[..., :3]
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         w = cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*"mp4v"), fps, (arr.shape[2], arr.shape[1]))
         for a in arr:
