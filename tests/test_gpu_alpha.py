@@ -14,6 +14,7 @@ import torch
 
 import alpha_reference as ar
 from conftest import sub
+from guarded_out import guarded
 
 pytestmark = pytest.mark.gpu
 BF16 = torch.bfloat16
@@ -43,10 +44,18 @@ def parity_report():
 
 
 def run_kernels(hip, rgb, alpha_lo, base=None):
-    edge = torch.empty(rgb.shape[:3], dtype=torch.uint8, device="cuda")
-    out = hip.alpha_upscale(rgb.cuda(), alpha_lo.cuda(), base=None if base is None else base.cuda(), edge_out=edge)
+    """Both outputs in guarded buffers (tests/guarded_out.py).  The alpha is poisoned with NaN and must be written everywhere; the
+    guard byte 0xA5 = 165 is a legitimate edge byte, so the edge map is not asked for left-over poison -- the tests compare it with
+    the reference's map byte for byte."""
+    shape = tuple(rgb.shape[:3])
+    g_out, g_edge = guarded(shape, torch.float32), guarded(shape, torch.uint8)
+    out = hip.alpha_upscale(rgb.cuda(), alpha_lo.cuda(), out=g_out.t, base=None if base is None else base.cuda(), edge_out=g_edge.t)
     torch.cuda.synchronize()
-    return out.cpu(), edge.cpu()
+    assert out is g_out.t
+    g_out.assert_guards("alpha_upscale out")
+    g_out.assert_written("alpha_upscale out")
+    g_edge.assert_guards("alpha_upscale edge_out")
+    return out.cpu(), g_edge.t.cpu()
 
 
 def restatement_pair(rgb, alpha_lo, base=None):

@@ -7,7 +7,10 @@
   B. Epilogues with a ZERO operand: the accumulator is exactly 0 and the stored value is store(epilogue(bias, resid)) -- a function
      stated exactly here, swept over rounding ties, overflow, the subnormal range of h16 and the saturation points of the fast
      activations, on every kernel class (asserted through record_kernel_class).
-  C. The row-normalising kernels and the row softmax at the magnitudes the wide residual stream allows."""
+  C. The row-normalising kernels and the row softmax at the magnitudes the wide residual stream allows.
+
+Every tensor a svr_* entry point writes comes from tests/guarded_out.py: guard bytes around a payload poisoned with NaN (``init=``
+where the launch gets a view that leaves the buffer's last row out, or works in place)."""
 import math
 
 import pytest
@@ -17,6 +20,7 @@ import local_error as le
 from conditioning_cases import (offset_groups, scaled_rows, bias_sweep, act_sweep, zero_operand_problem, ROW_KINDS, OPTION_DEFAULTS,
                                 STORE_KINDS, ZERO_OPERAND_CASES)
 from conftest import sub
+from guarded_out import Pool, guarded
 from ops_reference import H16, H16_SCALE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_RESID_GATE, EPI_SWIGLU, _ld, _st
 
 pytestmark = pytest.mark.gpu
@@ -36,6 +40,17 @@ def rnd(*shape, scale=1.0, seed=0, dtype=BF16):
     g = torch.Generator(device="cuda").manual_seed(seed + sum(shape))
     v = torch.randn(*shape, generator=g, device="cuda") * scale
     return (v * H16_SCALE).to(H16) if dtype == H16 else v.to(dtype)
+
+
+def nans(*shape, dtype=BF16):
+    return torch.full(shape, float("nan"), device="cuda", dtype=dtype)
+
+
+def checked(g, tag):
+    """a guarded buffer after the launch that owns all of it: guards intact, no poison left -> its tensor"""
+    g.assert_guards(tag)
+    g.assert_written(tag)
+    return g.t
 
 
 def gamma_beta(C):
@@ -60,9 +75,11 @@ def _composed(hip, x, stats, tag, silus=(True, False)):
     gamma, beta = gamma_beta(C)
     checks = [lambda: le.check_groupnorm_variance(stats, x, G, EPS, name=f"variance {tag}")]
     for silu in silus:
-        out = torch.full((T + 1, H, W, C), float("nan"), device="cuda", dtype=BF16)
+        g = guarded((T + 1, H, W, C), BF16, init=nans(T + 1, H, W, C))
+        out = g.t
         hip.groupnorm_apply(x, out[:T], stats, gamma, beta, G, EPS, silu)
         assert bool(torch.isnan(out[T]).all()) and not bool(torch.isnan(out[:T].float()).any()), tag
+        g.assert_guards(f"groupnorm_apply {tag}")
         checks.append(lambda out=out, silu=silu: le.check_groupnorm(out[:T], x, gamma, beta, G, EPS, silu, name=f"composed {tag} silu {silu}"))
     return checks
 
@@ -81,8 +98,9 @@ def test_groupnorm_composed_on_offset_groups(hip, H, W, kind, C, rho):
     checks = []
     for std in (1.0, 2.0 ** -6):
         x = offset_groups(2, H, W, C, G, rho, std, kind, "cuda")
-        stats = torch.empty(2, G, 2, device="cuda", dtype=F64)
-        hip.groupnorm_stats(x, stats, G)
+        g = guarded((2, G, 2), F64)
+        hip.groupnorm_stats(x, g.t, G)
+        stats = checked(g, "groupnorm_stats")
         checks += _composed(hip, x, stats, f"rho {rho} std {std}")
     all_of(checks)
 
@@ -98,16 +116,18 @@ def test_groupnorm_constant_groups(hip, H, W, kind):
     const = ((3, 0.0), (4, 1000.0), (17, -3e5), (31, 1000.0))
     for g, v in const:
         x[..., g * 4:g * 4 + 4] = v
-    x = _st(x, torch.empty(0, dtype=kind, device="cuda"))
+    x = _st(x, torch.empty(0, dtype=kind, device="cuda"))                         # (names the storage kind: no entry point writes it)
     mean, var = le.two_pass_moments(x, G)
     assert bool((var[:, [g for g, _ in const]] == 0).all())
-    stats = torch.empty(T, G, 2, device="cuda", dtype=F64)
-    hip.groupnorm_stats(x, stats, G)
+    gs = guarded((T, G, 2), F64)
+    hip.groupnorm_stats(x, gs.t, G)
+    stats = checked(gs, "groupnorm_stats")
     gamma, beta = gamma_beta(C)
     checks = _composed(hip, x, stats, "constant groups")
     for silu in (True, False):
-        out = torch.empty(T, H, W, C, device="cuda", dtype=BF16)
-        hip.groupnorm_apply(x, out, stats, gamma, beta, G, EPS, silu)
+        go = guarded((T, H, W, C), BF16)
+        hip.groupnorm_apply(x, go.t, stats, gamma, beta, G, EPS, silu)
+        out = checked(go, "groupnorm_apply")
         assert bool(torch.isfinite(out.float()).all())
         b = torch.nn.functional.silu(beta.double()) if silu else beta.double()
         want, _ = le.groupnorm_reference(x, gamma, beta, G, EPS, silu)
@@ -124,13 +144,16 @@ def test_groupnorm_statistics_of_a_frame_do_not_depend_on_the_clip_at_rho_256(hi
     for kind in KINDS:
         for H, W in ((3, 683), (64, 64)):
             x = offset_groups(3, H, W, 128, G, 256.0, 1.0, kind, "cuda")
-            stats, again, one = (torch.empty(n, G, 2, device="cuda", dtype=F64) for n in (3, 3, 1))
+            gout = Pool()
+            stats, again = (gout(3, G, 2, dtype=F64) for _ in range(2))
             hip.groupnorm_stats(x, stats, G)
             hip.groupnorm_stats(x, again, G)
             assert torch.equal(stats, again)
             for t in range(3):
+                one = gout(1, G, 2, dtype=F64)
                 hip.groupnorm_stats(x[t:t + 1].contiguous(), one, G)
                 assert torch.equal(one[0], stats[t]), (kind, H, W, t)
+            gout.check("groupnorm_stats")
 
 
 def _group_bias(free, rho, To):
@@ -167,13 +190,14 @@ def test_conv_halo_fused_statistics_on_offset_outputs(hip, kind, rho):
     geom = opsmod.Conv3dGeom(T, H, W, C, T, H, W, (3, 3, 3), (1, 1, 1), (2, 1, 1), None)
 
     def launch(bias, _):
-        out = torch.empty(T, H, W, C, device="cuda", dtype=kind)
+        g = guarded((T, H, W, C), kind)
         hip.record_kernel_class = True
         try:
-            res = hip.gemm(x, Wp, out, N=C, K=Wp.shape[1], bias=bias, conv=geom, ldc=C, W_frag=Wf, gn_groups=G, out_f32=kind != BF16)
+            res = hip.gemm(x, Wp, g.t, N=C, K=Wp.shape[1], bias=bias, conv=geom, ldc=C, W_frag=Wf, gn_groups=G, out_f32=kind != BF16)
             assert hip.last_kernel_class == "conv_halo"
         finally:
             hip.record_kernel_class = False
+        checked(g, "conv_halo")
         return res
     _fused_case(hip, launch, C, kind, rho, "conv_halo")
 
@@ -190,13 +214,14 @@ def test_conv_thin_input_fused_statistics_on_offset_outputs(hip, kind, rho):
     geom = opsmod.Conv3dGeom(T, H, W, 4, T, H, W, (3, 3, 3), (1, 1, 1), (2, 1, 1), None)
 
     def launch(bias, _):
-        out = torch.empty(T, H, W, C, device="cuda", dtype=kind)
+        g = guarded((T, H, W, C), kind)
         hip.record_kernel_class = True
         try:
-            res = hip.gemm(x, Wp, out, N=C, K=Wp.shape[1], bias=bias, conv=geom, ldc=C, gn_groups=G, out_f32=kind != BF16)
+            res = hip.gemm(x, Wp, g.t, N=C, K=Wp.shape[1], bias=bias, conv=geom, ldc=C, gn_groups=G, out_f32=kind != BF16)
             assert hip.last_kernel_class == "conv_thin_in"
         finally:
             hip.record_kernel_class = False
+        checked(g, "conv_thin_in")
         return res
     _fused_case(hip, launch, C, kind, rho, "conv_thin_in")
 
@@ -216,7 +241,8 @@ def test_conv_subpixel_fused_statistics_on_offset_outputs(hip, kind, rho):
     geom = opsmod.Conv3dGeom(T, H, W, C, T, H, W, (kt, 2, 2), (1, 1, 1), (kt - 1, 1, 1), None)
 
     def launch(bias, _):
-        out = torch.zeros(T, 2 * H, 2 * W, C, device="cuda", dtype=kind)
+        g = guarded((T, 2 * H, 2 * W, C), kind)                                     # (poisoned: the quad launch owns all four phases)
+        out = g.t
         bb = bias[None, :].expand(3, C).contiguous()
         quad = [(py, px, Wp, bias, bb, Wf) for py, px, Wp, Wf in wts]
         shared = {"frames": T, "frame0": 0}
@@ -227,7 +253,7 @@ def test_conv_subpixel_fused_statistics_on_offset_outputs(hip, kind, rho):
             assert hip.last_kernel_class == "conv_subpixel"
         finally:
             hip.record_kernel_class = False
-        return out, hip.gn_shared_stats(shared)
+        return checked(g, "conv_subpixel quad"), hip.gn_shared_stats(shared)
     _fused_case(hip, launch, C, kind, rho, "conv_subpixel quad")
 
 
@@ -254,7 +280,8 @@ class ZeroLaunch:
 
     def __call__(self, kind, cls=None, **epi):
         """-> the [M, N] view of the tensor the launch stored (NaN before it), after asserting the kernel class"""
-        hip, out = self.hip, torch.full(self.shape, float("nan"), device="cuda", dtype=kind)
+        hip, g = self.hip, guarded(self.shape, kind)
+        out = g.t
         for k, v in {**OPTION_DEFAULTS, **self.spec.get("options", {})}.items():
             hip.set_option(k, v)
         hip.record_kernel_class = True
@@ -265,7 +292,7 @@ class ZeroLaunch:
             hip.record_kernel_class = False
             for k, v in OPTION_DEFAULTS.items():
                 hip.set_option(k, v)
-        return out.reshape(self.M, self.N)
+        return checked(g, f"{self.name} {kind}").reshape(self.M, self.N)
 
     def vectors(self, sweep):
         """the sweep tiled over N; N shorter than the sweep: one launch per piece (the last one wraps around)"""
@@ -292,7 +319,7 @@ def assert_same_bits(got, want, tag):
 
 
 def stored(values, kind):
-    return _st(values, torch.empty(0, dtype=kind, device=values.device))
+    return _st(values, torch.empty(0, dtype=kind, device=values.device))            # (names the storage kind: no entry point writes it)
 
 
 @pytest.mark.parametrize("name", list(ZERO_OPERAND_CASES))
@@ -398,9 +425,9 @@ def test_swiglu_on_exact_accumulators(zero_launch, name):
     gate = sweep.repeat(N // 64).reshape(N // 32, 16)                              # group g: sweep[16 (g % 2) ..]
     inn = torch.where((grp // 2) % 2 == 0, 1.0, -0.5)[:, None].expand(N // 32, 16)
     W[:N, 3] = torch.stack([gate, inn], dim=1).reshape(N).to(BF16)
-    outs = []
+    outs, gout = [], Pool()
     for frag in ([None, hip.pack_gemm_frag(W)] if name == "gemm_persistent" else [None]):
-        out = torch.full((M, N // 2), float("nan"), device="cuda", dtype=BF16)
+        out = gout(M, N // 2, dtype=BF16)
         for k, v in {**OPTION_DEFAULTS, **L.spec.get("options", {})}.items():
             hip.set_option(k, v)
         hip.record_kernel_class = True
@@ -416,6 +443,7 @@ def test_swiglu_on_exact_accumulators(zero_launch, name):
     assert all(torch.equal(o.view(torch.int16), out.view(torch.int16)) for o in outs[1:])
     assert not bool(torch.isnan(out.float()).any())
     le.check_gemm(out, A, W, N=N, K=K, epilogue=EPI_SWIGLU, abs_err=DENORMAL, name=f"{name} swiglu")
+    gout.check(f"{name} swiglu")
     g, i = gate.reshape(-1), inn.reshape(-1)
     live = out[torch.arange(M, device="cuda") % 3 != 2]
     assert bool((out[2::3] == 0).all()) and bool((live[:, g <= -100.0] == 0).all())
@@ -433,8 +461,9 @@ def test_groupnorm_apply_silu_over_the_activation_sweep(hip, kind):
     stats = torch.zeros(T, G, 2, device="cuda", dtype=F64)
     stats[..., 1] = n * (1.0 - float(torch.tensor(EPS, dtype=F32)))
     gamma, beta = torch.ones(C, device="cuda"), torch.zeros(C, device="cuda")
-    out = torch.full((T, H, W, C), float("nan"), device="cuda", dtype=BF16)
-    hip.groupnorm_apply(x, out, stats, gamma, beta, G, EPS, True)
+    g = guarded((T, H, W, C), BF16)
+    hip.groupnorm_apply(x, g.t, stats, gamma, beta, G, EPS, True)
+    out = checked(g, "groupnorm_apply silu sweep")
     want, bound = le.groupnorm_apply_reference(x, stats, gamma, beta, G, EPS, True)
     xv = _ld(x)[0, 0, 0]
     _act_checks(out.reshape(-1, C), want.reshape(-1, C), (bound + DENORMAL).reshape(-1, C), torch.ones(H * W, C, dtype=torch.bool, device="cuda"),
@@ -450,9 +479,11 @@ def test_rmsnorm_mod_at_the_magnitudes_of_the_wide_stream(hip, kind, dim):
     x, which = scaled_rows(dim, kind, "cuda")
     w, sc, sh = (rnd(dim, dtype=F32, seed=s) for s in (1, 2, 3))
     for kw in (dict(), dict(scale=sc, shift=sh), dict(w=w, scale=sc, shift=sh)):
-        out = torch.full((x.shape[0] + 1, dim), float("nan"), device="cuda", dtype=BF16)
+        g = guarded((x.shape[0] + 1, dim), BF16, init=nans(x.shape[0] + 1, dim))
+        out = g.t
         hip.rmsnorm_mod(x, out[:-1], 1e-5, **kw)
         assert bool(torch.isnan(out[-1]).all()) and bool(torch.isfinite(out[:-1].float()).all())
+        g.assert_guards("rmsnorm_mod")
         zero = (le.values(x) == 0).all(dim=1)
         assert bool(zero[which == 4].all())
         want0 = (sh if "shift" in kw else torch.zeros(dim, device="cuda")).to(BF16)
@@ -475,8 +506,11 @@ def test_qknorm_rope_at_the_magnitudes_of_the_wide_stream(hip):
     pos = torch.stack([r % 7, (r * 7) % n_pos, (r * 13 + 5) % n_pos], -1).to(torch.int16).cuda()
     cos, sin = _rope_tables(n_pos, n_freq)
     wq, wk = rnd(128, dtype=F32, seed=1) + 1, rnd(128, dtype=F32, seed=2) + 1
-    got = qkv.clone()
+    g = guarded(qkv.shape, BF16, init=qkv)                                         # (in place: q and k rewritten, V left alone)
+    got = g.t
     hip.qknorm_rope(got, heads, pos, 2, cos, sin, wq, wk, 1e-5)
+    g.assert_guards("qknorm_rope")
+    assert torch.equal(got[:, 2 * heads * 128:], qkv[:, 2 * heads * 128:])
     assert bool(torch.isfinite(got.float()).all())
     assert bool((got[which == 4][:, :2 * heads * 128] == 0).all())
     for k, name in enumerate(ROW_KINDS):
@@ -496,8 +530,10 @@ def test_softmax_rows_wide_score_ranges(hip, cols):
     S[2] = 1e4 / scale                                                             # equal scores at the top of the range
     S[3] = -1e4 / scale
     S[4, -1] = 1e4 / scale                                                         # one dominant score, last column
-    P = torch.full((7, cols), float("nan"), device="cuda", dtype=BF16)
+    g = guarded((7, cols), BF16, init=nans(7, cols))
+    P = g.t
     hip.softmax_rows(S, P[:6], scale)
     assert bool(torch.isnan(P[6]).all()) and bool(torch.isfinite(P[:6].float()).all())
+    g.assert_guards("softmax_rows")
     le.check_softmax_rows(P[:6], S, scale, name=f"softmax_rows cols {cols}")
     assert torch.equal(P[2], P[3]) and float(P[4, -1]) == 1.0 and float(P[4, :-1].float().abs().max()) == 0.0

@@ -6,6 +6,10 @@ Tolerances (stated here as the contract):
   * production bf16 store: rel-err <= 2.5e-3 (one bf16 rounding of a perfect result is already 1.7e-3);
   * integer/index kernels (patchify, im2col): bit exact.
 rel-err = ||a - b||_2 / ||b||_2.
+
+Every tensor a svr_* entry point writes comes from tests/guarded_out.py (``gout = Pool()``): guard bytes on either side, the payload
+poisoned with a NaN pattern (or, where the launch owns only part of it, initialised with ``init=``); ``gout.check`` asserts the
+guards and that no poison is left.
 """
 import math
 
@@ -14,6 +18,7 @@ import torch
 
 import local_error as le
 from conftest import sub, rel_err
+from guarded_out import Pool
 from ops_reference import TorchOps, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_RESID_GATE, EPI_SWIGLU
 
 pytestmark = pytest.mark.gpu
@@ -64,11 +69,13 @@ def test_gemm_bias(hip, ref, gemm_epi, M, N, K, out_f32):
     A = rnd(M, K)
     w, W = packed(N, K)
     bias = rnd(N, dtype=torch.float32, seed=3)
-    out = torch.empty(M, N, device="cuda", dtype=torch.float32 if out_f32 else BF16)
+    gout = Pool()
+    out = gout(M, N, dtype=torch.float32 if out_f32 else BF16)
     hip.gemm(A, W, out, N=N, K=K, bias=bias, out_f32=out_f32)
-    want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias)
+    want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias)    # reference buffer
     assert rel_err(out.float(), want) < (TOL_F32 if out_f32 else TOL_BF16)
     le.check_gemm(out, A, W, N=N, K=K, bias=bias)
+    gout.check("gemm bias")
 
 
 def test_gemm_race_screen(hip, ref):
@@ -77,15 +84,16 @@ def test_gemm_race_screen(hip, ref):
     M, N, K = 3000, 2560, 6912
     A = rnd(M, K)
     w, W = packed(N, K)
-    outs = []
+    outs, gout = [], Pool()
     for _ in range(4):
-        out = torch.empty(M, N, device="cuda", dtype=BF16)
+        out = gout(M, N, dtype=BF16)
         hip.gemm(A, W, out, N=N, K=K)
         outs.append(out)
     torch.cuda.synchronize()
+    gout.check("gemm race screen")
     for o in outs[1:]:
         assert torch.equal(o, outs[0])
-    want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K)
+    want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K)    # reference buffer
     assert rel_err(outs[0].float(), want) < TOL_BF16
 
 
@@ -95,9 +103,11 @@ def test_gemm_transpose_detecting(hip):
     A = torch.eye(K, device="cuda", dtype=BF16)
     w = (torch.arange(N * K, device="cuda").reshape(N, K) % 251).to(BF16)
     W = sub("packing").pack_matrix(w, "cuda")
-    out = torch.empty(K, N, device="cuda", dtype=BF16)
+    gout = Pool()
+    out = gout(K, N, dtype=BF16)
     hip.gemm(A, W, out, N=N, K=K)
     assert torch.equal(out, w.t().contiguous())
+    gout.check("gemm transpose")
 
 
 def test_gemm_epilogues(hip, ref, gemm_epi):
@@ -107,29 +117,33 @@ def test_gemm_epilogues(hip, ref, gemm_epi):
     bias = rnd(N, dtype=torch.float32, seed=3)
     gate = rnd(N, dtype=torch.float32, seed=4)
     resid = rnd(M, N, seed=5)
+    gout = Pool()
     for epi, kw in ((EPI_BIAS_SILU, {}), (EPI_BIAS_GELU, {}), (EPI_RESID_GATE, dict(gate=gate, resid=resid)),
                     (EPI_RESID_GATE, dict(resid=resid)), (EPI_RESID_GATE, dict(gate=gate))):
-        out = torch.empty(M, N, device="cuda", dtype=BF16)
+        out = gout(M, N, dtype=BF16)
         hip.gemm(A, W, out, N=N, K=K, bias=bias, epilogue=epi, **kw)
-        want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=epi, **kw)
+        want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=epi, **kw)    # reference buffer
         assert rel_err(out.float(), want) < TOL_BF16, epi
         le.check_gemm(out, A, W, N=N, K=K, bias=bias, epilogue=epi, name=f"epilogue {epi} {sorted(kw)} bf16", **kw)
+        gout.check(f"epilogue {epi} bf16")
     # fp32-store test epilogue: the north star's 1e-3 bound, per fused epilogue (same inputs, no output rounding)
     for epi, kw in ((EPI_BIAS_SILU, {}), (EPI_BIAS_GELU, {}), (EPI_RESID_GATE, dict(gate=gate, resid=resid))):
-        out = torch.empty(M, N, device="cuda", dtype=torch.float32)
+        out = gout(M, N, dtype=torch.float32)
         hip.gemm(A, W, out, N=N, K=K, bias=bias, epilogue=epi, out_f32=True, **kw)
-        want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=epi, **kw)
+        want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=epi, **kw)    # reference buffer
         assert rel_err(out, want) < TOL_F32, epi
         le.check_gemm(out, A, W, N=N, K=K, bias=bias, epilogue=epi, name=f"epilogue {epi} {sorted(kw)} fp32", **kw)
+        gout.check(f"epilogue {epi} fp32")
     # in-place residual (C aliases resid), row-sliced views as the DiT uses them
-    buf = rnd(M + 58, N, seed=6)
-    want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE,
+    buf = gout(M + 58, N, dtype=BF16, init=rnd(M + 58, N, seed=6))
+    want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE,    # reference buffer
                     gate=gate, resid=buf[:M].clone())
     tail, before = buf[M:].clone(), buf[:M].clone()
     hip.gemm(A, W, buf[:M], N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=buf[:M])
     assert rel_err(buf[:M].float(), want) < TOL_BF16
     le.check_gemm(buf[:M], A, W, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=before, name="in-place residual")
     assert torch.equal(buf[M:], tail)
+    gout.check("in-place residual")
 
 
 def test_gemm_swiglu(hip, ref, gemm_epi):
@@ -138,17 +152,19 @@ def test_gemm_swiglu(hip, ref, gemm_epi):
     A = rnd(M, K)
     wg, wi = rnd(Hd, K, scale=1 / 16, seed=7), rnd(Hd, K, scale=1 / 16, seed=8)
     W = packing.pack_swiglu(wg, wi, "cuda")
-    out = torch.empty(M, Hd, device="cuda", dtype=BF16)
+    gout = Pool()
+    out = gout(M, Hd, dtype=BF16)
     hip.gemm(A, W, out, N=2 * Hd, K=K, epilogue=EPI_SWIGLU)
     want = torch.nn.functional.silu(A.float() @ wg.float().t()) * (A.float() @ wi.float().t())
     assert rel_err(out.float(), want) < TOL_BF16
     le.check_gemm(out, A, W, N=2 * Hd, K=K, epilogue=EPI_SWIGLU, name="swiglu bf16")
-    out32 = torch.empty(M, Hd, device="cuda", dtype=torch.float32)                 # fp32-store test epilogue: 1e-3
+    out32 = gout(M, Hd, dtype=torch.float32)                                       # fp32-store test epilogue: 1e-3
     hip.gemm(A, W, out32, N=2 * Hd, K=K, epilogue=EPI_SWIGLU, out_f32=True)
     assert rel_err(out32, want) < TOL_F32
     le.check_gemm(out32, A, W, N=2 * Hd, K=K, epilogue=EPI_SWIGLU, name="swiglu fp32")
+    gout.check("swiglu")
     # and the reference double agrees with the closed form (keeps the two test backends honest)
-    w2 = ref.gemm(A, W, torch.empty(M, Hd, device="cuda"), N=2 * Hd, K=K, epilogue=EPI_SWIGLU)
+    w2 = ref.gemm(A, W, torch.empty(M, Hd, device="cuda"), N=2 * Hd, K=K, epilogue=EPI_SWIGLU)    # reference buffer
     assert rel_err(w2, want) < 1e-5
 
 
@@ -178,15 +194,16 @@ def test_gemm_big_tiles_both_main_loops(hip, ref, gemm_big, M, N, K):
     hid = rnd(M, N, seed=6, dtype=torch.float32)
     cases = [dict(bias=bias), dict(bias=bias, epilogue=EPI_BIAS_GELU), dict(bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=resid),
              dict(bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid, out_f32=True), dict(out_f32=True)]
+    gout = Pool()
     for kw in cases:
         outs = []
         for _ in range(3):
-            out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.float32 if kw.get("out_f32") else BF16)
+            out = gout(M, N, dtype=torch.float32 if kw.get("out_f32") else BF16)
             hip.gemm(A, W, out, N=N, K=K, **kw)
             outs.append(out)
         torch.cuda.synchronize()
         assert not torch.isnan(outs[0].float()).any() and torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
-        want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, **{k: v for k, v in kw.items() if k != "out_f32"})
+        want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, **{k: v for k, v in kw.items() if k != "out_f32"})    # reference buffer
         assert rel_err(outs[0].float(), want) < (TOL_F32 if kw.get("out_f32") else TOL_BF16), kw.get("epilogue", 0)
         le.check_gemm(outs[0], A, W, N=N, K=K, name=f"big GEMM {sorted(kw)}", **kw)
         if gemm_big == 1:
@@ -196,24 +213,25 @@ def test_gemm_big_tiles_both_main_loops(hip, ref, gemm_big, M, N, K):
             Wf = hip.pack_gemm_frag(W)
             assert Wf is not None
             for rep in range(4):
-                out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.float32 if kw.get("out_f32") else BF16)
+                out = gout(M, N, dtype=torch.float32 if kw.get("out_f32") else BF16)
                 hip.gemm(A, W, out, N=N, K=K, W_frag=Wf, **kw)
                 assert torch.equal(out, outs[0]), ("w4r != w4q", rep, kw.get("epilogue", 0))
+        gout.check(f"big GEMM {sorted(kw)}")
     # SwiGLU (interleaved gate | in weights): N = 2 x hidden
     Hd = N // 2
     wg, wi = rnd(Hd, K, scale=1.0 / math.sqrt(K), seed=7), rnd(Hd, K, scale=1.0 / math.sqrt(K), seed=8)
-    o = torch.full((M, Hd), float("nan"), device="cuda", dtype=BF16)
+    o = gout(M, Hd, dtype=BF16)
     hip.gemm(A, packing.pack_swiglu(wg, wi, "cuda"), o, N=N, K=K, epilogue=EPI_SWIGLU)
     want = torch.nn.functional.silu(A.float() @ wg.float().t()) * (A.float() @ wi.float().t())
     assert not torch.isnan(o.float()).any() and rel_err(o.float(), want) < TOL_BF16
     le.check_gemm(o, A, packing.pack_swiglu(wg, wi, "cuda"), N=N, K=K, epilogue=EPI_SWIGLU, name="big GEMM swiglu")
     if gemm_big == 1:
         Wsw = packing.pack_swiglu(wg, wi, "cuda")
-        o2 = torch.full((M, Hd), float("nan"), device="cuda", dtype=BF16)
         for rep in range(2):
-            o2 = torch.full((M, Hd), float("nan"), device="cuda", dtype=BF16)
+            o2 = gout(M, Hd, dtype=BF16)
             hip.gemm(A, Wsw, o2, N=N, K=K, epilogue=EPI_SWIGLU, W_frag=hip.pack_gemm_frag(Wsw))
             assert torch.equal(o2, o), rep
+    gout.check("big GEMM swiglu")
 
 
 def test_gemm_pack_frag_layout_is_the_documented_one(hip):
@@ -241,12 +259,12 @@ def test_gemm_w4r_option_and_routing(hip):
     A = rnd(M, K)
     w, W = packed(N, K)
     Wf = hip.pack_gemm_frag(W)
-    outs = []
+    outs, gout = [], Pool()
     hip.record_kernel_class = True
     for opt in (1, 0):
         hip.set_option("gemm_w4r", opt)
         try:
-            out = torch.empty(M, N, device="cuda", dtype=BF16)
+            out = gout(M, N, dtype=BF16)
             hip.gemm(A, W, out, N=N, K=K, W_frag=Wf)
             assert hip.last_kernel_class == "gemm_persistent"
             outs.append(out)
@@ -255,8 +273,9 @@ def test_gemm_w4r_option_and_routing(hip):
             hip.record_kernel_class = False
     assert torch.equal(outs[0], outs[1])
     assert rel_err(outs[0].float(), A.float() @ w.float().t()) < TOL_BF16
+    gout.check("gemm_w4r")
     with pytest.raises(ValueError):
-        hip.gemm(A, W, torch.empty(M, N, device="cuda", dtype=BF16), N=N, K=K, W_frag=Wf[: N * K - 8])
+        hip.gemm(A, W, torch.empty(M, N, device="cuda", dtype=BF16), N=N, K=K, W_frag=Wf[: N * K - 8])    # refused: no entry point writes it
     assert hip.pack_gemm_frag(W[:128]) is None and hip.pack_gemm_frag(W[:, :64].contiguous()) is None
 
 
@@ -325,11 +344,12 @@ def _conv_case(hip, ref, case, frag=False, out_f32=False):
     Wo = (W + plo + phi - kw) // stride[2] + 1
     geom = opsmod.Conv3dGeom(T, H, W, Cin, To, Ho, Wo, k, stride, (pt, plo, plo), halo)
     resid = rnd(To, Ho, Wo, Cout, seed=11)
-    out = torch.empty(To, Ho, Wo, Cout, device="cuda", dtype=torch.float32 if out_f32 else BF16)
+    gout = Pool()
+    out = gout(To, Ho, Wo, Cout, dtype=torch.float32 if out_f32 else BF16)
     Wf = hip.pack_conv_frag(Wp, kt, Cin, Cout) if frag and (kh, kw) == (3, 3) else None
     hip.gemm(x, Wp, out, N=Cout, K=Wp.shape[1], bias=bias, conv=geom, epilogue=EPI_RESID_GATE, resid=resid,
              ldc=Cout, ldr=Cout, W_frag=Wf, out_f32=out_f32)
-    want = ref.gemm(x, Wp, torch.empty(To, Ho, Wo, Cout, device="cuda"), N=Cout, K=Wp.shape[1], bias=bias,
+    want = ref.gemm(x, Wp, torch.empty(To, Ho, Wo, Cout, device="cuda"), N=Cout, K=Wp.shape[1], bias=bias,    # reference buffer
                     conv=geom, epilogue=EPI_RESID_GATE, resid=resid)
     # independent check of the reference double itself against F.conv3d semantics of the causal conv
     head = halo.float() if hf else x[:1].float().expand(pt, H, W, Cin)
@@ -339,6 +359,7 @@ def _conv_case(hip, ref, case, frag=False, out_f32=False):
     assert rel_err(want, y) < 1e-5
     assert rel_err(out.float(), want) < (TOL_F32 if out_f32 else TOL_BF16)
     le.check_gemm(out, x, Wp, N=Cout, K=Wp.shape[1], bias=bias, conv=geom, epilogue=EPI_RESID_GATE, resid=resid, name="conv")
+    gout.check("conv")
 
 
 def test_conv3d_halo_kernel_race_screen_and_generic_agreement(hip):
@@ -352,12 +373,13 @@ def test_conv3d_halo_kernel_race_screen_and_generic_agreement(hip):
     Wp = packing.pack_conv3d(w5, "cuda")
     bias = rnd(Cout, dtype=torch.float32, seed=3)
     geom = opsmod.Conv3dGeom(T, H, W, Cin, T, H, W, (3, 3, 3), (1, 1, 1), (2, 1, 1), None)
-    outs = []
+    outs, gout = [], Pool()
     for _ in range(3):
-        out = torch.empty(T, H, W, Cout, device="cuda", dtype=torch.float32)
+        out = gout(T, H, W, Cout, dtype=torch.float32)
         hip.gemm(x, Wp, out, N=Cout, K=Wp.shape[1], bias=bias, conv=geom, ldc=Cout, out_f32=True)
         outs.append(out)
     torch.cuda.synchronize()
+    gout.check("halo conv race screen")
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
     # weights streamed to registers from the fragment-ordered copy: same MFMAs in the same order -> same bits,
     # in both shapes of that kernel (4 rows per wave, two workgroups per CU / 8 rows per wave, one wave per SIMD)
@@ -366,18 +388,20 @@ def test_conv3d_halo_kernel_race_screen_and_generic_agreement(hip):
         for rows in (4, 8):
             hip.set_option("conv_rows", rows)
             for _ in range(4):
-                out = torch.full((T, H, W, Cout), float("nan"), device="cuda", dtype=torch.float32)
+                out = gout(T, H, W, Cout, dtype=torch.float32)
                 hip.gemm(x, Wp, out, N=Cout, K=Wp.shape[1], bias=bias, conv=geom, ldc=Cout, out_f32=True, W_frag=Wf)
                 assert torch.equal(out, outs[0]), rows
+                gout.check(f"halo conv W_frag, conv_rows {rows}")
     finally:
         hip.set_option("conv_rows", CONV_ROWS_DEFAULT)
     hip.set_option("conv_impl", 1)
     try:
-        gen = torch.empty(T, H, W, Cout, device="cuda", dtype=torch.float32)
+        gen = gout(T, H, W, Cout, dtype=torch.float32)
         hip.gemm(x, Wp, gen, N=Cout, K=Wp.shape[1], bias=bias, conv=geom, ldc=Cout, out_f32=True)
     finally:
         hip.set_option("conv_impl", 0)
     assert rel_err(outs[0], gen) < 1e-5
+    gout.check("generic conv")
 
 
 @pytest.mark.parametrize("kt,T,H,W,hf,resid_on", [(3, 3, 21, 70, 0, False), (3, 2, 9, 33, 2, True), (1, 2, 8, 32, 0, False),
@@ -401,20 +425,22 @@ def test_conv3d_thin_input_fused(hip, ref, kt, T, H, W, hf, resid_on):
     geom = opsmod.Conv3dGeom(T, H, W, 4, To, H, W, (kt, 3, 3), (1, 1, 1), (pt, 1, 1), halo)
     resid = rnd(To, H, W, Cout, seed=11) if resid_on else None
     epi = EPI_RESID_GATE if resid_on else EPI_BIAS
-    out = torch.empty(To, H, W, Cout, device="cuda", dtype=BF16)
+    gout = Pool()
+    out = gout(To, H, W, Cout, dtype=BF16)
     _, stats = hip.gemm(x, Wp, out, N=Cout, K=128, bias=bias, conv=geom, epilogue=epi, resid=resid, ldc=Cout, ldr=Cout,
                         gn_groups=32)
-    want = ref.gemm(x, Wp, torch.empty(To, H, W, Cout, device="cuda"), N=Cout, K=128, bias=bias, conv=geom,
+    want = ref.gemm(x, Wp, torch.empty(To, H, W, Cout, device="cuda"), N=Cout, K=128, bias=bias, conv=geom,    # reference buffer
                     epilogue=epi, resid=resid)
     assert rel_err(out.float(), want) < TOL_BF16
     le.check_gemm(out, x, Wp, N=Cout, K=128, bias=bias, conv=geom, epilogue=epi, resid=resid, name="thin-input conv")
     # the older route: explicit im2col + plain GEMM
-    cols = torch.empty(To * H * W, 128, device="cuda", dtype=BF16)
+    cols = gout(To * H * W, 128, dtype=BF16)
     hip.im2col_causal(x, cols, geom)
-    out2 = torch.empty_like(out)
+    out2 = gout.like(out)
     hip.gemm(cols, Wp, out2, N=Cout, K=128, M=To * H * W, bias=bias, epilogue=epi, resid=resid, lda=128, ldc=Cout, ldr=Cout)
     assert rel_err(out.float(), out2.float()) < TOL_BF16
     le.check_gemm(out2, x, Wp, N=Cout, K=128, bias=bias, conv=geom, epilogue=epi, resid=resid, name="im2col + GEMM")
+    gout.check("thin-input conv, im2col, GEMM")
     assert stats is not None
     o = out.double().reshape(To, H * W, 32, Cout // 32)
     want_stats = torch.stack([o.sum(dim=(1, 3)), (o * o).sum(dim=(1, 3))], dim=-1)
@@ -430,9 +456,11 @@ def test_upscale_pixel_shuffle_epilogue(hip, ref, gemm_epi, rz, drop):
     bias = rnd(4 * rz * Cc, dtype=torch.float32, seed=3)
     ps = opsmod.PixelShuffleGeom(F_, H, W, rz, Cc, drop)
     To = F_ * rz - (1 if drop else 0)
-    out = torch.full((To, 2 * H, 2 * W, Cc), float("nan"), device="cuda", dtype=BF16)
+    # (drop_first: the launch skips the duplicated head frame, ``out`` has no room for it -- every element of it is written)
+    gout = Pool()
+    out = gout(To, 2 * H, 2 * W, Cc, dtype=BF16)
     hip.gemm(x, Wp, out, N=4 * rz * Cc, K=Cc, M=F_ * H * W, bias=bias, ps=ps)
-    want = ref.gemm(x, Wp, torch.empty(To, 2 * H, 2 * W, Cc, device="cuda"), N=4 * rz * Cc, K=Cc, M=F_ * H * W,
+    want = ref.gemm(x, Wp, torch.empty(To, 2 * H, 2 * W, Cc, device="cuda"), N=4 * rz * Cc, K=Cc, M=F_ * H * W,    # reference buffer
                     bias=bias, ps=ps)
     # closed form: "b (x y z c) f h w -> b c (f z) (h x) (w y)"
     y = (x.float() @ w.float().t() + bias).reshape(F_, H, W, 2, 2, rz, Cc)
@@ -443,12 +471,14 @@ def test_upscale_pixel_shuffle_epilogue(hip, ref, gemm_epi, rz, drop):
     assert not torch.isnan(out.float()).any()
     assert rel_err(out.float(), want) < TOL_BF16
     le.check_gemm(out, x, Wp, N=4 * rz * Cc, K=Cc, M=F_ * H * W, bias=bias, ps=ps, name="pixel shuffle")
+    gout.check("pixel shuffle")
 
 
 def test_gemm_epilogue_paths_bit_identical(hip):
     """The LDS-staged epilogue performs the direct epilogue's arithmetic in the same order: identical bits, for every fused
     epilogue, the fp32 test store, the pixel-shuffle scatter, the generic (strided / 1x1) conv and ragged M."""
     packing, opsmod = sub("packing"), sub("ops")
+    gout = Pool()
 
     def both(fn):
         outs = []
@@ -461,6 +491,7 @@ def test_gemm_epilogue_paths_bit_identical(hip):
         torch.cuda.synchronize()
         assert outs[0].dtype == outs[1].dtype and not torch.isnan(outs[0].float()).any()
         assert torch.equal(outs[0], outs[1])
+        gout.check("gemm_epi 1 | 2")
 
     M, N, K = 1531, 768, 192
     A = rnd(M, K)
@@ -470,7 +501,7 @@ def test_gemm_epilogue_paths_bit_identical(hip):
                     (EPI_RESID_GATE, dict(resid=resid))):
         for f32 in (False, True):
             def run(epi=epi, kw=kw, f32=f32):
-                out = torch.full((M, N), float("nan"), device="cuda", dtype=torch.float32 if f32 else BF16)
+                out = gout(M, N, dtype=torch.float32 if f32 else BF16)
                 hip.gemm(A, W, out, N=N, K=K, bias=bias, epilogue=epi, out_f32=f32, **kw)
                 return out
             both(run)
@@ -482,7 +513,7 @@ def test_gemm_epilogue_paths_bit_identical(hip):
     for drop in (False, True):
         def run_ps(drop=drop):
             ps = opsmod.PixelShuffleGeom(F_, H, Wd, rz, Cc, drop)
-            out = torch.full((F_ * rz - (1 if drop else 0), 2 * H, 2 * Wd, Cc), float("nan"), device="cuda", dtype=BF16)
+            out = gout(F_ * rz - (1 if drop else 0), 2 * H, 2 * Wd, Cc, dtype=BF16)
             hip.gemm(x, Wp, out, N=4 * rz * Cc, K=Cc, M=F_ * H * Wd, bias=b2, ps=ps)
             return out
         both(run_ps)
@@ -491,7 +522,7 @@ def test_gemm_epilogue_paths_bit_identical(hip):
     Wsw = packing.pack_swiglu(rnd(Hd, K, scale=1 / 16, seed=7), rnd(Hd, K, scale=1 / 16, seed=8), "cuda")
     for f32 in (False, True):
         def run_sw(f32=f32):
-            out = torch.full((M, Hd), float("nan"), device="cuda", dtype=torch.float32 if f32 else BF16)
+            out = gout(M, Hd, dtype=torch.float32 if f32 else BF16)
             hip.gemm(A, Wsw, out, N=2 * Hd, K=K, epilogue=EPI_SWIGLU, out_f32=f32)
             return out
         both(run_sw)
@@ -510,7 +541,7 @@ def test_gemm_epilogue_paths_bit_identical(hip):
         bc = rnd(Cout, dtype=torch.float32, seed=3)
 
         def run_conv():
-            out = torch.full((To, Ho, Wo, Cout), float("nan"), device="cuda", dtype=BF16)
+            out = gout(To, Ho, Wo, Cout, dtype=BF16)
             hip.gemm(xin, Wc, out, N=Cout, K=Wc.shape[1], bias=bc, conv=geom, epilogue=EPI_RESID_GATE, resid=rs,
                      ldc=Cout, ldr=Cout)
             return out
@@ -529,9 +560,10 @@ def test_conv_phase_scatter_subpixel(hip, ref, gemm_epi, frag, T, H, W, Cin, Cou
     halo = rnd(hf, H, W, Cin, seed=9) if hf else None
     pt = hf if hf else kt - 1
     To = T + pt - kt + 1
-    out = torch.full((To * ts, 2 * H, 2 * W, Cout), float("nan"), device="cuda", dtype=BF16)
+    gout = Pool()
+    out = gout(To * ts, 2 * H, 2 * W, Cout, dtype=BF16)                           # (poisoned: the phases together must write all of it)
     want = torch.full((To * ts, 2 * H, 2 * W, Cout), float("nan"), device="cuda", dtype=torch.float32)
-    out_quad = torch.full_like(out, float("nan"))
+    out_quad = gout.like(out) if frag else None                                    # (the quad launch exists on the sub-pixel kernel only)
     for tz in range(ts):                                                           # temporal phase = first frame of the launch
         quad = []
         for ph, (py, px) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
@@ -570,6 +602,7 @@ def test_conv_phase_scatter_subpixel(hip, ref, gemm_epi, frag, T, H, W, Cin, Cou
     assert rel_err(out.float(), want) < TOL_BF16
     if frag:
         assert torch.equal(out_quad, out)
+    gout.check("sub-pixel phases")
 
 
 @pytest.mark.parametrize("T,H,W,Cin,Cout,hf,kt,ts", [(3, 9, 11, 128, 128, 0, 3, 1), (2, 40, 70, 256, 256, 2, 3, 1), (3, 17, 33, 128, 256, 1, 2, 2),
@@ -587,7 +620,8 @@ def test_conv_subpixel_fused_groupnorm_statistics(hip, T, H, W, Cin, Cout, hf, k
     lead = 2                                                                       # frames in front of the launches' first frame
     runs = []
     for _ in range(2):
-        out = torch.zeros((lead + To * ts, 2 * H, 2 * W, Cout), device="cuda", dtype=BF16)
+        gout = Pool()
+        out = gout(lead + To * ts, 2 * H, 2 * W, Cout, dtype=BF16)                # (the lead and phase launches together write all of it)
         shared = {"frames": out.shape[0]}
         # the lead frames get their four phases from a launch of their own (as a head launch of the engine would); then one
         # launch group per temporal phase: (first output frame, input, halo, causal pad, frames, frame stride)
@@ -605,7 +639,7 @@ def test_conv_subpixel_fused_groupnorm_statistics(hip, T, H, W, Cin, Cout, hf, k
         stats = hip.gn_shared_stats(shared)
         assert stats is not None and tuple(stats.shape) == (out.shape[0], G, 2)
         # the same launches in their quad form (one launch per group): same output, same statistics, bit for bit
-        out_q = torch.zeros_like(out)
+        out_q = gout.like(out)
         shared_q = {"frames": out.shape[0]}
         for base, xin, hl, p_t, to_n, stride in groups:
             quad = []
@@ -618,9 +652,10 @@ def test_conv_subpixel_fused_groupnorm_statistics(hip, T, H, W, Cin, Cout, hf, k
             hip.gemm(xin, quad[0][2], out_q[base:], N=Cout, K=quad[0][2].shape[1], bias=quad[0][3], conv=geom, W_frag=quad[0][5],
                      phase=opsmod.PhaseScatter(0, 0, quad[0][4], stride, quad=quad), gn_groups=G, gn_shared=shared_q)
         assert torch.equal(out_q, out) and torch.equal(hip.gn_shared_stats(shared_q), stats)
-        want = torch.empty(out.shape[0], G, 2, dtype=torch.float64, device="cuda")
+        want = gout(out.shape[0], G, 2, dtype=torch.float64)
         hip.groupnorm_stats(out, want, G)
         assert rel_err(stats[..., 0], want[..., 0]) < 1e-5 and rel_err(stats[..., 1], want[..., 1]) < 1e-6
+        gout.check("sub-pixel phases with fused statistics")
         runs.append(stats)
     assert torch.equal(runs[0], runs[1])
 
@@ -642,23 +677,24 @@ def test_conv_thin_output_kernel(hip, ref, Cin, Cout, kt, T, H, W, hf):
     resid = rnd(To, H, W, Cout, seed=11)
     for kw in (dict(), dict(epilogue=EPI_RESID_GATE, resid=resid, ldr=Cout)):
         kw = dict(N=Cout, K=Wp.shape[1], bias=bias, conv=geom, ldc=Cout, **kw)
-        outs = []
+        outs, gout = [], Pool()
         for _ in range(3):
-            out = torch.full((To, H, W, Cout), float("nan"), device="cuda", dtype=BF16)
+            out = gout(To, H, W, Cout, dtype=BF16)
             hip.gemm(x, Wp, out, **kw)
             outs.append(out)
         torch.cuda.synchronize()
         assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
-        want = ref.gemm(x, Wp, torch.empty(To, H, W, Cout, device="cuda"), **kw)
+        want = ref.gemm(x, Wp, torch.empty(To, H, W, Cout, device="cuda"), **kw)    # reference buffer
         assert not torch.isnan(outs[0].float()).any() and rel_err(outs[0].float(), want) < TOL_BF16
         le.check_gemm(outs[0], x, Wp, name=f"thin-output conv {kw.get('epilogue', 0)}", **kw)
         hip.set_option("conv_impl", 1)                      # the generic implicit-GEMM kernel on the same launch
         try:
-            old = torch.empty(To, H, W, Cout, device="cuda", dtype=BF16)
+            old = gout(To, H, W, Cout, dtype=BF16)
             hip.gemm(x, Wp, old, **kw)
         finally:
             hip.set_option("conv_impl", 0)
         assert rel_err(outs[0].float(), old.float()) < 2e-3
+        gout.check(f"thin-output conv {kw.get('epilogue', 0)}")
 
 
 @pytest.mark.parametrize("kt,ts,H,W", [(2, 2, 40, 70), (3, 1, 33, 64), (1, 1, 16, 32)])
@@ -676,9 +712,10 @@ def test_conv_subpixel_kernel_race_screen_and_generic_agreement(hip, kt, ts, H, 
     bias, bb = rnd(Cout, dtype=torch.float32, seed=3), rnd(3, Cout, dtype=torch.float32, seed=4)
     geom = opsmod.Conv3dGeom(T, H, W, Cin, T, H, W, (kt, 2, 2), (1, 1, 1), (kt - 1, 1, 0), halo)
     kw = dict(N=Cout, K=Wp.shape[1], bias=bias, conv=geom, phase=opsmod.PhaseScatter(0, 1, bb, ts), W_frag=Wf)
-    outs = []
+    outs, gout = [], Pool()
+    zeros = torch.zeros(T * ts, 2 * H, 2 * W, Cout, device="cuda", dtype=BF16)
     for _ in range(4):
-        out = torch.zeros(T * ts, 2 * H, 2 * W, Cout, device="cuda", dtype=BF16)
+        out = gout.like(zeros, init=zeros)                                         # (one phase of four is written: the others stay zero)
         hip.gemm(x, Wp, out, **kw)
         outs.append(out)
     torch.cuda.synchronize()
@@ -686,7 +723,7 @@ def test_conv_subpixel_kernel_race_screen_and_generic_agreement(hip, kt, ts, H, 
         assert torch.equal(o, outs[0])
     hip.set_option("conv_sub", 0)
     try:
-        gen = torch.zeros_like(outs[0])
+        gen = gout.like(zeros, init=zeros)
         hip.gemm(x, Wp, gen, **kw)
     finally:
         hip.set_option("conv_sub", 1)
@@ -694,15 +731,16 @@ def test_conv_subpixel_kernel_race_screen_and_generic_agreement(hip, kt, ts, H, 
     assert rel_err(outs[0].float(), gen.float()) < 2e-3
     # and without the phase scatter: a plain (kt, 2, 2) conv into a dense tensor
     kw2 = dict(N=Cout, K=Wp.shape[1], bias=bias, conv=geom, W_frag=Wf, ldc=Cout)
-    d1 = torch.full((T, H, W, Cout), float("nan"), device="cuda", dtype=BF16)
+    d1 = gout(T, H, W, Cout, dtype=BF16)
     hip.gemm(x, Wp, d1, **kw2)
     hip.set_option("conv_sub", 0)
     try:
-        d0 = torch.full((T, H, W, Cout), float("nan"), device="cuda", dtype=BF16)
+        d0 = gout(T, H, W, Cout, dtype=BF16)
         hip.gemm(x, Wp, d0, **kw2)
     finally:
         hip.set_option("conv_sub", 1)
     assert not torch.isnan(d1.float()).any() and rel_err(d1.float(), d0.float()) < 2e-3
+    gout.check("sub-pixel conv race screen")
 
 
 def test_vae_subpixel_upsampler_matches_two_step_on_gpu(hip):
@@ -785,22 +823,24 @@ def test_conv_fused_groupnorm_stats(hip, ref, conv_variant, Cin, Cout, resid):
     kw = dict(N=Cout, K=Wp.shape[1], bias=bias, conv=geom, ldc=Cout, ldr=Cout,
               epilogue=EPI_RESID_GATE if resid else EPI_BIAS, resid=res,
               W_frag=hip.pack_conv_frag(Wp, 3, Cin, Cout) if conv_variant else None)
-    out = torch.empty(T, H, W, Cout, device="cuda", dtype=BF16)
+    gout = Pool()
+    out = gout(T, H, W, Cout, dtype=BF16)
     got, stats = hip.gemm(x, Wp, out, gn_groups=32, **kw)
     assert got is out and stats is not None and stats.shape == (T, 32, 2)
-    plain = torch.empty_like(out)
+    plain = gout.like(out)
     hip.gemm(x, Wp, plain, **kw)
     assert torch.equal(out, plain)                         # the fused statistics do not change the output
-    want = ref.groupnorm_stats(out, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)
+    want = ref.groupnorm_stats(out, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)    # reference buffer
     assert torch.allclose(stats, want, rtol=1e-6, atol=1e-6)
-    _, again = hip.gemm(x, Wp, torch.empty_like(out), gn_groups=32, **kw)
+    _, again = hip.gemm(x, Wp, gout.like(out), gn_groups=32, **kw)
     assert torch.equal(stats, again)
     # a geometry the halo kernel does not take: no fused statistics, the caller falls back
     g2 = opsmod.Conv3dGeom(T, H, W, Cin, T, (H + 1 - 3) // 2 + 1, (W + 1 - 3) // 2 + 1, (1, 3, 3), (1, 2, 2), (0, 0, 0), None)
     w2 = packing.pack_conv3d(rnd(Cout, Cin, 1, 3, 3, scale=0.05, seed=4), "cuda")
-    o2 = torch.empty(T, g2.Ho, g2.Wo, Cout, device="cuda", dtype=BF16)
+    o2 = gout(T, g2.Ho, g2.Wo, Cout, dtype=BF16)
     _, none = hip.gemm(x, w2, o2, N=Cout, K=w2.shape[1], bias=bias, conv=g2, ldc=Cout, gn_groups=32)
     assert none is None
+    gout.check("conv with fused statistics")
 
 
 # ------------------------------------------------------------------ DiT side kernels
@@ -808,22 +848,26 @@ def test_conv_fused_groupnorm_stats(hip, ref, conv_variant, Cin, Cout, resid):
 def test_rmsnorm_mod(hip, ref, rows, dim):
     x = rnd(rows, dim, scale=2.0)
     w, sc, sh = (rnd(dim, dtype=torch.float32, seed=s) for s in (1, 2, 3))
+    gout = Pool()
     for kw in (dict(), dict(scale=sc, shift=sh), dict(w=w, scale=sc, shift=sh)):
-        out = torch.empty(rows, dim, device="cuda", dtype=BF16)
+        out = gout(rows, dim, dtype=BF16)
         hip.rmsnorm_mod(x, out, 1e-5, **kw)
-        want = ref.rmsnorm_mod(x, torch.empty(rows, dim, device="cuda"), 1e-5, **kw)
+        want = ref.rmsnorm_mod(x, torch.empty(rows, dim, device="cuda"), 1e-5, **kw)    # reference buffer
         assert rel_err(out.float(), want) < TOL_BF16
         le.check_rmsnorm_mod(out, x, 1e-5, **kw)
+        gout.check("rmsnorm_mod")
 
 
 def test_ada_combine(hip, ref):
     dim, nv = 2560, 13
     emb, params = rnd(dim * 6), rnd(nv, dim, seed=2)
     slots = torch.tensor([0, 1, 2, 3, 4, 5, 0, 1, 2, 3, 4, 5, 1], dtype=torch.int32, device="cuda")
-    out = torch.empty(nv, dim, device="cuda", dtype=torch.float32)
+    gout = Pool()
+    out = gout(nv, dim, dtype=torch.float32)
     hip.ada_combine(emb, params, slots, out)
-    want = ref.ada_combine(emb, params, slots, torch.empty(nv, dim, device="cuda"))
+    want = ref.ada_combine(emb, params, slots, torch.empty(nv, dim, device="cuda"))    # reference buffer
     assert torch.allclose(out, want, atol=1e-6)
+    gout.check("ada_combine")
 
 
 def _rope_tables(n_pos):
@@ -841,11 +885,13 @@ def test_qknorm_rope(hip, ref):
     cos, sin = _rope_tables(100)
     wq, wk = rnd(128, dtype=torch.float32, seed=1) + 1, rnd(128, dtype=torch.float32, seed=2) + 1
     want = ref.qknorm_rope(qkv.float().clone(), heads, pos, 58, cos, sin, wq, wk, 1e-5)
-    got = qkv.clone()
+    gout = Pool()
+    got = gout.like(qkv, init=qkv)                                                  # (in place: q and k rewritten, V left alone)
     hip.qknorm_rope(got, heads, pos, 58, cos, sin, wq, wk, 1e-5)
     assert torch.equal(got[:, 2 * heads * 128:], qkv[:, 2 * heads * 128:])          # V untouched
     assert rel_err(got.float(), want) < TOL_BF16
     le.check_qknorm_rope(got, qkv, heads, pos, 58, cos, sin, wq, wk, 1e-5)
+    gout.check("qknorm_rope")
 
 
 def _attn_case(lens, heads, D, n_rows, seed=0):
@@ -883,7 +929,8 @@ def test_attn_varlen(hip, ref, attn_impl, lens, heads, D, request):
     qkv = rnd(n_rows, 3 * heads * D)
     seq_rows, out_rows, cu, total = _attn_case(lens, heads, D, n_rows)
     scale = 1.0 / math.sqrt(D)
-    out = torch.full((total, heads * D), float("nan"), device="cuda", dtype=BF16)     # every row must be written
+    gout = Pool()
+    out = gout(total, heads * D, dtype=BF16)                                           # poisoned: every row must be written
     hip.attn_varlen(qkv, out, seq_rows, out_rows, cu, max(lens), heads, D, scale)
     want = ref.attn_varlen(qkv, torch.zeros(total, heads * D, device="cuda"), seq_rows, out_rows, cu, max(lens),
                            heads, D, scale)
@@ -891,18 +938,20 @@ def test_attn_varlen(hip, ref, attn_impl, lens, heads, D, request):
     le.check_attn(out, qkv, seq_rows, out_rows, cu, heads, D, scale)
     # race screen: the double-buffered LDS pipeline must be deterministic
     for _ in range(3):
-        again = torch.zeros_like(out)
+        again = gout.like(out)
         hip.attn_varlen(qkv, again, seq_rows, out_rows, cu, max(lens), heads, D, scale)
         assert torch.equal(again, out)
+    gout.check("attn_varlen")
     if attn_impl == 0 and D == 128 and "variants" in (request.config.getoption("-m") or ""):   # the kernel's build variants (A/B knob)
         for variant in (1, 3, 4):   # 4 waves + s_setprio, 8 waves + s_setprio, 4 waves (default: 8 waves)
             hip.set_option("attn_variant", variant)
             try:
-                other = torch.full_like(out, float("nan"))
+                other = gout.like(out)
                 hip.attn_varlen(qkv, other, seq_rows, out_rows, cu, max(lens), heads, D, scale)
             finally:
                 hip.set_option("attn_variant", 0)
             assert torch.equal(other, out), variant     # same MFMAs in the same order per query row -> same bits
+            gout.check(f"attn_varlen variant {variant}")
 
 
 def test_attn_varlen_scattered_output_rows(hip, ref, attn_impl):
@@ -917,7 +966,8 @@ def test_attn_varlen_scattered_output_rows(hip, ref, attn_impl):
     seq_rows = perm[:total].to(torch.int32).cuda()
     out_rows = torch.randperm(total + 500, generator=g)[:total].to(torch.int32).cuda()
     cu = torch.tensor([0] + list(torch.tensor(lens).cumsum(0)), dtype=torch.int32).cuda()
-    out = torch.full((total + 500, heads * D), 7.0, device="cuda", dtype=BF16)
+    gout = Pool()
+    out = gout(total + 500, heads * D, dtype=BF16, init=torch.full((total + 500, heads * D), 7.0, device="cuda", dtype=BF16))
     hip.attn_varlen(qkv, out, seq_rows, out_rows, cu, max(lens), heads, D, 1.0 / math.sqrt(D))
     want = ref.attn_varlen(qkv, torch.full((total + 500, heads * D), 7.0, device="cuda"), seq_rows, out_rows, cu,
                            max(lens), heads, D, 1.0 / math.sqrt(D))
@@ -926,6 +976,7 @@ def test_attn_varlen_scattered_output_rows(hip, ref, attn_impl):
     untouched = torch.ones(total + 500, dtype=torch.bool, device="cuda")
     untouched[out_rows.long()] = False
     assert bool((out[untouched] == 7.0).all())
+    gout.check("attn_varlen scattered rows")
 
 
 def test_attn_varlen_spiky_scores(hip, ref, attn_impl):
@@ -936,12 +987,14 @@ def test_attn_varlen_spiky_scores(hip, ref, attn_impl):
     qkv[300, heads * D:2 * heads * D] = qkv[5, :heads * D] * 8          # k[300] aligned with q[5]
     rows = torch.arange(L, dtype=torch.int32, device="cuda")
     cu = torch.tensor([0, L], dtype=torch.int32, device="cuda")
-    out = torch.zeros(L, heads * D, device="cuda", dtype=BF16)
+    gout = Pool()
+    out = gout(L, heads * D, dtype=BF16)
     hip.attn_varlen(qkv, out, rows, rows, cu, L, heads, D, 1.0 / math.sqrt(D))
     want = ref.attn_varlen(qkv, torch.zeros(L, heads * D, device="cuda"), rows, rows, cu, L, heads, D, 1.0 / math.sqrt(D))
     assert rel_err(out.float(), want) < 4e-3
     assert rel_err(out[5].float(), want[5]) < 4e-3                      # the row whose max jumps at key 300
     le.check_attn(out, qkv, rows, rows, cu, heads, D, 1.0 / math.sqrt(D), name="attn_varlen spiky")
+    gout.check("attn_varlen spiky")
 
 
 def test_attn_varlen_constant_scores_skip_rescale(hip, ref, attn_impl):
@@ -953,27 +1006,31 @@ def test_attn_varlen_constant_scores_skip_rescale(hip, ref, attn_impl):
     qkv[:, D:2 * D] = qkv[0, D:2 * D]
     rows = torch.arange(L, dtype=torch.int32, device="cuda")
     cu = torch.tensor([0, L], dtype=torch.int32, device="cuda")
-    out = torch.zeros(L, D, device="cuda", dtype=BF16)
+    gout = Pool()
+    out = gout(L, D, dtype=BF16)
     hip.attn_varlen(qkv, out, rows, rows, cu, L, heads, D, 1.0 / math.sqrt(D))
     want = qkv[:, 2 * D:].float().mean(0, keepdim=True).expand(L, D)
     assert rel_err(out.float(), want) < 4e-3
     le.check_attn(out, qkv, rows, rows, cu, heads, D, 1.0 / math.sqrt(D), name="attn_varlen constant scores")
+    gout.check("attn_varlen constant scores")
 
 
 def test_rows_mean_patchify_unpatchify(hip, ref):
     src = rnd(7 * 58, 2560)
-    dst = torch.empty(58, 2560, device="cuda", dtype=BF16)
+    gout = Pool()
+    dst = gout(58, 2560, dtype=BF16)
     hip.rows_mean(src, dst, 7, 58)
-    assert rel_err(dst.float(), ref.rows_mean(src, torch.empty(58, 2560, device="cuda"), 7, 58)) < TOL_BF16
+    assert rel_err(dst.float(), ref.rows_mean(src, torch.empty(58, 2560, device="cuda"), 7, 58)) < TOL_BF16    # reference buffer
     vid = rnd(3, 8, 12, 33)
-    out = torch.empty(3 * 4 * 6, 192, device="cuda", dtype=BF16)
+    out = gout(3 * 4 * 6, 192, dtype=BF16)
     hip.patchify(vid, out)
-    assert torch.equal(out, ref.patchify(vid, torch.empty(3 * 4 * 6, 192, device="cuda", dtype=BF16)))
+    assert torch.equal(out, ref.patchify(vid, torch.empty(3 * 4 * 6, 192, device="cuda", dtype=BF16)))    # reference buffer
     pred, x_t = rnd(3 * 4 * 6, 64), rnd(3, 8, 12, 16, seed=4)
     for xt in (x_t, None):
-        o = torch.empty(3, 8, 12, 16, device="cuda", dtype=BF16)
+        o = gout(3, 8, 12, 16, dtype=BF16)
         hip.unpatchify_euler(pred, xt, o)
-        assert rel_err(o.float(), ref.unpatchify_euler(pred, xt, torch.empty(3, 8, 12, 16, device="cuda"))) < TOL_BF16
+        assert rel_err(o.float(), ref.unpatchify_euler(pred, xt, torch.empty(3, 8, 12, 16, device="cuda"))) < TOL_BF16    # reference buffer
+    gout.check("rows_mean, patchify, unpatchify_euler")
 
 
 # ------------------------------------------------------------------ VAE side kernels
@@ -982,25 +1039,27 @@ def test_groupnorm(hip, ref, C):
     T, H, W = 3, 37, 41
     x = rnd(T, H, W, C, scale=1.5) + 0.7
     gamma, beta = rnd(C, dtype=torch.float32, seed=1) + 1, rnd(C, dtype=torch.float32, seed=2)
-    stats = torch.empty(T, 32, 2, device="cuda", dtype=torch.float64)
+    gout = Pool()
+    stats = gout(T, 32, 2, dtype=torch.float64)
     hip.groupnorm_stats(x, stats, 32)
-    want_stats = ref.groupnorm_stats(x, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)
+    want_stats = ref.groupnorm_stats(x, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)    # reference buffer
     assert torch.allclose(stats, want_stats, rtol=1e-5)
     le.check_groupnorm_stats(stats, x, 32)
-    again = torch.empty_like(stats)
+    again = gout.like(stats)
     hip.groupnorm_stats(x, again, 32)
     assert torch.equal(stats, again)                       # fixed-order reduction: bit-reproducible
-    one = torch.empty(1, 32, 2, device="cuda", dtype=torch.float64)
+    one = gout(1, 32, 2, dtype=torch.float64)
     hip.groupnorm_stats(x[1:2].contiguous(), one, 32)
     assert torch.equal(one[0], stats[1])                   # and independent of the frame's position in the slice
     for silu in (True, False):
-        out = torch.empty_like(x)
+        out = gout.like(x)
         hip.groupnorm_apply(x, out, stats, gamma, beta, 32, 1e-6, silu)
-        want = ref.groupnorm_apply(x, torch.empty(T, H, W, C, device="cuda"), want_stats, gamma, beta, 32, 1e-6, silu)
+        want = ref.groupnorm_apply(x, torch.empty(T, H, W, C, device="cuda"), want_stats, gamma, beta, 32, 1e-6, silu)    # reference buffer
         gn = torch.nn.functional.group_norm(x.float().permute(0, 3, 1, 2), 32, gamma, beta, 1e-6).permute(0, 2, 3, 1)
         assert rel_err(want, torch.nn.functional.silu(gn) if silu else gn) < 1e-4
         assert rel_err(out.float(), want) < TOL_BF16
         le.check_groupnorm_apply(out, x, stats, gamma, beta, 32, 1e-6, silu)    # (reference from the statistics the kernel was given)
+    gout.check("groupnorm")
 
 
 @pytest.mark.parametrize("Cin,kpad,hf", [(4, 128, 0), (4, 128, 2), (16, 448, 0)])
@@ -1010,41 +1069,48 @@ def test_im2col_causal(hip, ref, Cin, kpad, hf):
     x = rnd(T, H, W, Cin)
     halo = rnd(hf, H, W, Cin, seed=5) if hf else None
     geom = opsmod.Conv3dGeom(T, H, W, Cin, T, H, W, (3, 3, 3), (1, 1, 1), (2, 1, 1), halo)
-    out = torch.empty(T * H * W, kpad, device="cuda", dtype=BF16)
+    gout = Pool()
+    out = gout(T * H * W, kpad, dtype=BF16)
     hip.im2col_causal(x, out, geom)
-    assert torch.equal(out, ref.im2col_causal(x, torch.empty(T * H * W, kpad, device="cuda", dtype=BF16), geom))
+    assert torch.equal(out, ref.im2col_causal(x, torch.empty(T * H * W, kpad, device="cuda", dtype=BF16), geom))    # reference buffer
+    gout.check("im2col_causal")
 
 
 def test_blend_and_affine(hip, ref):
     T, h, w, C, H, W = 2, 5, 6, 32, 9, 11
     tile = rnd(T, h, w, C)
     wy, wx = torch.rand(h, device="cuda"), torch.rand(w, device="cuda")
-    acc, cnt = torch.zeros(T, H, W, C, device="cuda"), torch.zeros(H, W, device="cuda")
+    gout = Pool()
+    acc = gout(T, H, W, C, dtype=torch.float32, init=torch.zeros(T, H, W, C, device="cuda"))       # (accumulated into: start at zero)
+    cnt = gout(H, W, dtype=torch.float32, init=torch.zeros(H, W, device="cuda"))
     acc2, cnt2 = acc.clone(), cnt.clone()
     for (y0, x0) in ((0, 0), (3, 4), (4, 5)):
         hip.blend_accumulate(tile, acc, cnt, wy, wx, y0, x0)
         ref.blend_accumulate(tile, acc2, cnt2, wy, wx, y0, x0)
     assert torch.allclose(acc, acc2, atol=1e-5) and torch.allclose(cnt, cnt2, atol=1e-6)
-    out = torch.empty(T, H, W, 16, device="cuda", dtype=BF16)
+    out = gout(T, H, W, 16, dtype=BF16)
     hip.blend_finalize(acc, cnt, out, 0.9152, 0.1)
-    want = ref.blend_finalize(acc2, cnt2, torch.empty(T, H, W, 16, device="cuda"), 0.9152, 0.1)
+    want = ref.blend_finalize(acc2, cnt2, torch.empty(T, H, W, 16, device="cuda"), 0.9152, 0.1)    # reference buffer
     assert rel_err(out.float(), want) < TOL_BF16
     inp = rnd(50, 32)
-    o = torch.empty(50, 16, device="cuda", dtype=BF16)
+    o = gout(50, 16, dtype=BF16)
     hip.affine_slice(inp, o, 1 / 0.9152, -0.05)
-    assert rel_err(o.float(), ref.affine_slice(inp, torch.empty(50, 16, device="cuda"), 1 / 0.9152, -0.05)) < TOL_BF16
+    assert rel_err(o.float(), ref.affine_slice(inp, torch.empty(50, 16, device="cuda"), 1 / 0.9152, -0.05)) < TOL_BF16    # reference buffer
+    gout.check("blend, affine_slice")
 
 
 @pytest.mark.parametrize("rows,cols", [(64, 64), (100, 4416), (33, 16384), (7, 260), (9, 20000), (5, 65536)])
 def test_softmax_rows(hip, rows, cols):
     g = torch.Generator(device="cuda").manual_seed(rows + cols)
     S = torch.randn(rows, cols, device="cuda", generator=g) * 30.0
-    P = hip.empty(rows, cols)
+    gout = Pool()
+    P = gout(rows, cols, dtype=BF16)
     hip.softmax_rows(S, P, 0.044)
     want = torch.softmax(S * 0.044, dim=-1)
     assert torch.isfinite(P.float()).all()
     assert (P.float() - want).abs().max() <= 2 ** -8 * want.max() + 1e-6         # bf16 rounding of the output
     assert (P.float().sum(-1) - 1).abs().max() < 2e-2
+    gout.check("softmax_rows")
 
 
 @pytest.mark.parametrize("T,H,W", [(2, 16, 24), (1, 128, 160)], ids=["one_block", "two_row_blocks_20480_tokens"])
@@ -1145,20 +1211,21 @@ def test_conv_thin_output_4_cout_kernel(hip, ref, T, H, W, Cin, N, hf, kt, out_f
     To = T + pt - kt + 1
     geom = opsmod.Conv3dGeom(T, H, W, Cin, To, H, W, (kt, 3, 3), (1, 1, 1), (pt, 1, 1), halo)
     kw = dict(N=N, K=Wp.shape[1], bias=bias, conv=geom, ldc=N)
-    want = ref.gemm(x, Wp, torch.empty(To, H, W, N, device="cuda"), **kw)
-    outs = []
+    want = ref.gemm(x, Wp, torch.empty(To, H, W, N, device="cuda"), **kw)    # reference buffer
+    outs, gout = [], Pool()
     for new in (1, 0):
         hip.set_option("conv_thinout4", new)
         try:
-            out = torch.full((To, H, W, N), float("nan"), device="cuda", dtype=torch.float32 if out_f32 else BF16)
+            out = gout(To, H, W, N, dtype=torch.float32 if out_f32 else BF16)
             hip.gemm(x, Wp, out, out_f32=out_f32, **kw)
-            again = torch.full_like(out, float("nan"))
+            again = gout.like(out)
             hip.gemm(x, Wp, again, out_f32=out_f32, **kw)
         finally:
             hip.set_option("conv_thinout4", 1)
         assert not torch.isnan(out.float()).any() and torch.equal(out, again)          # every voxel written, reproducible
         assert rel_err(out.float(), want) < (1e-3 if out_f32 else TOL_BF16), new
         le.check_gemm(out, x, Wp, name=f"thin-output conv, conv_thinout4 {new}", **kw)
+        gout.check(f"thin-output conv, conv_thinout4 {new}")
         outs.append(out.float())
     assert rel_err(outs[0], outs[1]) < (2e-4 if out_f32 else 4e-3)
 

@@ -5,7 +5,10 @@ ragged row blocks in the GroupNorm statistics, the capped grid and the per-chunk
 smallest row and the first 1024-thread row of softmax_rows.  Each case states the launcher arithmetic that takes it there.
 
 Every result is checked element by element against the fp64 reference and the derived bound of tests/local_error.py (index
-kernels and untouched memory: bit-exact)."""
+kernels and untouched memory: bit-exact).
+
+Every tensor a svr_* entry point writes comes from tests/guarded_out.py (``gout = Pool()``); where a launch gets a view that leaves
+the last row / frame of the buffer out, the buffer starts as NaN (``init=``) and the test asserts that the row stayed NaN."""
 import math
 
 import pytest
@@ -13,6 +16,7 @@ import torch
 
 import local_error as le
 from conftest import sub
+from guarded_out import Pool
 from ops_reference import TorchOps, H16, H16_SCALE, _ld
 
 pytestmark = pytest.mark.gpu
@@ -29,6 +33,10 @@ def hip():
 @pytest.fixture(scope="module")
 def ref():
     return TorchOps("cuda:0", act_dtype=torch.float32)
+
+
+def nans(*shape, dtype=BF16):
+    return torch.full(shape, float("nan"), device="cuda", dtype=dtype)
 
 
 def rnd(*shape, scale=1.0, seed=0, dtype=BF16, shift=0.0):
@@ -56,13 +64,15 @@ def test_rmsnorm_mod_rows_in_flight(hip, kind, dim):
     xall = rnd(RMS_ROWS[-1], dim, scale=2.0, dtype=F32) * ramp
     xall = (xall * H16_SCALE).to(H16) if kind == H16 else xall.to(kind)
     w, sc, sh = (rnd(dim, dtype=F32, seed=s) for s in (1, 2, 3))
+    gout = Pool()
     for rows in RMS_ROWS:
         x = xall[:rows]
         for kw in (dict(), dict(scale=sc, shift=sh), dict(w=w, scale=sc, shift=sh)):
-            out = torch.full((rows + 1, dim), float("nan"), device="cuda", dtype=BF16)
+            out = gout(rows + 1, dim, dtype=BF16, init=nans(rows + 1, dim))
             hip.rmsnorm_mod(x, out[:rows], 1e-5, **kw)
             assert bool(torch.isnan(out[rows]).all())                               # nothing behind the last row
             le.check_rmsnorm_mod(out[:rows], x, 1e-5, name=f"rmsnorm_mod rows {rows} {sorted(kw)}", **kw)
+            gout.check(f"rmsnorm_mod rows {rows}")
 
 
 # ------------------------------------------------------------------ qknorm_rope
@@ -80,9 +90,11 @@ def _qknorm_case(hip, rows, heads, n_freq):
     pos = torch.stack([r % 70 - 3, (r * 7) % n_pos, (r * 13 + 5) % (n_pos + 4)], -1).to(torch.int16).cuda()
     cos, sin = _rope_tables(n_pos, n_freq)
     wq, wk = rnd(128, dtype=F32, seed=1) + 1, rnd(128, dtype=F32, seed=2) + 1
-    got = qkv.clone()
+    gout = Pool()
+    got = gout.like(qkv, init=qkv)                                                 # (in place: q and k rewritten, V left alone)
     hip.qknorm_rope(got, heads, pos, t_offset, cos, sin, wq, wk, 1e-5)
     le.check_qknorm_rope(got, qkv, heads, pos, t_offset, cos, sin, wq, wk, 1e-5, name=f"qknorm_rope rows {rows} heads {heads} n_freq {n_freq}")
+    gout.check("qknorm_rope")
 
 
 @pytest.mark.parametrize("n_freq", [21, 10, 1])
@@ -118,24 +130,26 @@ def _gn_case(hip, H, W, C, kind, groups, silus=(True,)):
     T = 2
     x = rnd(T, H, W, C, scale=1.5, shift=0.7, dtype=kind, seed=C)
     gamma, beta = rnd(C, dtype=F32, seed=1) + 1, rnd(C, dtype=F32, seed=2)
-    stats = torch.empty(T, groups, 2, device="cuda", dtype=torch.float64)
+    gout = Pool()
+    stats = gout(T, groups, 2, dtype=torch.float64)
     hip.groupnorm_stats(x, stats, groups)
     slab = 64 if H * W * C > (1 << 26) else None                                  # fp64 temporaries of a slab: <= 0.5 GB each
     tag = f"HW {H * W} C {C} groups {groups}"
     for t in range(T):
         le.check_groupnorm_stats(stats[t:t + 1], x[t:t + 1], groups, name=f"groupnorm_stats {tag}", slab_rows=slab)
-    again = torch.empty_like(stats)
+    again = gout.like(stats)
     hip.groupnorm_stats(x, again, groups)
     assert torch.equal(stats, again)                                              # fixed-order reduction: bit-reproducible
-    one = torch.empty(1, groups, 2, device="cuda", dtype=torch.float64)
+    one = gout(1, groups, 2, dtype=torch.float64)
     hip.groupnorm_stats(x[1:2].contiguous(), one, groups)
     assert torch.equal(one[0], stats[1])                                          # independent of the frame's position, at nblk > 1 too
     for silu in silus:
-        out = torch.full((T + 1, H, W, C), float("nan"), device="cuda", dtype=BF16)
+        out = gout(T + 1, H, W, C, dtype=BF16, init=nans(T + 1, H, W, C))
         hip.groupnorm_apply(x, out[:T], stats, gamma, beta, groups, 1e-6, silu)
         assert bool(torch.isnan(out[T, 0, 0]).all())                              # nothing behind the last frame
         le.check_groupnorm_apply(out[:T], x, stats, gamma, beta, groups, 1e-6, silu, name=f"groupnorm_apply {tag} silu {silu}",
                                  slab_rows=slab)
+        gout.check(f"groupnorm {tag} silu {silu}")
 
 
 @pytest.mark.parametrize("C", [128, 256, 512])
@@ -159,12 +173,14 @@ def test_groupnorm_apply_capped_grid_on_an_untiled_4k_frame(hip, kind):
     H, W, C = 2160, 3840, 128
     x = rnd(1, H, W, C, scale=1.5, shift=0.7, dtype=kind)
     gamma, beta = rnd(C, dtype=F32, seed=1) + 1, rnd(C, dtype=F32, seed=2)
-    stats = torch.empty(1, 32, 2, device="cuda", dtype=torch.float64)
+    gout = Pool()
+    stats = gout(1, 32, 2, dtype=torch.float64)
     hip.groupnorm_stats(x, stats, 32)
     le.check_groupnorm_stats(stats, x, 32, name="groupnorm_stats 4K frame", slab_rows=64)
-    out = torch.full((1, H, W, C), float("nan"), device="cuda", dtype=BF16)
+    out = gout(1, H, W, C, dtype=BF16)
     hip.groupnorm_apply(x, out, stats, gamma, beta, 32, 1e-6, True)
     le.check_groupnorm_apply(out, x, stats, gamma, beta, 32, 1e-6, True, name="groupnorm_apply 4K frame", slab_rows=64)
+    gout.check("groupnorm 4K frame")
 
 
 @pytest.mark.parametrize("kind", KINDS, ids=KIND_IDS)
@@ -177,12 +193,14 @@ def test_groupnorm_apply_channel_counts_that_do_not_divide_a_sweep(hip, ref, C, 
     T, H, W = 2, 37, 41
     x = rnd(T, H, W, C, scale=1.5, shift=0.7, dtype=kind, seed=C)
     gamma, beta = rnd(C, dtype=F32, seed=1) + 1, rnd(C, dtype=F32, seed=2)
-    stats = ref.groupnorm_stats(x, torch.empty(T, groups, 2, device="cuda", dtype=torch.float64), groups)
+    stats = ref.groupnorm_stats(x, torch.empty(T, groups, 2, device="cuda", dtype=torch.float64), groups)    # reference buffer
+    gout = Pool()
     for silu in (True, False):
-        out = torch.full((T + 1, H, W, C), float("nan"), device="cuda", dtype=BF16)
+        out = gout(T + 1, H, W, C, dtype=BF16, init=nans(T + 1, H, W, C))
         hip.groupnorm_apply(x, out[:T], stats, gamma, beta, groups, 1e-6, silu)
         assert bool(torch.isnan(out[T]).all())
         le.check_groupnorm_apply(out[:T], x, stats, gamma, beta, groups, 1e-6, silu, name=f"groupnorm_apply C {C} silu {silu}")
+        gout.check(f"groupnorm_apply C {C} silu {silu}")
 
 
 # ------------------------------------------------------------------ softmax_rows
@@ -197,25 +215,29 @@ def test_softmax_rows_edges(hip, cols):
     S[1, -1] = 400.0                                                               # the maximum is the row's last element
     S[2] = 3.25                                                                    # a row of equal values
     S[3, 0] = -1e4                                                                 # exp2 underflows to zero
-    P = torch.full((8, cols), float("nan"), device="cuda", dtype=BF16)
+    gout = Pool()
+    P = gout(8, cols, dtype=BF16, init=nans(8, cols))
     hip.softmax_rows(S, P[:7], 0.044)
     assert bool(torch.isnan(P[7]).all())
     le.check_softmax_rows(P[:7], S, 0.044, name=f"softmax_rows cols {cols}")
+    gout.check(f"softmax_rows cols {cols}")
 
 
 # ------------------------------------------------------------------ rows_mean, unpatchify_euler
 def test_rows_mean_one_group_and_ragged_dim(hip):
     """n_groups = 1 (a copy through fp32: bit-exact); dim 520 = 65 chunks: the second 64-thread block has one live thread."""
     src = rnd(58, 2560)
-    dst = torch.empty(58, 2560, device="cuda", dtype=BF16)
+    gout = Pool()
+    dst = gout(58, 2560, dtype=BF16)
     hip.rows_mean(src, dst, 1, 58)
     assert torch.equal(dst, src)
     for n_groups, rows, dim in ((7, 58, 520), (3, 5, 8)):
         src = rnd(n_groups * rows, dim)
-        dst = torch.full((rows + 1, dim), float("nan"), device="cuda", dtype=BF16)
+        dst = gout(rows + 1, dim, dtype=BF16, init=nans(rows + 1, dim))
         hip.rows_mean(src, dst[:rows], n_groups, rows)
         assert bool(torch.isnan(dst[rows]).all())
         le.check(f"rows_mean {n_groups} x {rows} x {dim}", dst[:rows], *le.rows_mean_reference(src, n_groups, rows))
+    gout.check("rows_mean")
 
 
 def test_unpatchify_euler_padded_prediction(hip):
@@ -224,14 +246,16 @@ def test_unpatchify_euler_padded_prediction(hip):
     pred = rnd(T * (H // 2) * (W // 2), 96)
     pred[:, 4 * C:] = float("nan")
     x_t = rnd(T, H, W, C, seed=4)
+    gout = Pool()
     for xt in (x_t, None):
-        o = torch.empty(T, H, W, C, device="cuda", dtype=BF16)
+        o = gout(T, H, W, C, dtype=BF16)
         hip.unpatchify_euler(pred, xt, o)
         le.check("unpatchify_euler ldp 96", o, *le.unpatchify_euler_reference(pred, xt, o.shape))
-    o = torch.empty(T, H, W, C, device="cuda", dtype=BF16)
+    o = gout(T, H, W, C, dtype=BF16)
     hip.unpatchify_euler(pred, None, o)                                            # without x_t it is an index map: bit-exact
     want = pred[:, :4 * C].reshape(T, H // 2, W // 2, 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(T, H, W, C)
     assert torch.equal(o, want)
+    gout.check("unpatchify_euler")
 
 
 # ------------------------------------------------------------------ window attention, first-generation kernel
@@ -246,7 +270,9 @@ def test_attn_varlen_windows_beyond_the_row_table(hip, lens, heads):
     seq_rows = torch.cat([torch.randint(0, n_rows, (L,), generator=g) for L in lens]).to(torch.int32).cuda()
     out_rows = torch.randperm(total + 16, generator=g)[:total].to(torch.int32).cuda()
     cu = torch.tensor([0] + list(torch.tensor(lens).cumsum(0)), dtype=torch.int32).cuda()
-    out = torch.full((total + 16, heads * D), 7.0, device="cuda", dtype=BF16)
+    gout = Pool()
+    out = gout(total + 16, heads * D, dtype=BF16, init=torch.full((total + 16, heads * D), 7.0, device="cuda", dtype=BF16))
     before = out.clone()
     hip.attn_varlen(qkv, out, seq_rows, out_rows, cu, max(lens), heads, D, 1.0 / math.sqrt(D))
     le.check_attn(out, qkv, seq_rows, out_rows, cu, heads, D, 1.0 / math.sqrt(D), before=before, name=f"attn_varlen {lens} x {heads}")
+    gout.check("attn_varlen beyond the row table")

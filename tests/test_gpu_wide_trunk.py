@@ -6,7 +6,9 @@ Contract: the arithmetic is unchanged (bf16 MFMA operands, fp32 accumulate); wha
 not rounded to bf16 when it is stored.  So an fp32 store must meet the fp32-store bound 1e-3 (measured ~3e-4: MFMA summation
 order), fused GroupNorm statistics are those of the fp32 values that were stored, and a bf16 store after an fp32 residual
 meets the bf16-store bound 2.5e-3.  An h16 store rounds once to 11 significant bits (2.8e-4 rms): it meets the fp32-store bound
-1e-3 as well (measured ~4e-4), and its fused statistics are those of the h16 values that were stored."""
+1e-3 as well (measured ~4e-4), and its fused statistics are those of the h16 values that were stored.
+
+Every tensor a svr_* entry point writes comes from tests/guarded_out.py (``gout = Pool()``; ``init=`` for in-place launches)."""
 import math
 
 import pytest
@@ -14,6 +16,7 @@ import torch
 
 import local_error as le
 from conftest import sub, rel_err
+from guarded_out import Pool
 from ops_reference import TorchOps, EPI_BIAS, EPI_RESID_GATE, H16, H16_SCALE, _ld
 
 pytestmark = pytest.mark.gpu
@@ -59,19 +62,21 @@ def test_conv_halo_wide_trunk_epilogues(hip, ref, frag, out_dt, res_dt, Cin, Cou
     resid = rnd(To, H, W, Cout, seed=11, dtype=res_dt) if res_dt is not None else None
     kw = dict(N=Cout, K=Wp.shape[1], bias=bias, conv=geom, ldc=Cout, ldr=Cout, resid=resid,
               epilogue=EPI_RESID_GATE if resid is not None else EPI_BIAS, W_frag=hip.pack_conv_frag(Wp, 3, Cin, Cout) if frag else None)
-    want = ref.gemm(x, Wp, torch.empty(To, H, W, Cout, device="cuda"), **{k: v for k, v in kw.items() if k != "W_frag"})
-    out = torch.full((To, H, W, Cout), float("nan"), device="cuda", dtype=out_dt)
+    want = ref.gemm(x, Wp, torch.empty(To, H, W, Cout, device="cuda"), **{k: v for k, v in kw.items() if k != "W_frag"})    # reference buffer
+    gout = Pool()
+    out = gout(To, H, W, Cout, dtype=out_dt)
     got, stats = hip.gemm(x, Wp, out, gn_groups=32, out_f32=out_dt in WIDE, **kw)
     assert got is out and stats is not None and not torch.isnan(out.float()).any()
     assert rel_err(_ld(out), want) < (TOL_F32 if out_dt in WIDE else TOL_BF16)
     le.check_gemm(out, x, Wp, **kw)
-    plain = torch.empty_like(out)
+    plain = gout.like(out)
     hip.gemm(x, Wp, plain, out_f32=out_dt in WIDE, **kw)
     assert torch.equal(plain, out)                                   # the fused statistics do not change the output
-    ws = ref.groupnorm_stats(out, torch.empty(To, 32, 2, device="cuda", dtype=torch.float64), 32)
+    ws = ref.groupnorm_stats(out, torch.empty(To, 32, 2, device="cuda", dtype=torch.float64), 32)    # reference buffer
     assert rel_err(stats[..., 0], ws[..., 0]) < 1e-5 and rel_err(stats[..., 1], ws[..., 1]) < 1e-6
-    _, again = hip.gemm(x, Wp, torch.empty_like(out), gn_groups=32, out_f32=out_dt in WIDE, **kw)
+    _, again = hip.gemm(x, Wp, gout.like(out), gn_groups=32, out_f32=out_dt in WIDE, **kw)
     assert torch.equal(again, stats)
+    gout.check("halo conv, wide trunk")
 
 
 @pytest.mark.parametrize("wide", WIDE, ids=["fp32", "h16"])
@@ -86,11 +91,13 @@ def test_conv_halo_wide_trunk_in_place_residual(hip, ref, wide):
     trunk = rnd(T, H, W, C, seed=5, dtype=wide)
     kw = dict(N=C, K=Wp.shape[1], bias=rnd(C, dtype=F32, seed=3), conv=geom, ldc=C, ldr=C, epilogue=EPI_RESID_GATE,
               W_frag=hip.pack_conv_frag(Wp, 3, C, C), out_f32=True)
-    sep = torch.empty_like(trunk)
+    gout = Pool()
+    sep = gout.like(trunk)
     hip.gemm(x, Wp, sep, resid=trunk, **kw)
-    inplace = trunk.clone()
+    inplace = gout.like(trunk, init=trunk)
     hip.gemm(x, Wp, inplace, resid=inplace, **kw)
     assert torch.equal(inplace, sep)
+    gout.check("halo conv, in-place residual")
 
 
 @pytest.mark.parametrize("wide", WIDE, ids=["fp32", "h16"])
@@ -104,7 +111,8 @@ def test_conv_subpixel_wide_output_and_statistics(hip, ref, kt, ts, hf, wide):
     halo = rnd(hf, H, W, Cin, seed=9) if hf else None
     pt = hf if hf else kt - 1
     To = T + pt - kt + 1
-    out = torch.full((To * ts, 2 * H, 2 * W, Cout), float("nan"), device="cuda", dtype=wide)
+    gout = Pool()
+    out = gout(To * ts, 2 * H, 2 * W, Cout, dtype=wide)                # (poisoned: the phases together must write all of it)
     want = torch.zeros(out.shape, device="cuda")
     shared = {"frames": out.shape[0]}
     for tz in range(ts):
@@ -121,9 +129,10 @@ def test_conv_subpixel_wide_output_and_statistics(hip, ref, kt, ts, hf, wide):
             ref.gemm(x, Wp, want[tz:], **kw)
     assert not torch.isnan(out).any() and rel_err(_ld(out), want) < TOL_F32
     stats = hip.gn_shared_stats(shared)
-    ws = ref.groupnorm_stats(out, torch.empty(out.shape[0], G, 2, device="cuda", dtype=torch.float64), G)
+    ws = ref.groupnorm_stats(out, torch.empty(out.shape[0], G, 2, device="cuda", dtype=torch.float64), G)    # reference buffer
     # (compare as vectors, like the bf16 test of this kernel)
     assert stats is not None and rel_err(stats[..., 0], ws[..., 0]) < 1e-5 and rel_err(stats[..., 1], ws[..., 1]) < 1e-6
+    gout.check("sub-pixel conv, wide output")
 
 
 @pytest.mark.parametrize("epi", [1, 2], ids=["epi_direct", "epi_lds"])
@@ -137,11 +146,12 @@ def test_gemm_wide_residual_stream(hip, ref, epi, M, N, K):
         A = rnd(M, K)
         W = packing.pack_matrix(rnd(N, K, scale=1.0 / math.sqrt(K), seed=1), "cuda")
         bias, gate = rnd(N, dtype=F32, seed=3), rnd(N, dtype=F32, seed=4)
-        hid = rnd(M + 58, N, seed=5, dtype=F32)
+        gout = Pool()
+        hid = gout(M + 58, N, dtype=F32, init=rnd(M + 58, N, seed=5, dtype=F32))
         tail = hid[M:].clone()
-        want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate,
+        want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate,    # reference buffer
                         resid=hid[:M].clone())
-        narrow = torch.empty(M, N, device="cuda", dtype=BF16)
+        narrow = gout(M, N, dtype=BF16)
         hip.gemm(A, W, narrow, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid[:M])
         assert rel_err(narrow.float(), want) < TOL_BF16
         before = hid[:M].clone()
@@ -149,6 +159,7 @@ def test_gemm_wide_residual_stream(hip, ref, epi, M, N, K):
         hip.gemm(A, W, hid[:M], N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid[:M], out_f32=True)
         assert rel_err(hid[:M], want) < TOL_F32 and torch.equal(hid[M:], tail)
         le.check_gemm(hid[:M], A, W, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=before, name="fp32 stream in place")
+        gout.check("fp32 residual stream")
     finally:
         hip.set_option("gemm_epi", 0)
 
@@ -166,20 +177,22 @@ def test_gemm_h16_trunk_epilogues(hip, ref, epi, M, N, K, gated):
         W = packing.pack_matrix(rnd(N, K, scale=1.0 / math.sqrt(K), seed=1), "cuda")
         bias = rnd(N, dtype=F32, seed=3)
         gate = rnd(N, dtype=F32, seed=4) if gated else None
-        out = torch.full((M, N), float("nan"), device="cuda", dtype=H16)
+        gout = Pool()
+        out = gout(M, N, dtype=H16)
         hip.gemm(A, W, out, N=N, K=K, bias=bias, out_f32=True)
-        assert rel_err(_ld(out), ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias)) < TOL_F32
+        assert rel_err(_ld(out), ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias)) < TOL_F32    # reference buffer
         le.check_gemm(out, A, W, N=N, K=K, bias=bias, name="bias -> h16")
         for res_dt, out_dt in ((H16, H16), (H16, BF16), (BF16, H16)):
-            res = rnd(M, N, seed=5, dtype=res_dt)
-            want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=res)
-            o = torch.full((M, N), float("nan"), device="cuda", dtype=out_dt)
+            res = gout(M, N, dtype=res_dt, init=rnd(M, N, seed=5, dtype=res_dt))      # (written in place below where res_dt == out_dt)
+            want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=res)    # reference buffer
+            o = gout(M, N, dtype=out_dt)
             hip.gemm(A, W, o, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=res, out_f32=out_dt in WIDE)
             assert rel_err(_ld(o), want) < (TOL_F32 if out_dt in WIDE else TOL_BF16), (res_dt, out_dt)
             le.check_gemm(o, A, W, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=res, name=f"{res_dt} residual -> {out_dt}")
             if res_dt == out_dt:                                       # in place on the trunk
                 hip.gemm(A, W, res, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=res, out_f32=True)
                 assert torch.equal(res, o)
+            gout.check(f"h16 trunk {res_dt} -> {out_dt}")
     finally:
         hip.set_option("gemm_epi", 0)
 
@@ -195,27 +208,31 @@ def test_generic_conv_h16_output(hip, ref):
         To, Ho, Wo = (T + pt - k[0]) // stride[0] + 1, (Hh + pads[0] + pads[1] - k[1]) // stride[1] + 1, (Ww + pads[0] + pads[1] - k[2]) // stride[2] + 1
         geom = opsmod.Conv3dGeom(T, Hh, Ww, Cin, To, Ho, Wo, k, stride, (pt, pads[0], pads[0]), None)
         kw = dict(N=Cout, K=Wc.shape[1], bias=rnd(Cout, dtype=F32, seed=3), conv=geom, ldc=Cout)
-        out = torch.full((To, Ho, Wo, Cout), float("nan"), device="cuda", dtype=H16)
+        gout = Pool()
+        out = gout(To, Ho, Wo, Cout, dtype=H16)
         hip.gemm(x, Wc, out, out_f32=True, **kw)
-        assert rel_err(_ld(out), ref.gemm(x, Wc, torch.empty(To, Ho, Wo, Cout, device="cuda"), **kw)) < TOL_F32
+        assert rel_err(_ld(out), ref.gemm(x, Wc, torch.empty(To, Ho, Wo, Cout, device="cuda"), **kw)) < TOL_F32    # reference buffer
         le.check_gemm(out, x, Wc, name=f"generic conv {k} -> h16", **kw)
+        gout.check(f"generic conv {k} -> h16")
 
 
 @pytest.mark.parametrize("rows,dim", [(1000, 2560), (58, 2560), (7, 3072), (333, 256)])
 def test_rmsnorm_mod_fp32_input(hip, ref, rows, dim):
     x = rnd(rows, dim, scale=2.0, dtype=F32)
     w, sc, sh = (rnd(dim, dtype=F32, seed=s) for s in (1, 2, 3))
+    gout = Pool()
     for kw in (dict(), dict(scale=sc, shift=sh), dict(w=w, scale=sc, shift=sh)):
-        out = torch.empty(rows, dim, device="cuda", dtype=BF16)
+        out = gout(rows, dim, dtype=BF16)
         hip.rmsnorm_mod(x, out, 1e-5, **kw)
-        assert rel_err(out.float(), ref.rmsnorm_mod(x, torch.empty(rows, dim, device="cuda"), 1e-5, **kw)) < TOL_BF16
+        assert rel_err(out.float(), ref.rmsnorm_mod(x, torch.empty(rows, dim, device="cuda"), 1e-5, **kw)) < TOL_BF16    # reference buffer
         le.check_rmsnorm_mod(out, x, 1e-5, **kw)
     # a bf16-representable fp32 input gives the bf16 kernel's bits
     xb = rnd(rows, dim, scale=2.0)
-    a, b = torch.empty(rows, dim, device="cuda", dtype=BF16), torch.empty(rows, dim, device="cuda", dtype=BF16)
+    a, b = gout(rows, dim, dtype=BF16), gout(rows, dim, dtype=BF16)
     hip.rmsnorm_mod(xb, a, 1e-5, scale=sc, shift=sh)
     hip.rmsnorm_mod(xb.float(), b, 1e-5, scale=sc, shift=sh)
     assert torch.equal(a, b)
+    gout.check("rmsnorm_mod fp32 input")
 
 
 @pytest.mark.parametrize("C", [128, 256, 512])
@@ -226,26 +243,28 @@ def test_groupnorm_h16_input(hip, ref, C):
     g = torch.Generator(device="cuda").manual_seed(C)
     x = ((torch.randn(T, H, W, C, generator=g, device="cuda") * 1.5 + 0.7) * H16_SCALE).to(H16)
     gamma, beta = rnd(C, dtype=F32, seed=1) + 1, rnd(C, dtype=F32, seed=2)
-    stats = torch.empty(T, 32, 2, device="cuda", dtype=torch.float64)
+    gout = Pool()
+    stats = gout(T, 32, 2, dtype=torch.float64)
     hip.groupnorm_stats(x, stats, 32)
-    want_stats = ref.groupnorm_stats(x, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)
+    want_stats = ref.groupnorm_stats(x, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)    # reference buffer
     assert torch.allclose(stats, want_stats, rtol=1e-5)
     assert torch.allclose(stats, ref.groupnorm_stats(_ld(x), torch.empty_like(stats), 32), rtol=1e-5)      # == the fp32 view's
     le.check_groupnorm_stats(stats, x, 32)
     for silu in (True, False):
-        out = torch.empty(T, H, W, C, device="cuda", dtype=BF16)
+        out = gout(T, H, W, C, dtype=BF16)
         hip.groupnorm_apply(x, out, stats, gamma, beta, 32, 1e-6, silu)
-        want = ref.groupnorm_apply(x, torch.empty(T, H, W, C, device="cuda"), want_stats, gamma, beta, 32, 1e-6, silu)
+        want = ref.groupnorm_apply(x, torch.empty(T, H, W, C, device="cuda"), want_stats, gamma, beta, 32, 1e-6, silu)    # reference buffer
         assert rel_err(out.float(), want) < TOL_BF16
         le.check_groupnorm_apply(out, x, stats, gamma, beta, 32, 1e-6, silu)
     # the h16 kernels on an exactly representable tensor == the fp32 kernels on its fp32 view, bit for bit
-    sf = torch.empty_like(stats)
+    sf = gout.like(stats)
     hip.groupnorm_stats(_ld(x), sf, 32)
     assert torch.equal(stats, sf)
-    a, b = torch.empty(T, H, W, C, device="cuda", dtype=BF16), torch.empty(T, H, W, C, device="cuda", dtype=BF16)
+    a, b = gout(T, H, W, C, dtype=BF16), gout(T, H, W, C, dtype=BF16)
     hip.groupnorm_apply(x, a, stats, gamma, beta, 32, 1e-6, True)
     hip.groupnorm_apply(_ld(x), b, stats, gamma, beta, 32, 1e-6, True)
     assert rel_err(a.float(), b.float()) < 2e-4 and (a != b).float().mean() < 0.02    # (x * (a * 64) vs (x * 64) * a: last-bit flips)
+    gout.check("groupnorm h16 input")
 
 
 @pytest.mark.parametrize("C", [128, 256, 512])
@@ -253,26 +272,28 @@ def test_groupnorm_fp32_input(hip, ref, C):
     T, H, W = 3, 37, 41
     x = rnd(T, H, W, C, scale=1.5, dtype=F32) + 0.7
     gamma, beta = rnd(C, dtype=F32, seed=1) + 1, rnd(C, dtype=F32, seed=2)
-    stats = torch.empty(T, 32, 2, device="cuda", dtype=torch.float64)
+    gout = Pool()
+    stats = gout(T, 32, 2, dtype=torch.float64)
     hip.groupnorm_stats(x, stats, 32)
-    want_stats = ref.groupnorm_stats(x, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)
+    want_stats = ref.groupnorm_stats(x, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)    # reference buffer
     assert torch.allclose(stats, want_stats, rtol=1e-5)
     le.check_groupnorm_stats(stats, x, 32)
     for silu in (True, False):
-        out = torch.empty(T, H, W, C, device="cuda", dtype=BF16)
+        out = gout(T, H, W, C, dtype=BF16)
         hip.groupnorm_apply(x, out, stats, gamma, beta, 32, 1e-6, silu)
-        want = ref.groupnorm_apply(x, torch.empty(T, H, W, C, device="cuda"), want_stats, gamma, beta, 32, 1e-6, silu)
+        want = ref.groupnorm_apply(x, torch.empty(T, H, W, C, device="cuda"), want_stats, gamma, beta, 32, 1e-6, silu)    # reference buffer
         assert rel_err(out.float(), want) < TOL_BF16
         le.check_groupnorm_apply(out, x, stats, gamma, beta, 32, 1e-6, silu)
     xb = rnd(T, H, W, C, scale=1.5)                               # bf16-representable fp32 input == the bf16 kernel, bit for bit
-    sb, sf = torch.empty_like(stats), torch.empty_like(stats)
+    sb, sf = gout.like(stats), gout.like(stats)
     hip.groupnorm_stats(xb, sb, 32)
     hip.groupnorm_stats(xb.float(), sf, 32)
     assert torch.equal(sb, sf)
-    a, b = torch.empty_like(xb), torch.empty_like(xb)
+    a, b = gout.like(xb), gout.like(xb)
     hip.groupnorm_apply(xb, a, sb, gamma, beta, 32, 1e-6, True)
     hip.groupnorm_apply(xb.float(), b, sb, gamma, beta, 32, 1e-6, True)
     assert torch.equal(a, b)
+    gout.check("groupnorm fp32 input")
 
 
 @pytest.mark.parametrize("wide", WIDE, ids=["fp32", "h16"])
@@ -285,13 +306,15 @@ def test_conv_thin_input_wide_output(hip, ref, wide):
     Wp = packing.pack_conv3d(rnd(Cout, 3, 3, 3, 3, scale=1.0 / math.sqrt(81), seed=2), "cuda", 4)
     geom = opsmod.Conv3dGeom(T, H, W, 4, T, H, W, (3, 3, 3), (1, 1, 1), (2, 1, 1), None)
     kw = dict(N=Cout, K=Wp.shape[1], bias=rnd(Cout, dtype=F32, seed=3), conv=geom, ldc=Cout)
-    out = torch.full((T, H, W, Cout), float("nan"), device="cuda", dtype=wide)
+    gout = Pool()
+    out = gout(T, H, W, Cout, dtype=wide)
     _, stats = hip.gemm(x, Wp, out, gn_groups=32, out_f32=True, **kw)
-    want = ref.gemm(x, Wp, torch.empty(T, H, W, Cout, device="cuda"), **kw)
+    want = ref.gemm(x, Wp, torch.empty(T, H, W, Cout, device="cuda"), **kw)    # reference buffer
     assert rel_err(_ld(out), want) < TOL_F32 and stats is not None
     le.check_gemm(out, x, Wp, name="thin-input conv wide output", **kw)
-    ws = ref.groupnorm_stats(out, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)
+    ws = ref.groupnorm_stats(out, torch.empty(T, 32, 2, device="cuda", dtype=torch.float64), 32)    # reference buffer
     assert rel_err(stats[..., 0], ws[..., 0]) < 1e-5 and rel_err(stats[..., 1], ws[..., 1]) < 1e-6
+    gout.check("thin-input conv, wide output")
 
 
 def test_vae_engine_storage_regimes_agree_with_their_cpu_emulation(hip):
@@ -329,14 +352,16 @@ def test_rmsnorm_mod_h16_input(hip, ref, rows, dim):
     xv = rnd(rows, dim, scale=2.0, dtype=F32)
     x = (xv * H16_SCALE).to(H16)
     w, sc, sh = (rnd(dim, dtype=F32, seed=s) for s in (1, 2, 3))
+    gout = Pool()
     for kw in (dict(), dict(scale=sc, shift=sh), dict(w=w, scale=sc, shift=sh)):
-        out = torch.empty(rows, dim, device="cuda", dtype=BF16)
+        out = gout(rows, dim, dtype=BF16)
         hip.rmsnorm_mod(x, out, 1e-5, **kw)
-        assert rel_err(out.float(), ref.rmsnorm_mod(x, torch.empty(rows, dim, device="cuda"), 1e-5, **kw)) < TOL_BF16
+        assert rel_err(out.float(), ref.rmsnorm_mod(x, torch.empty(rows, dim, device="cuda"), 1e-5, **kw)) < TOL_BF16    # reference buffer
         le.check_rmsnorm_mod(out, x, 1e-5, **kw)
-        same = torch.empty_like(out)
+        same = gout.like(out)
         hip.rmsnorm_mod(_ld(x), same, 1e-5, **kw)                 # == the fp32 kernel on the values the halves stand for
         assert torch.equal(out, same)
+        gout.check("rmsnorm_mod h16 input")
 
 
 @pytest.mark.parametrize("M,N,K", [(70000, 2560, 2560), (16300, 4096, 192), (9000, 2560, 6912)])
@@ -352,21 +377,24 @@ def test_gemm_persistent_h16_stream_epilogues(hip, ref, M, N, K):
     hid0 = (rnd(M, N, seed=6, dtype=F32) * 3.0 * H16_SCALE).to(H16)
     hip.record_kernel_class = True
     try:
-        out = torch.full((M, N), float("nan"), device="cuda", dtype=H16)
+        gout = Pool()
+        out = gout(M, N, dtype=H16)
         hip.gemm(A, W, out, N=N, K=K, bias=bias, out_f32=True, W_frag=Wf)
         assert hip.last_kernel_class == "gemm_persistent"
-        assert rel_err(_ld(out), ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias)) < TOL_F32
+        assert rel_err(_ld(out), ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias)) < TOL_F32    # reference buffer
         le.check_gemm(out, A, W, N=N, K=K, bias=bias, name="persistent bias -> h16")
-        want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid0)
+        gout.check("persistent bias -> h16")
+        want = ref.gemm(A, W, torch.empty(M, N, device="cuda"), N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid0)    # reference buffer
         outs = []
         for frag in (Wf, None, Wf):
-            hid = hid0.clone()
+            hid = gout.like(hid0, init=hid0)
             hip.gemm(A, W, hid, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid, out_f32=True, W_frag=frag)
             assert hip.last_kernel_class == "gemm_persistent"
             outs.append(hid)
         assert rel_err(_ld(outs[0]), want) < TOL_F32
         le.check_gemm(outs[0], A, W, N=N, K=K, bias=bias, epilogue=EPI_RESID_GATE, gate=gate, resid=hid0, name="persistent h16 stream")
         assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+        gout.check("persistent h16 stream")
     finally:
         hip.record_kernel_class = False
 
