@@ -133,6 +133,9 @@ int svr_groupnorm_reduce(const void* partial, double* stats, int32_t T, int32_t 
 int svr_rmsnorm_mod(const void* x, void* y, int64_t rows, int32_t dim, float eps, const float* w, const float* scale,
                     const float* shift, int32_t x_f32, void* stream) {
     StreamDeviceGuard on_stream_device(stream);
+    // layout contract (checked on an empty call too): rows are dense and dim % 8 == 0, so a 16-byte aligned base makes every uint4
+    // load of x and store of y naturally aligned
+    if ((uintptr_t)x % 16 || (uintptr_t)y % 16) return fail("svr_rmsnorm_mod: x and y must be 16-byte aligned (rows are read and written in 16-byte units)");
     if (rows <= 0) return 0;
     if (dim <= 0 || dim % 8 || dim > 64 * 8 * 8) return fail("svr_rmsnorm_mod: dim must be a multiple of 8 and <= 4096");
     if (!x || !y) return fail("svr_rmsnorm_mod: null pointer");
@@ -228,6 +231,11 @@ int svr_conv_pack_frag(const void* W, void* out, int32_t N, int32_t K, int32_t k
 int svr_softmax_rows(const float* S, void* P, int64_t rows, int32_t cols, int64_t ld_s, int64_t ld_p, float scale,
                      void* stream) {
     StreamDeviceGuard on_stream_device(stream);
+    // layout contract (checked on an empty call too, so that a caller's layout can be validated without a launch): float4 loads at
+    // S + r * ld_s + 4 j, uint2 stores at P + r * ld_p + 4 j
+    if (ld_s < cols || ld_p < cols) return fail("svr_softmax_rows: ld_s and ld_p must cover the cols columns of a row");
+    if ((uintptr_t)S % 16) return fail("svr_softmax_rows: S must be 16-byte aligned (rows are read as float4)");
+    if ((uintptr_t)P % 8) return fail("svr_softmax_rows: P must be 8-byte aligned (rows are written in 8-byte units)");
     if (rows <= 0 || cols <= 0) return 0;
     if (!S || !P) return fail("svr_softmax_rows: null pointer");
     if (rows > 0x7fffffff) return fail("svr_softmax_rows: at most 2^31 - 1 rows per call");

@@ -247,9 +247,19 @@ int attn_dispatch(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out, co
                   const int32_t* out_rows, const int32_t* cu, int n_seq, int max_len, int heads, int head_dim,
                   float scale, hipStream_t s, const char** why) {
     *why = nullptr;
-    if (n_seq <= 0 || max_len <= 0) return 0;
+    // Layout contract (include/seedvr2_hip.h): both kernels read q, k and v rows in 16-byte units (LDS-DMA, uint4 / bf16x8 loads at
+    // qkv + row * ld_qkv + 8 j), so neither serves a row pitch or base off 16 bytes; the window kernel stores 16 bytes per lane
+    // (out + row * ld_out + 8 j), the first kernel 8 (out + row * ld_out + 4 j)
+    if (ld_qkv < 3 * (int64_t)heads * head_dim) { *why = "svr_attn_varlen: ld_qkv must cover the 3 * heads * head_dim columns of a qkv row"; return -1; }
+    if (ld_out < (int64_t)heads * head_dim) { *why = "svr_attn_varlen: ld_out must cover the heads * head_dim columns of an out row"; return -1; }
+    if (((uintptr_t)qkv % 16) != 0 || (ld_qkv % 8) != 0) { *why = "svr_attn_varlen: qkv must be 16-byte aligned and ld_qkv a multiple of 8 (rows are read in 16-byte units)"; return -1; }
+    if (((uintptr_t)out % 8) != 0 || (ld_out % 4) != 0) { *why = "svr_attn_varlen: out must be 8-byte aligned and ld_out a multiple of 4 (the first kernel's 8-byte stores; the window kernel takes 16-byte aligned rows only)"; return -1; }
+    if (n_seq <= 0 || max_len <= 0) return 0;            // (an empty call still validates its layout: the checks above)
     if (n_seq > 65535 || heads > 65535) { *why = "svr_attn_varlen: grid too large"; return -1; }
-    if (head_dim == 128 && max_len <= AW_MAXL && (ld_qkv % 8) == 0 && g_attn_impl != 1)
+    if (head_dim != 128 && head_dim != 512) { *why = "svr_attn_varlen: head_dim must be 128 or 512"; return -1; }
+    if (heads <= 0) { *why = "svr_attn_varlen: heads must be positive"; return -1; }
+    const bool out16 = ((uintptr_t)out % 16) == 0 && (ld_out % 8) == 0;
+    if (head_dim == 128 && max_len <= AW_MAXL && out16 && g_attn_impl != 1)
         return launch_attn_win(qkv, ld_qkv, out, ld_out, seq_rows, out_rows, cu, n_seq, max_len, heads, scale, s);
     if (head_dim == 128)
         return launch_attn<128, 2, 64>(qkv, ld_qkv, out, ld_out, seq_rows, out_rows, cu, n_seq, max_len, heads, scale, s);

@@ -980,14 +980,22 @@ static int launch_conv_halo2(const svr_gemm_args& a, hipStream_t s) {
     return launch_conv_halo2_t<16, 0>(a, s);
 }
 
+// what conv_halo2_kernel's epilogue needs of the output side (every instance, the thin-input one included): one thread finishes 8
+// couts of a voxel with 16-byte stores / residual loads at C + m * ldc + n and resid + m * ldr + n, n % 8 == 0 (fp32: two of them,
+// 32-byte rows), and loads its 8 bias values as two float4
+static bool conv_halo2_out_layout(const svr_gemm_args& a) {
+    return (a.ldc % 8) == 0 && ((uintptr_t)a.C % 16) == 0 && (!a.resid || ((a.ldr % 8) == 0 && ((uintptr_t)a.resid % 16) == 0)) &&
+           (!a.bias || ((uintptr_t)a.bias % 16) == 0);
+}
 // thin-input variant: Cin = 4 (RGB padded), 3x3 spatial taps, stride 1, the whole K in one 128-wide image
-static bool conv_thin_eligible(const svr_gemm_args& a) {
+static bool conv_thin_geometry(const svr_gemm_args& a) {
     const svr_conv_geom& g = a.conv;
     return g.enabled && g.Cin == 4 && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 && g.st == 1 &&
            g.ph == 1 && g.pw == 1 && g.Ho == g.H && g.Wo == g.W && g.kt >= 1 && g.kt <= 3 && a.K == 128 &&
            g.To == g.T + g.pt - g.kt + 1 && !a.ps.enabled && a.epilogue != SVR_EPI_SWIGLU && a.epilogue != SVR_EPI_BIAS_GELU &&
-           (a.N % 128) == 0 && (a.ldc % 8) == 0 && (!a.resid || (a.ldr % 8) == 0);
+           (a.N % 128) == 0;
 }
+static bool conv_thin_eligible(const svr_gemm_args& a) { return conv_thin_geometry(a) && conv_halo2_out_layout(a); }
 static int launch_conv_thin(const svr_gemm_args& a, hipStream_t s) { return launch_conv_halo2_t<8, 2>(a, s); }
 
 static int conv_gn_blocks(const svr_gemm_args& a) {
@@ -1011,7 +1019,7 @@ static bool conv_halo_eligible(const svr_gemm_args& a) {
     return g.enabled && g.kh == 3 && g.kw == 3 && g.sh == 1 && g.sw == 1 && g.st == 1 && g.ph == 1 && g.pw == 1 &&
            g.Ho == g.H && g.Wo == g.W && g.Cin % 64 == 0 && g.kt >= 1 && g.kt <= 3 &&
            g.To == g.T + g.pt - g.kt + 1 && !a.ps.enabled && !a.phase.enabled && a.epilogue != SVR_EPI_SWIGLU &&
-           (a.N <= 32 || ((a.N % 128) == 0 && (a.ldc % 8) == 0 && (!a.resid || (a.ldr % 8) == 0))) &&
+           (a.N <= 32 || ((a.N % 128) == 0 && conv_halo2_out_layout(a))) &&
            (int64_t)g.H * g.W * g.Cin * 2 < (int64_t)1 << 32;
 }
 

@@ -69,7 +69,9 @@ __global__ __launch_bounds__(CT_NT) void conv_thinout_kernel(const svr_gemm_args
         akeys |= (uint32_t)(spos ^ ((hx >> 1) & 7)) << (3 * q);
     }
     // weight piece q: row = q * 64 + srow = tap * 32 + cout; element offset of the thread's source chunk inside W for tap-slice 0
+    // (W may be an exact [N, K] tensor: couts N .. 31 take the zero page, like the 4-cout kernel's rows >= N)
     int64_t woff[CT_WPIECES];
+    const bool wreal = (srow & 31) < a.N;                 // row & 31 = srow & 31 for every piece (q * 64 keeps the low five bits)
 #pragma unroll
     for (int q = 0; q < CT_WPIECES; ++q) {
         const int row = q * 64 + srow;
@@ -99,7 +101,7 @@ __global__ __launch_bounds__(CT_NT) void conv_thinout_kernel(const svr_gemm_args
         const bf16_t* wsl = (const bf16_t*)a.W + (int64_t)dt * 9 * g.Cin + c0;
 #pragma unroll
         for (int q = 0; q < CT_WPIECES; ++q)
-            if (q * CT_NT + tid < CT_WCHUNKS) glds16(wsl + woff[q], dst + CT_ABUF + q * 8192);
+            if (q * CT_NT + tid < CT_WCHUNKS) glds16(wreal ? (const void*)(wsl + woff[q]) : g.zeros, dst + CT_ABUF + q * 8192);
     };
 
     // ---- fragment addressing (lane constants): halo pixel (wave + dy, dx + l31), weight row tap * 32 + l31; k-step ks reads

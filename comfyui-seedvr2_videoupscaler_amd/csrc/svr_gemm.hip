@@ -1301,6 +1301,7 @@ static int launch(const svr_gemm_args& a_in, hipStream_t s) {
 static bool conv_halo_eligible(const svr_gemm_args& a);
 static int launch_conv_halo2(const svr_gemm_args& a, hipStream_t s);
 static bool conv_halo2_eligible(const svr_gemm_args& a);
+static bool conv_thin_geometry(const svr_gemm_args& a);
 static bool conv_thin_eligible(const svr_gemm_args& a);
 static int launch_conv_thin(const svr_gemm_args& a, hipStream_t s);
 // thin-output conv kernel (svr_conv_thinout.hip)
@@ -1348,6 +1349,52 @@ static bool gemm_w4_eligible(const svr_gemm_args& a) {
 // per-frame partial blocks of fused GroupNorm statistics for this problem (0: not produced)
 static int conv_gn_blocks(const svr_gemm_args& a);
 
+static inline bool aligned_to(const void* p, unsigned bytes) { return ((uintptr_t)p % bytes) == 0; }
+
+// Layout contract, part 1 (include/seedvr2_hip.h, "Operand layouts"): every pitch covers its extent.  -> message or nullptr.
+static const char* gemm_extent_refusal(const svr_gemm_args& a) {
+    if (!a.conv.enabled && a.lda < a.K) return "svr_gemm_bf16: lda must cover the K columns of a row of A (lda >= K)";
+    if (!a.ps.enabled && !a.phase.enabled && a.ldc < (a.epilogue == SVR_EPI_SWIGLU ? a.N / 2 : a.N))
+        return "svr_gemm_bf16: ldc must cover the columns of a row of C (ldc >= N, N / 2 for SwiGLU)";
+    if (a.resid && a.ldr < a.N) return "svr_gemm_bf16: ldr must cover the N columns of a row of resid (ldr >= N)";
+    return nullptr;
+}
+// what epilogue_store()'s accesses need (the direct epilogue of gemm_kernel in both modes and of the thin-output kernels): a whole
+// quad of columns n .. n + 3, n % 4 == 0, leaves as ONE 8-byte store (16 bytes for fp32) and a bf16 residual quad arrives as one
+// 8-byte load; fp32 / h16 residuals, bias, gate and the columns behind the last whole quad go element by element.  N < 4 has no
+// whole quad.  -> message or nullptr.
+static const char* gemm_epi_direct_refusal(const svr_gemm_args& a) {
+    if (a.epilogue != SVR_EPI_SWIGLU && a.N < 4) return nullptr;
+    if (!aligned_to(a.C, a.out_f32 == SVR_STORE_FP32 ? 16 : 8))
+        return "svr_gemm_bf16: C must be 8-byte aligned (16-byte for fp32 output): the direct epilogue stores whole quads of columns";
+    if (a.phase.enabled ? (a.N % 4) != 0 : (!a.ps.enabled && (a.ldc % 4) != 0))
+        return "svr_gemm_bf16: ldc must be a multiple of 4 (phase scatter: N): the direct epilogue stores whole quads of columns";
+    if (a.resid && a.resid_f32 == SVR_STORE_BF16 && (!aligned_to(a.resid, 8) || (a.ldr % 4) != 0))
+        return "svr_gemm_bf16: a bf16 resid must be 8-byte aligned with ldr a multiple of 4: the direct epilogue loads whole quads of columns";
+    return nullptr;
+}
+// Layout contract, part 2: the operand alignment of the kernel class that serves the launch (the eligibility predicates above have
+// already turned the launches whose OUTPUT side misses a kernel's 16-byte accesses over to a kernel with narrower ones).
+static const char* gemm_layout_refusal(const svr_gemm_args& a, int cls) {
+    const svr_conv_geom& g = a.conv;
+    if (!aligned_to(a.W, 16)) return "svr_gemm_bf16: W must be 16-byte aligned (staged in 16-byte units)";
+    if (g.enabled) {
+        // the thin-input kernel gathers 8-byte voxels (Cin = 4); every other conv kernel stages 16-byte chunks by LDS-DMA
+        const unsigned ab = cls == SVR_KERNEL_CONV_THIN_IN ? 8 : 16;
+        if (!aligned_to(a.A, ab)) return "svr_gemm_bf16(conv): A must be 16-byte aligned (8-byte for the thin Cin = 4 input)";
+        if (!aligned_to(g.halo, ab)) return "svr_gemm_bf16(conv): halo must be 16-byte aligned (8-byte for the thin Cin = 4 input)";
+        if (!aligned_to(g.zeros, 16)) return "svr_gemm_bf16(conv): zeros (the zero page) must be 16-byte aligned";
+        if (!aligned_to(a.W_frag, 16)) return "svr_gemm_bf16(conv): W_frag must be 16-byte aligned";
+        if (!aligned_to(a.gn_partial, 16)) return "svr_gemm_bf16(conv): gn_partial must be 16-byte aligned (fp64 pairs)";
+    } else {
+        // gemm_kernel and the persistent kernel stage A rows in 16-byte units from A + m * lda * 2 + chunk * 16
+        if (!aligned_to(a.A, 16)) return "svr_gemm_bf16: A must be 16-byte aligned (rows are staged in 16-byte units)";
+        if ((a.lda % 8) != 0) return "svr_gemm_bf16: lda must be a multiple of 8 (rows of A are staged in 16-byte units)";
+    }
+    if (cls == SVR_KERNEL_GEMM || cls == SVR_KERNEL_CONV_GENERIC || cls == SVR_KERNEL_CONV_THIN_OUT) return gemm_epi_direct_refusal(a);
+    return nullptr;
+}
+
 // Which kernel serves a problem: ONE decision, used by the launch below and reported through svr_gemm_kernel_class() (bench.py
 // attributes launch times to kernels with it; a second copy of these predicates in Python would drift).
 // -> SVR_KERNEL_* (include/seedvr2_hip.h), or -1 with *why set when the arguments are invalid.
@@ -1362,8 +1409,13 @@ int gemm_route(const svr_gemm_args& a, const char** why) {
         *why = "svr_gemm_bf16: out_f32 / resid_f32 must be SVR_STORE_BF16 / _FP32 / _H16"; return -1;
     }
     if (a.out_f32 == SVR_STORE_H16 && (a.epilogue == SVR_EPI_SWIGLU || a.ps.enabled)) { *why = "svr_gemm_bf16: h16 output with SwiGLU / pixel shuffle"; return -1; }
+    if ((*why = gemm_extent_refusal(a)) != nullptr) return -1;
     if (a.conv.enabled) {
         const svr_conv_geom& g = a.conv;
+        if (conv_thin_geometry(a) && !conv_thin_eligible(a)) {      // (no other kernel takes Cin = 4)
+            *why = "svr_gemm_bf16(conv, thin Cin = 4 input): C, resid and bias must be 16-byte aligned, ldc and ldr multiples of 8 (the LDS-halo kernel's 16-byte accesses; no other kernel serves this geometry)";
+            return -1;
+        }
         if (!conv_thin_eligible(a)) {       // (thin input: Cin = 4, K = taps * 4 zero-padded to 128)
             if (g.Cin % BK != 0) { *why = "svr_gemm_bf16(conv): Cin must be a multiple of 64 (or the thin Cin = 4, 3x3, stride-1 geometry)"; return -1; }
             if (a.K != g.kt * g.kh * g.kw * g.Cin) { *why = "svr_gemm_bf16(conv): K != taps*Cin"; return -1; }
@@ -1389,13 +1441,16 @@ int gemm_route(const svr_gemm_args& a, const char** why) {
         }
     }
     if (a.gn_partial && conv_gn_blocks(a) == 0) { *why = "svr_gemm_bf16: gn_partial set but this launch cannot produce fused GroupNorm statistics"; return -1; }
-    if (conv_thin_eligible(a)) return SVR_KERNEL_CONV_THIN_IN;
-    if (conv_sub_eligible(a)) return SVR_KERNEL_CONV_SUBPIXEL;
-    if ((g_conv_impl == 0 || g_conv_impl == 3) && conv_halo2_eligible(a)) return SVR_KERNEL_CONV_HALO;
-    if (g_conv_impl != 1 && conv_halo_eligible(a) && a.N <= 32) return SVR_KERNEL_CONV_THIN_OUT;
-    if (a.conv.enabled) return SVR_KERNEL_CONV_GENERIC;
-    if (gemm_w4_eligible(a)) return SVR_KERNEL_GEMM_PERSISTENT;
-    return SVR_KERNEL_GEMM;
+    // the kernel a launch prefers takes it only if every vector access it makes on this layout is naturally aligned (the eligibility
+    // predicates); the class that is left must pass too, or the call is refused before any launch
+    const int cls = conv_thin_eligible(a) ? SVR_KERNEL_CONV_THIN_IN
+                  : conv_sub_eligible(a) ? SVR_KERNEL_CONV_SUBPIXEL
+                  : (g_conv_impl == 0 || g_conv_impl == 3) && conv_halo2_eligible(a) ? SVR_KERNEL_CONV_HALO
+                  : g_conv_impl != 1 && conv_halo_eligible(a) && a.N <= 32 ? SVR_KERNEL_CONV_THIN_OUT
+                  : a.conv.enabled ? SVR_KERNEL_CONV_GENERIC
+                  : gemm_w4_eligible(a) ? SVR_KERNEL_GEMM_PERSISTENT : SVR_KERNEL_GEMM;
+    if ((*why = gemm_layout_refusal(a, cls)) != nullptr) return -1;
+    return cls;
 }
 
 int gemm_dispatch(const svr_gemm_args& a, hipStream_t s, const char** why) {

@@ -5,11 +5,47 @@
  * layer; its hot path runs as torch ops below three call sites of the runner
  * (src/core/infer.py:164-184 vae.encode, :249-266 vae.decode, :361-367 dit forward).  Each entry
  * point below replaces the torch op sequence cited next to it.  All pointers are raw DEVICE
- * pointers (tensor.data_ptr()), all tensors are dense row-major, activations bf16 unless noted,
+ * pointers (tensor.data_ptr()), all tensors are row-major (dense, or with the leading dimension the
+ * entry point takes: "Operand layouts" below), activations bf16 unless noted,
  * `stream` is a hipStream_t.  Functions return 0 on success, non-zero on failure
  * (svr_last_error() gives the message).  The library never allocates caller-visible memory.
  *
  * Layouts: DiT activations  [tokens, channels]; VAE activations NDHWC = [T, H, W, C].
+ *
+ * Operand layouts (the contract of every pointer + leading-dimension pair; tests/layout_cases.py is its table, swept on the CPU by
+ * tests/test_layout_cases.py and on the device by tests/test_gpu_layouts.py).  An operand may be a column window of a wider
+ * row-major tensor -- base = tensor + c0, pitch = the tensor's row length, in ELEMENTS -- under two rules:
+ *   1. a pitch covers its extent (lda >= K, ldc >= N, ldr >= N, ld_qkv >= 3 * heads * head_dim, ...): rows never overlap, and the
+ *      columns between the extent and the pitch are neither read nor written;
+ *   2. every vector access of the kernel that serves the call is naturally aligned: 16 bytes where a kernel moves uint4 / float4 /
+ *      LDS-DMA units, 8 bytes where it moves uint2.  With base % B == 0 bytes and (pitch * element size) % B == 0 every row starts
+ *      on a B-byte boundary; the tables below give B per operand as "base bytes / pitch multiple (elements)".
+ * Where the kernel a call prefers would break rule 2, the call is routed to a kernel of the same family whose accesses are aligned
+ * (a different class from svr_gemm_kernel_class(), same results within the same bounds); where there is none the call FAILS
+ * BEFORE ANY LAUNCH (-1, svr_last_error() names the operand; svr_gemm_kernel_class() returns -1).  Dense tensors from an allocator
+ * that aligns to 16 bytes or more meet every rule below whenever the extents themselves do (K % 64, N % 8, ...).
+ *
+ *   svr_gemm_bf16, plain GEMM                  A 16 / lda % 8     W 16 (dense [Npad, K])     W_frag 16
+ *     SVR_KERNEL_GEMM_PERSISTENT, and the      C 16 / ldc % 8     resid 16 / ldr % 8     bias 16     gate 16      (any storage kind)
+ *       row-contiguous epilogue of SVR_KERNEL_GEMM  (N % 8 == 0; a launch that misses any of these takes the next line)
+ *     SVR_KERNEL_GEMM, direct epilogue         C 8 (fp32: 16) / ldc % 4     bf16 resid 8 / ldr % 4     fp32 | h16 resid, bias, gate: element
+ *                                              (N < 4: no whole quad of columns, C / resid element-aligned too)
+ *   svr_gemm_bf16, conv mode                   A 16, halo 16, zeros 16 (thin Cin = 4 input: A 8, halo 8), W 16, W_frag 16, gn_partial 16
+ *     SVR_KERNEL_CONV_HALO / _THIN_IN          C 16 / ldc % 8     resid 16 / ldr % 8     bias 16     gate element
+ *                                              (HALO: a launch that misses these takes SVR_KERNEL_CONV_GENERIC; THIN_IN: refused)
+ *     SVR_KERNEL_CONV_SUBPIXEL                 C 16, ldc == N (phase scatter: dense output)     bias / bias_border 16
+ *                                              (without phase scatter a launch that misses these takes SVR_KERNEL_CONV_GENERIC)
+ *     SVR_KERNEL_CONV_THIN_OUT                 the direct epilogue's line above (ldc == N with a plain bias epilogue and N <= 4: the
+ *                                              dense store path; any other ldc >= N: quad / element stores)
+ *     SVR_KERNEL_CONV_GENERIC                  the two epilogue lines of the plain GEMM; pixel shuffle / phase scatter outputs are
+ *                                              dense (ldc ignored): C 16 and ps.C % 8 for the row-contiguous epilogue, else C 8, ps.C % 4
+ *   svr_attn_varlen                            qkv 16 / ld_qkv % 8 (both kernels read rows in 16-byte units)
+ *                                              out 16 / ld_out % 8: window kernel (head_dim 128);  out 8 / ld_out % 4: first kernel
+ *                                              (head_dim 128 output rows that are only 8-byte aligned are routed to it; head_dim 512)
+ *   svr_softmax_rows                           S 16 / ld_s % 4 (float4)     P 8 / ld_p % 4 (uint2)     ld_s, ld_p >= cols
+ *   svr_rmsnorm_mod                            x 16, y 16 (dense rows, dim % 8 == 0); w / scale / shift element
+ *   svr_unpatchify_euler                       element accesses only: pred, x_t, out 2-byte aligned, any ldp >= 4 * C
+ *   svr_alpha_*                                element accesses only: any ld_px >= 3
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -26,7 +62,12 @@ extern "C" {
  * v9 (round 6): + svr_mfma_calibrate() / svr_mfma_calibrate_workspace_bytes() (measurement aid, not on the data path); a thin-output
  * conv with N <= 4 couts accepts an exact [N, K] weight (the 4-row units take rows >= N from the zero page).  No signature changed.
  * v9, additive: + svr_alpha_workspace_bytes() / svr_alpha_stats() / svr_alpha_edges() / svr_alpha_refine() (edge-guided alpha
- * upscaling).  New symbols only -- nothing that existed changed, so the version number stays 9. */
+ * upscaling).  New symbols only -- nothing that existed changed, so the version number stays 9.
+ * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
+ * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
+ * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
+ * allocator-aligned calls route exactly as before; a thin-output conv's exact [N, K] weight is honoured by the 32-cout kernel too
+ * (couts >= N are staged from the zero page).  No signature changed. */
 #define SVR_ABI_VERSION 9
 
 /* ---- GEMM / implicit-GEMM convolution epilogues ------------------------------------------ */
@@ -98,14 +139,17 @@ typedef struct svr_phase_scatter {
 } svr_phase_scatter;
 
 typedef struct svr_gemm_args {
-    const void* A;  int64_t lda;        /* bf16 [M, K] (ignored rows/K layout when conv.enabled: A = input tensor) */
+    const void* A;  int64_t lda;        /* bf16 [M, K] (ignored rows/K layout when conv.enabled: A = input tensor); lda >= K.
+                                           Alignment of every operand below: "Operand layouts" at the top of this file     */
     const void* W;                      /* bf16 [Npad, K] row-major (nn.Linear layout), K % 64 == 0,
                                            Npad = N rounded up to the tile width (128)                       */
-    void* C;        int64_t ldc;        /* bf16 (or fp32 if out_f32) [M, N(/2 for SWIGLU)]                     */
+    void* C;        int64_t ldc;        /* bf16 (or fp32 if out_f32) [M, N(/2 for SWIGLU)]; ldc >= N (N / 2); ignored
+                                           (dense output) with ps / phase                                      */
     int32_t M, N, K;
     const float* bias;                  /* fp32 [N] or NULL                                                    */
     const float* gate;                  /* fp32 [N] or NULL (=1)            SVR_EPI_RESID_GATE                 */
-    const void* resid; int64_t ldr;     /* bf16 [M, N] or NULL (may alias C) SVR_EPI_RESID_GATE                */
+    const void* resid; int64_t ldr;     /* bf16 [M, N] or NULL (may alias C, then with ldr == ldc) SVR_EPI_RESID_GATE;
+                                           ldr >= N                                                            */
     int32_t epilogue;
     int32_t out_f32;
     svr_conv_geom conv;
@@ -203,7 +247,8 @@ int svr_qknorm_rope(void* qkv, int64_t rows, int32_t heads, const int16_t* pos, 
 /* Variable-length window attention, softmax(q k^T / sqrt(d)) v per window.  attention.py:27-64,
  * mmattn.py:245-264 (gather by window, text rows appended to every window, scatter back).
  * qkv bf16 [*, 3*heads*D] (q|k|v); seq_rows int32 [total] = source row of each window position;
- * out_rows int32 [total] = destination row in `out` (bf16 [*, heads*D]); cu int32 [n_seq+1].       */
+ * out_rows int32 [total] = destination row in `out` (bf16 [*, heads*D]); cu int32 [n_seq+1].
+ * ld_qkv >= 3*heads*D, ld_out >= heads*D; alignment: "Operand layouts" above.                       */
 int svr_attn_varlen(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out,
                     const int32_t* seq_rows, const int32_t* out_rows, const int32_t* cu,
                     int32_t n_seq, int32_t max_len, int32_t heads, int32_t head_dim, float scale,

@@ -153,13 +153,30 @@ def test_engines_pass_hipops_validation_and_reach_every_entry_point(recorded):
     assert "svr_gemm_pack_frag" in names and "svr_conv_pack_frag_taps" in names          # fragment-ordered weight copies are requested
 
 
+def _addr(p):
+    """a recorded pointer argument as an integer (None / NULL: 0).  The engines run on CPU tensors here, whose allocator aligns to 64
+    bytes like the device's aligns to 256: an operand's offset from 16 bytes is what it would be on the device."""
+    return 0 if p is None else int(getattr(p, "value", p) or 0)
+
+
 def test_recorded_calls_satisfy_the_librarys_own_host_rules(recorded):
-    """The rules of csrc/svr_api.hip, applied to what the engines actually pass (scalars only: pointers are opaque here)."""
+    """The rules of csrc/svr_api.hip, applied to what the engines actually pass: scalars, and the operand-layout contract of
+    include/seedvr2_hip.h (base alignment, pitch multiple, pitch >= extent) for the entry points that take a pointer + pitch."""
     calls, _ = recorded
     for name, a in calls:
         if name == "svr_rmsnorm_mod":
             rows, dim, x_f32 = a[2], a[3], a[8]
             assert rows > 0 and dim % 8 == 0 and 0 < dim <= 4096 and x_f32 in (0, 1, 2), a
+            assert _addr(a[0]) % 16 == 0 and _addr(a[1]) % 16 == 0, a                # x, y: 16-byte units
+        elif name == "svr_attn_varlen":
+            ld_qkv, ld_out, heads, D = a[1], a[3], a[9], a[10]
+            assert D in (128, 512) and heads > 0 and ld_qkv >= 3 * heads * D and ld_out >= heads * D, a
+            assert _addr(a[0]) % 16 == 0 and ld_qkv % 8 == 0, a                      # both kernels read rows in 16-byte units
+            assert _addr(a[2]) % 16 == 0 and ld_out % 8 == 0, a                      # the window kernel's 16-byte stores
+        elif name == "svr_softmax_rows":
+            cols, ld_s, ld_p = a[3], a[4], a[5]
+            assert cols % 4 == 0 and ld_s % 4 == 0 and ld_p % 4 == 0 and ld_s >= cols and ld_p >= cols, a
+            assert _addr(a[0]) % 16 == 0 and _addr(a[1]) % 8 == 0, a
         elif name == "svr_groupnorm_apply":
             T, HW, Cc, groups, x_f32 = a[5], a[6], a[7], a[8], a[11]
             assert T > 0 and HW > 0 and Cc % 8 == 0 and Cc <= 512 and groups > 0 and Cc % groups == 0 and x_f32 in (0, 1, 2), a
@@ -180,6 +197,29 @@ def test_recorded_calls_satisfy_the_librarys_own_host_rules(recorded):
             assert a[6] <= a[5], a                                     # c_take <= C
         elif name == "svr_affine_slice":
             assert 0 < a[4] <= a[3], a
+
+
+def test_recorded_gemm_calls_pass_the_librarys_layout_contract(recorded):
+    """Every svr_gemm_bf16 call the engines make, put to the library's own routing function (a pure host function of the recorded
+    struct: no second copy of its rules here): none is refused -- a product call whose pitch did not cover its extent, or whose
+    operands missed the alignment of every kernel that could serve it, would return -1 here -- and the pitches are the dense ones."""
+    hip_lib = sub("hip_lib")
+    try:
+        real = hip_lib.lib()
+    except hip_lib.HipLibraryError as e:
+        pytest.skip(f"libseedvr2_hip.so not built: {e}")
+    calls, _ = recorded
+    gemms = [c[1][0]._obj for c in calls if c[0] == "svr_gemm_bf16"]
+    assert len(gemms) > 100
+    for a in gemms:
+        cls = int(real.svr_gemm_kernel_class(ctypes.byref(a)))
+        assert cls >= 0, (real.svr_last_error().decode(), a.M, a.N, a.K, a.lda, a.ldc, a.ldr)
+        if a.M > 0 and a.N > 0:
+            assert a.conv.enabled or a.lda >= a.K
+            assert a.ps.enabled or a.phase.enabled or a.ldc >= (a.N // 2 if a.epilogue == 3 else a.N)
+            assert not a.resid or a.ldr >= a.N
+            for ptr in (a.A, a.W, a.C, a.resid, a.bias, a.gate, a.W_frag, a.conv.halo, a.conv.zeros):
+                assert _addr(ptr) % 16 == 0, (a.M, a.N, a.K)                         # dense operands at the allocator's alignment
 
 
 def test_hipops_rejects_bad_side_operands():
