@@ -16,6 +16,7 @@
 #include "svr_elementwise.hip"
 #include "svr_calibrate.hip"
 #include "svr_alpha.hip"
+#include "svr_frame_pack.hip"
 
 using namespace svr;
 
@@ -444,5 +445,58 @@ int svr_alpha_refine(const void* rgb, const float* base, float* out, uint8_t* ed
     return check(hipGetLastError(), "svr_alpha_refine");
 }
 #undef SVR_ALPHA_REFUSE
+
+// ---- packed output frames (svr_frame_pack.hip)
+int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t fmt, void* out,
+                    int64_t out_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const char* why = nullptr;
+    if (!frames) why = "frames is a null pointer";
+    else if (!out) why = "out is a null pointer";
+    else if (x_kind != SVR_STORE_BF16 && x_kind != SVR_STORE_FP32) why = "x_kind must be SVR_STORE_BF16 or SVR_STORE_FP32";
+    else if (T < 1 || H < 1 || W < 1) why = "need T >= 1, H >= 1, W >= 1";
+    else if ((int64_t)H * W > ((int64_t)1 << 40) / T) why = "T * H * W must not exceed 2^40 pixels";
+    else if (fmt != SVR_PACK_RGB8 && fmt != SVR_PACK_BGR8 && fmt != SVR_PACK_YUV420P10) why = "fmt must be SVR_PACK_RGB8, SVR_PACK_BGR8 or SVR_PACK_YUV420P10";
+    else if (fmt == SVR_PACK_YUV420P10 ? C != 3 : (C != 3 && C != 4)) why = fmt == SVR_PACK_YUV420P10 ? "C must be 3 for SVR_PACK_YUV420P10" : "C must be 3 or 4";
+    else if ((uintptr_t)frames % (x_kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
+    else if (fmt == SVR_PACK_YUV420P10 && (uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
+    if (why) { snprintf(g_err, sizeof(g_err), "svr_pack_frames: %s", why); return -1; }
+    const int64_t px = (int64_t)T * H * W, h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
+    const int64_t need = fmt == SVR_PACK_YUV420P10 ? 2 * (int64_t)T * ((int64_t)H * W + 2 * h2 * w2) : px * C;
+    if (out_bytes != need) {
+        snprintf(g_err, sizeof(g_err), "svr_pack_frames: out_bytes is %lld, the format needs exactly %lld", (long long)out_bytes, (long long)need);
+        return -1;
+    }
+    const bool aligned = (uintptr_t)frames % 16 == 0 && (uintptr_t)out % 16 == 0;
+    // capped in 64 bits: under the 2^40-pixel limit the block count of the element-wise routes does not fit 32
+    const int64_t cap = (int64_t)device_cu_count() * 8;
+    auto capped = [cap](int64_t work) { return (unsigned)std::min<int64_t>((work + 255) / 256, cap); };
+    const hipStream_t s = (hipStream_t)stream;
+    const bool f32 = x_kind == SVR_STORE_FP32;
+    if (fmt == SVR_PACK_YUV420P10) {
+        unsigned short* o = (unsigned short*)out;
+        if (aligned && W % 16 == 0) {
+            const unsigned grid = capped((int64_t)T * h2 * (W / 16));
+            if (f32) hipLaunchKernelGGL(pack_yuv_vec_kernel<SVR_STORE_FP32>, dim3(grid), dim3(256), 0, s, frames, o, T, H, W);
+            else hipLaunchKernelGGL(pack_yuv_vec_kernel<SVR_STORE_BF16>, dim3(grid), dim3(256), 0, s, frames, o, T, H, W);
+        } else {
+            const unsigned grid = capped((int64_t)T * h2 * w2);
+            if (f32) hipLaunchKernelGGL(pack_yuv_kernel<SVR_STORE_FP32>, dim3(grid), dim3(256), 0, s, frames, o, T, H, W);
+            else hipLaunchKernelGGL(pack_yuv_kernel<SVR_STORE_BF16>, dim3(grid), dim3(256), 0, s, frames, o, T, H, W);
+        }
+        return check(hipGetLastError(), "svr_pack_frames");
+    }
+    const int64_t n = px * C;
+    const int swap = fmt == SVR_PACK_BGR8 ? C : 0;                 // pack8_kernel's C: 0 = samples in place
+    const int unit = swap == 3 ? 48 : 16;
+    const int64_t n_units = aligned ? n / unit : 0;
+    const unsigned grid = capped(std::max<int64_t>(n_units, n - n_units * unit));
+    unsigned char* o = (unsigned char*)out;
+#define SVR_PACK8(KIND, CH) hipLaunchKernelGGL((pack8_kernel<KIND, CH>), dim3(grid), dim3(256), 0, s, frames, o, n_units, n)
+    if (f32) { if (swap == 0) SVR_PACK8(SVR_STORE_FP32, 0); else if (swap == 3) SVR_PACK8(SVR_STORE_FP32, 3); else SVR_PACK8(SVR_STORE_FP32, 4); }
+    else { if (swap == 0) SVR_PACK8(SVR_STORE_BF16, 0); else if (swap == 3) SVR_PACK8(SVR_STORE_BF16, 3); else SVR_PACK8(SVR_STORE_BF16, 4); }
+#undef SVR_PACK8
+    return check(hipGetLastError(), "svr_pack_frames");
+}
 
 }  // extern "C"

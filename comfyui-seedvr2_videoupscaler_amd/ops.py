@@ -536,3 +536,30 @@ class HipOps:
         hip_lib.check(self.lib.svr_alpha_refine(rgb_p, _ptr(base), _ptr(out), self._opt(edge_out, torch.uint8, "edge_out"), T, H, W, ld,
                                                 kind, n_alpha, ws_p, nbytes, self._stream()), "svr_alpha_refine")
         return out
+
+    # ------------------------------------------------------------------ packed output frames
+    def pack_frames(self, frames, fmt, out=None):
+        """Output frames narrowed on the device (frameio.py is the specification; csrc/svr_frame_pack.hip): frames [T, H, W, 3 | 4]
+        fp32 / bf16, dense -> uint8 [T, H, W, C] ("rgb8", "bgr8") or uint16 [T, H*W + 2*h2*w2] ("yuv420p10", C = 3).  One launch on
+        the current stream, no host synchronisation.  ``out``: a dense tensor of exactly that shape and dtype."""
+        from . import frameio
+        if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
+            raise ValueError(f"pack_frames: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
+        T, H, W, Cn = frames.shape
+        try:
+            shape = frameio.packed_shape(T, H, W, Cn, fmt)
+        except ValueError as e:
+            raise ValueError(f"pack_frames: {e}") from None
+        if T < 1 or H < 1 or W < 1:
+            raise ValueError(f"pack_frames: frames must hold at least one pixel, got {tuple(frames.shape)}")
+        self._chk(frames, None, "pack_frames: frames")
+        dtype = frameio.packed_dtype(fmt)
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        self._chk(out, dtype, "pack_frames: out")
+        if tuple(out.shape) != tuple(shape):
+            raise ValueError(f"pack_frames: out must be {tuple(shape)} for {fmt}, got {tuple(out.shape)}")
+        kind = 1 if frames.dtype == torch.float32 else 0                     # SVR_STORE_FP32 / SVR_STORE_BF16
+        hip_lib.check(self.lib.svr_pack_frames(_ptr(frames), kind, T, H, W, Cn, hip_lib.PACK_FORMATS[fmt], _ptr(out),
+                                               out.numel() * out.element_size(), self._stream()), "svr_pack_frames")
+        return out

@@ -248,3 +248,34 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
         final = final[prepend_frames:]
         spans = {i: (max(a - prepend_frames, 0), max(b - prepend_frames, 0)) for i, (a, b) in spans.items()}
     return (final, spans) if return_spans else final
+
+
+def upscale_stream(chunks, runner, text_pos: torch.Tensor, *, temporal_overlap: int = 0, prepend_frames: int = 0, **upscale_kwargs):
+    """A clip too long to hold, as a stream: ``chunks`` is any iterable of [t, H, W, 3 | 4] tensors (consecutive pieces of one
+    clip), the generator yields one upscaled [t, H', W', C] tensor per chunk.  The reference's ``_stream_video_chunks``
+    (inference_cli.py:621-718): chunk k > 0 is upscaled with the last min(temporal_overlap, t_prev) RAW input frames of chunk k - 1
+    prepended as temporal context, whose output frames are dropped; ``prepend_frames`` applies to the first chunk only; everything
+    else goes to ``upscale`` unchanged (``temporal_overlap`` also as the batch overlap inside a chunk).  So the stream equals, bit
+    for bit, ``upscale`` called on each (context + chunk) with the context trimmed -- and NOT the one-call result of the whole clip
+    wherever a batch boundary falls differently.
+
+    Memory: nothing of chunk k stays referenced here once chunk k + 1 is yielded except its raw input tail (``temporal_overlap``
+    input frames), so device memory is bounded by one chunk whatever the clip's length -- provided the caller drops (or packs,
+    frameio.pack_frames) each yielded tensor before asking for the next."""
+    tail = None
+    for k, chunk in enumerate(chunks):
+        if chunk.dim() != 4 or chunk.shape[0] == 0:
+            raise ValueError(f"chunk {k} must be [t, H, W, 3 | 4] with t >= 1, got {tuple(chunk.shape)}")
+        context = 0
+        frames = chunk
+        if tail is not None and temporal_overlap > 0:
+            context = min(temporal_overlap, tail.shape[0])
+            frames = torch.cat([tail[-context:].to(chunk.device), chunk], dim=0)
+        out = upscale(frames, runner, text_pos, temporal_overlap=temporal_overlap,
+                      prepend_frames=prepend_frames if k == 0 else 0, **upscale_kwargs)
+        tail = chunk[-temporal_overlap:].clone() if temporal_overlap > 0 else None
+        del frames, chunk
+        if context > 0:
+            out = out[context:]
+        yield out
+        del out

@@ -46,6 +46,9 @@
  *   svr_rmsnorm_mod                            x 16, y 16 (dense rows, dim % 8 == 0); w / scale / shift element
  *   svr_unpatchify_euler                       element accesses only: pred, x_t, out 2-byte aligned, any ldp >= 4 * C
  *   svr_alpha_*                                element accesses only: any ld_px >= 3
+ *   svr_pack_frames                            element alignment is enough (frames 4 / 2 bytes for fp32 / bf16, out 2 bytes for
+ *                                              yuv420p10); 16-byte loads and stores where frames and out are 16-byte aligned (and,
+ *                                              for yuv420p10, W % 16 == 0), element accesses otherwise
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -63,6 +66,7 @@ extern "C" {
  * conv with N <= 4 couts accepts an exact [N, K] weight (the 4-row units take rows >= N from the zero page).  No signature changed.
  * v9, additive: + svr_alpha_workspace_bytes() / svr_alpha_stats() / svr_alpha_edges() / svr_alpha_refine() (edge-guided alpha
  * upscaling).  New symbols only -- nothing that existed changed, so the version number stays 9.
+ * v9, additive: + svr_pack_frames() (output frames narrowed to rgb8 / bgr8 / yuv420p10 on the device).  A new symbol only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -335,6 +339,23 @@ int svr_alpha_edges(const void* rgb, int32_t T, int32_t H, int32_t W, int64_t ld
  * trunc(sqrt(n) / sqrt(max n) * 255) (fp64; 0 on a constant frame) goes to edge_out [T, H, W] uint8 unless that is NULL. */
 int svr_alpha_refine(const void* rgb, const float* base, float* out, uint8_t* edge_out, int32_t T, int32_t H, int32_t W,
                      int64_t ld_px, int32_t rgb_kind, int64_t n_alpha, const void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- packed output frames ------------------------------------------------------------------- */
+/* frameio.py (the specification, bit for bit): frames [T, H, W, C] dense, fp32 or bf16 (x_kind SVR_STORE_FP32 / SVR_STORE_BF16),
+ * nominally in [0, 1], C = 3 or 4 -> out:
+ *   SVR_PACK_RGB8 / SVR_PACK_BGR8   uint8 [T, H, W, C]: rint(clamp(x, 0, 1) * 255) (ties to even); BGR8 swaps channels 0 and 2, a
+ *                                   fourth channel stays in place.  out_bytes = T*H*W*C.
+ *   SVR_PACK_YUV420P10              C = 3 only.  uint16 [T, H*W + 2*h2*w2], h2 = ceil(H/2), w2 = ceil(W/2): per frame the Y plane,
+ *                                   then Cb, then Cr (ffmpeg's yuv420p10le), BT.709 limited range in exact integers from
+ *                                   q = rint(clamp(x, 0, 1) * 65535); chroma from the sums over 2 x 2 blocks, rows / columns beyond
+ *                                   the frame repeating the last one.  out_bytes = 2 * T * (H*W + 2*h2*w2).
+ * NaN -> code 0, +inf -> full scale, -inf -> 0.  Every argument is checked before the launch (T * H * W <= 2^40 pixels); out_bytes
+ * must be EXACTLY the size above.  One launch on `stream`, no host synchronisation, no workspace. */
+#define SVR_PACK_RGB8      0
+#define SVR_PACK_BGR8      1
+#define SVR_PACK_YUV420P10 2
+int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t fmt, void* out,
+                    int64_t out_bytes, void* stream);
 
 /* ---- misc ------------------------------------------------------------------------------------ */
 /* Tuning / measurement knobs (no effect on results):

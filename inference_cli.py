@@ -9,17 +9,25 @@ two parsers by ``ast``), so existing scripts keep working.  What the flags DO is
   * frames -> ``pipeline.upscale`` (one GPU) or ``dist.upscale_sharded`` (--cuda_device a,b,...: one process per GPU over
     RCCL, temporal batches dealt round-robin; replaces the reference's mp.Process + mp.Queue workers,
     inference_cli.py:1127-1288);
-  * flags that select a small-VRAM policy (--blocks_to_swap, --swap_io_components, --*_offload_device, --cache_dit/_vae,
-    --chunk_size), another attention backend or torch.compile are accepted and have no effect: one attention kernel, no
-    tracing compiler, 288 GB of HBM (DESIGN.md section 8);
-  * media I/O is plumbing, not the hot path: images through PIL, tensors as .pt / .npy, video through OpenCV when it is
-    installed (the reference's own dependency).
+  * flags that select a small-VRAM policy (--blocks_to_swap, --swap_io_components, --*_offload_device, --cache_dit/_vae),
+    another attention backend or torch.compile are accepted and have no effect: one attention kernel, no tracing compiler,
+    288 GB of HBM (DESIGN.md section 8);
+  * --chunk_size N streams a long clip: the input is read N frames at a time, each chunk goes through
+    ``pipeline.upscale_stream`` (the previous chunk's last --temporal_overlap raw frames as context), its result is narrowed
+    on the device (frameio.py / csrc/svr_frame_pack.hip) and handed to ONE writer thread through two pinned host buffers,
+    so the encoder works while the next chunk computes and neither device nor host memory grows with the clip;
+  * media I/O is plumbing, not the hot path: images through PIL, tensors as .pt / .npy, video in through OpenCV when it is
+    installed (the reference's own dependency), video out through OpenCV or (--video_backend ffmpeg, with --10bit a real
+    10-bit BT.709 plane) an ffmpeg subprocess fed through stdin.
 """
 import argparse
 import os
 import platform
+import queue
+import shutil
 import subprocess
 import sys
+import threading
 import time
 from typing import List, Optional
 
@@ -60,7 +68,7 @@ def build_parser() -> argparse.ArgumentParser:
     g.add_argument("--seed", type=int, default=42, help="Random seed for reproducibility (default: 42)")
     g.add_argument("--skip_first_frames", type=int, default=0, help="Skip N initial frames (default: 0)")
     g.add_argument("--load_cap", type=int, default=0, help="Load maximum N frames from video. 0 = load all (default: 0)")
-    g.add_argument("--chunk_size", type=int, default=0, help="Frames per chunk for streaming mode (accepted; clips stay resident in HBM)")
+    g.add_argument("--chunk_size", type=int, default=0, help="Frames per chunk for streaming mode: read, upscale, pack and write N frames at a time. 0 = whole clip resident in HBM (default: 0)")
     g.add_argument("--prepend_frames", type=int, default=0, help="Prepend N reversed frames to reduce start artifacts (auto-removed). Default: 0")
     g.add_argument("--temporal_overlap", type=int, default=0, help="Frames to overlap between batches/GPUs for smooth blending (default: 0)")
     g = parser.add_argument_group("Quality control")
@@ -150,32 +158,297 @@ def load_frames(path: str, skip: int = 0, cap: int = 0):
     return frames[..., :4 if frames.shape[-1] == 4 else 3].contiguous(), fps
 
 
-def save_frames(frames, path: str, fmt: str, fps: float = 30.0):
-    """pt: the tensor as it is; png: RGB or, for four-channel frames, RGBA files; mp4 has no alpha: it is dropped with a warning."""
+def _keep_channels(frames):
+    return frames[..., :4 if frames.shape[-1] == 4 else 3]
+
+
+def open_chunks(path: str, chunk_size: int, skip: int = 0, cap: int = 0):
+    """-> (generator of [t <= chunk_size, H, W, 3 | 4] float32 tensors in [0, 1], fps): the input read ``chunk_size`` frames at a
+    time -- a video through cv2.VideoCapture, a .npy memory-mapped, a .pt loaded and sliced.  ``skip`` / ``cap`` as load_frames."""
     import numpy as np
     import torch
-    arr = (frames.float().clamp(0, 1) * 255.0).round().to(torch.uint8).cpu().numpy()
-    if fmt == "pt":
-        torch.save(frames.cpu(), path)
-    elif fmt == "png":
-        from PIL import Image
-        if arr.shape[0] == 1 and path.lower().endswith(".png"):
-            os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-            Image.fromarray(arr[0]).save(path)
-        else:
-            os.makedirs(path, exist_ok=True)
-            for i, a in enumerate(arr):
-                Image.fromarray(a).save(os.path.join(path, f"frame_{i:06d}.png"))
-    else:
+    ext = os.path.splitext(path)[1].lower()
+    if chunk_size <= 0:
+        raise ValueError("chunk_size must be positive")
+    if ext in TENSOR_EXT:
+        src = torch.load(path, weights_only=True) if ext == ".pt" else np.load(path, mmap_mode="r")
+        if src.ndim == 3:
+            src = src[None]
+        stop = src.shape[0] if cap <= 0 else min(src.shape[0], skip + cap)
+        if stop - skip <= 0:
+            raise ValueError("No frames to process")
+
+        def tensor_chunks():
+            for i in range(skip, stop, chunk_size):
+                part = src[i:min(i + chunk_size, stop)]
+                part = part if ext == ".pt" else torch.from_numpy(np.array(part))          # (np.array: out of the mapping)
+                yield _keep_channels(part.float()).contiguous()
+        return tensor_chunks(), 30.0
+    if ext not in VIDEO_EXT:
+        raise ValueError(f"cannot stream {path}: a video or a .pt / .npy tensor is read in chunks (an image is one frame)")
+    try:
         import cv2  # type: ignore
-        if arr.shape[-1] == 4:
-            print(f"Warning: {fmt} output has no alpha channel; writing RGB only (use --output_format png to keep it)", file=sys.stderr)
-            arr = arr[..., :3]
-        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-        w = cv2.VideoWriter(path, cv2.VideoWriter_fourcc(*"mp4v"), fps, (arr.shape[2], arr.shape[1]))
+    except ImportError as e:
+        raise RuntimeError("reading video files needs OpenCV (the reference's own dependency); pass an image folder or a .pt tensor") from e
+    cap_ = cv2.VideoCapture(path)
+    fps = cap_.get(cv2.CAP_PROP_FPS) or 30.0
+
+    def video_chunks():
+        try:
+            for _ in range(skip):
+                if not cap_.grab():
+                    break
+            left, first = (cap if cap > 0 else None), True
+            while left is None or left > 0:
+                out, want = [], chunk_size if left is None else min(chunk_size, left)
+                while len(out) < want:
+                    ok, f = cap_.read()
+                    if not ok:
+                        break
+                    out.append(torch.from_numpy(cv2.cvtColor(f, cv2.COLOR_BGR2RGB)).float() / 255.0)
+                if not out:
+                    if first:
+                        raise ValueError("No frames to process")
+                    return
+                first = False
+                if left is not None:
+                    left -= len(out)
+                short = len(out) < want
+                yield torch.stack(out)
+                if short:
+                    return
+        finally:
+            cap_.release()
+    return video_chunks(), fps
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Writers: host code only (no GPU call), fed packed frames (frameio.py) as numpy arrays by FrameSink's thread.  ``fmt`` names the
+# packed format a writer takes (None: the fp32 frames themselves), ``alpha`` whether it keeps a fourth channel.
+class PngWriter:
+    """rgb8 (RGBA for four channels): one file per frame, frame_%06d.png, the index continuing across chunks; ``single``: the one
+    frame of an image job goes to ``path`` itself."""
+    fmt, alpha = "rgb8", True
+
+    def __init__(self, path: str, single: bool = False):
+        self.path, self.single, self.index = path, single, 0
+
+    def write(self, arr, height, width):
+        from PIL import Image
+        if self.single:
+            os.makedirs(os.path.dirname(os.path.abspath(self.path)), exist_ok=True)
+        else:
+            os.makedirs(self.path, exist_ok=True)
         for a in arr:
-            w.write(np.ascontiguousarray(a[..., ::-1]))
-        w.release()
+            Image.fromarray(a).save(self.path if self.single else os.path.join(self.path, f"frame_{self.index:06d}.png"))
+            self.index += 1
+
+    def close(self):
+        pass
+
+
+class OpenCVWriter:
+    """bgr8 into cv2.VideoWriter (mp4v), which stays open across chunks."""
+    fmt, alpha = "bgr8", False
+
+    def __init__(self, path: str, fps: float):
+        self.path, self.fps, self.writer = path, fps, None
+
+    def write(self, arr, height, width):
+        import cv2  # type: ignore
+        if self.writer is None:
+            os.makedirs(os.path.dirname(os.path.abspath(self.path)), exist_ok=True)
+            self.writer = cv2.VideoWriter(self.path, cv2.VideoWriter_fourcc(*"mp4v"), self.fps, (width, height))
+        for a in arr:
+            self.writer.write(a)
+
+    def close(self):
+        if self.writer is not None:
+            self.writer.release()
+            self.writer = None
+
+
+def find_ffmpeg() -> str:
+    exe = shutil.which("ffmpeg")
+    if exe is None:
+        raise RuntimeError("--video_backend ffmpeg needs the ffmpeg executable on PATH and there is none "
+                           "(install ffmpeg, or use --video_backend opencv)")
+    return exe
+
+
+class FFmpegWriter:
+    """An ffmpeg subprocess fed raw frames through stdin: bgr24 -> libx264 / yuv420p, or (``ten_bit``) yuv420p10le -> libx265 /
+    yuv420p10le -- the planes frameio.py computes from the fp32 frames, not 8-bit frames widened.  The stream is tagged BT.709,
+    tv range.  ``exe``: the executable (find_ffmpeg(), resolved before any GPU work; a test passes its own)."""
+    alpha = False
+
+    def __init__(self, exe: str, path: str, fps: float, ten_bit: bool = False):
+        self.exe, self.path, self.fps, self.ten_bit = exe, path, fps, ten_bit
+        self.fmt = "yuv420p10" if ten_bit else "bgr8"
+        self.proc, self.errlog = None, None
+
+    def command(self, height, width):
+        raw, codec, pix = ("yuv420p10le", "libx265", "yuv420p10le") if self.ten_bit else ("bgr24", "libx264", "yuv420p")
+        tags = ["-colorspace", "bt709", "-color_primaries", "bt709", "-color_trc", "bt709", "-color_range", "tv"]
+        # 8 bits: ffmpeg converts bgr24 itself, and its default RGB -> YUV matrix is BT.601 whatever the output is tagged with:
+        # the scale filter is told the matrix and range the tags then state
+        convert = [] if self.ten_bit else ["-vf", "scale=out_color_matrix=bt709:out_range=tv"]
+        return ([self.exe, "-y", "-loglevel", "error", "-f", "rawvideo", "-pix_fmt", raw, "-s", f"{width}x{height}", "-r", f"{self.fps:g}"]
+                + (tags if self.ten_bit else []) + ["-i", "-"] + convert
+                + ["-c:v", codec, "-pix_fmt", pix, "-preset", "medium", "-crf", "12"] + tags + [self.path])
+
+    def write(self, arr, height, width):
+        if self.proc is None:
+            import tempfile
+            os.makedirs(os.path.dirname(os.path.abspath(self.path)), exist_ok=True)
+            self.errlog = tempfile.TemporaryFile()              # (a file, not a pipe: nobody drains stderr while frames flow)
+            self.proc = subprocess.Popen(self.command(height, width), stdin=subprocess.PIPE, stdout=subprocess.DEVNULL, stderr=self.errlog)
+        try:
+            self.proc.stdin.write(memoryview(arr).cast("B"))
+        except (BrokenPipeError, OSError):
+            self._finish()                                       # ffmpeg went away: report ITS message
+            raise
+
+    def _finish(self):
+        proc, self.proc = self.proc, None
+        if proc is None:
+            return
+        try:
+            proc.stdin.close()
+        except OSError:
+            pass
+        rc = proc.wait()
+        self.errlog.seek(0)
+        tail = self.errlog.read()[-2000:].decode(errors="replace")
+        self.errlog.close()
+        if rc != 0:
+            raise RuntimeError(f"ffmpeg exited with status {rc}: {tail.strip()}")
+
+    def close(self):
+        self._finish()
+
+
+class TensorWriter:
+    """.pt output: the fp32 chunks collected on the host, saved once at close (streaming bounds DEVICE memory only here)."""
+    fmt, alpha = None, True
+
+    def __init__(self, path: str):
+        self.path, self.parts = path, []
+
+    def write(self, frames, height, width):
+        self.parts.append(frames)
+
+    def close(self):
+        import torch
+        if self.parts:
+            os.makedirs(os.path.dirname(os.path.abspath(self.path)), exist_ok=True)
+            torch.save(self.parts[0] if len(self.parts) == 1 else torch.cat(self.parts), self.path)
+            self.parts = []
+
+
+class FrameSink:
+    """Frames -> writer.  ``put(frames)`` narrows a chunk to the writer's format where the frames live (``ops.pack_frames`` on the
+    device, ``ops`` being the resident runner's backend; frameio's torch statement for a backend without one and for host frames),
+    copies the result into one of TWO host buffers (pinned for device frames) and hands it to ONE writer thread through a queue of depth 2, so the encoder works while the next chunk computes.  The thread makes no GPU
+    call.  An exception of the writer is raised in the caller's thread at the next put() or at close()."""
+
+    def __init__(self, writer, ops=None):
+        self.writer, self.ops = writer, ops
+        self.frames = 0
+        self.error = None
+        self.work = queue.Queue(maxsize=2)
+        self.free = queue.Queue()
+        self.buffers = [None, None]
+        for slot in range(2):
+            self.free.put(slot)
+        self.warned_alpha = False
+        self.thread = threading.Thread(target=self._drain, name="frame-writer", daemon=True)
+        self.thread.start()
+
+    def _drain(self):
+        while True:
+            item = self.work.get()
+            if item is None:
+                return
+            slot, arr, height, width = item
+            try:
+                if self.error is None:                           # (after a failure: keep returning buffers, write nothing)
+                    self.writer.write(arr, height, width)
+            except BaseException as e:                           # noqa: BLE001 (handed to the caller's thread)
+                self.error = e
+            finally:
+                del arr, item
+                if slot is not None:
+                    self.free.put(slot)
+
+    def _raise_pending(self):
+        if self.error is not None:
+            raise RuntimeError(f"writing frames failed: {type(self.error).__name__}: {self.error}") from self.error
+
+    def put(self, frames):
+        import importlib
+        import torch
+        frameio = importlib.import_module(f"{PKG}.frameio")
+        self._raise_pending()
+        if frames.shape[-1] == 4 and not self.writer.alpha:
+            if not self.warned_alpha:
+                print("Warning: this output has no alpha channel; writing RGB only (use --output_format png to keep it)", file=sys.stderr)
+                self.warned_alpha = True
+            frames = frames[..., :3]
+        height, width = frames.shape[1], frames.shape[2]
+        self.frames += frames.shape[0]
+        if self.writer.fmt is None:
+            self.work.put((None, frames.cpu(), height, width))
+            return
+        if frames.dtype not in (torch.float32, torch.bfloat16):
+            frames = frames.float()
+        if frames.is_cuda and self.ops is None:
+            raise ValueError("FrameSink: frames on a GPU need the backend that narrows them there (ops=runner.dit.ops)")
+        packed = frameio.pack_frames(frames.contiguous(), self.writer.fmt, self.ops if frames.is_cuda else None)
+        nbytes = packed.numel() * packed.element_size()
+        slot = self.free.get()                                   # waits until the writer is done with one of the two buffers
+        self._raise_pending()
+        if self.buffers[slot] is None or self.buffers[slot].numel() < nbytes:
+            self.buffers[slot] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=packed.is_cuda)
+        host = self.buffers[slot][:nbytes].view(packed.dtype).view(packed.shape)
+        host.copy_(packed)                                       # (device -> pinned host: returns when the bytes are there)
+        self.work.put((slot, host.numpy(), height, width))
+
+    def close(self, quiet: bool = False):
+        """Let the writer finish what it was handed, close it, raise what it raised (``quiet``: on the way out of another error)."""
+        self.work.put(None)
+        self.thread.join()
+        try:
+            self.writer.close()
+        except BaseException as e:                               # noqa: BLE001
+            if self.error is None:
+                self.error = e
+        if not quiet:
+            self._raise_pending()
+
+
+def open_writer(fmt: str, path: str, fps: float, single: bool = False, video_backend: str = "opencv", ten_bit: bool = False,
+                ffmpeg: Optional[str] = None):
+    if fmt == "pt":
+        return TensorWriter(path)
+    if fmt == "png":
+        return PngWriter(path, single)
+    if video_backend == "ffmpeg":
+        return FFmpegWriter(ffmpeg or find_ffmpeg(), path, fps, ten_bit)
+    return OpenCVWriter(path, fps)
+
+
+def save_frames(frames, path: str, fmt: str, fps: float = 30.0, ops=None, **writer_kw):
+    """pt: the tensor as it is; png: RGB or, for four-channel frames, RGBA files; mp4 has no alpha: it is dropped with a warning.
+    One hand-over to the writer the streaming path uses chunk by chunk."""
+    single = fmt == "png" and frames.shape[0] == 1 and path.lower().endswith(".png")
+    sink = FrameSink(open_writer(fmt, path, fps, single, **writer_kw), ops)
+    try:
+        sink.put(frames)
+    except BaseException:
+        sink.close(quiet=True)
+        raise
+    sink.close()
 
 
 def list_inputs(path: str) -> List[str]:
@@ -205,13 +478,11 @@ def default_output(inp: str, fmt: str) -> str:
     return os.path.join("output", f"{stem}_upscaled" + ("" if fmt == "png_dir" else f".{fmt}"))
 
 
-def run(args, frames):
-    """One rank's work: engines resident on cuda:LOCAL_RANK, single-GPU or sharded pipeline; returns the full clip."""
+def engines(args):
+    """-> (runner, text embedding, pipeline keyword arguments, rank, world): the engines resident on cuda:LOCAL_RANK."""
     import importlib
-    import torch
     itf = _itf()
     dist_mod = importlib.import_module(f"{PKG}.dist")
-    pipeline = importlib.import_module(f"{PKG}.pipeline")
     rank, world, local = dist_mod.init_from_env()
     device = f"cuda:{local}"
     vae_cfg = dict(model=itf.DEFAULT_VAE, device=device, encode_tiled=args.vae_encode_tiled,
@@ -224,16 +495,66 @@ def run(args, frames):
               uniform_batch_size=args.uniform_batch_size, temporal_overlap=args.temporal_overlap,
               prepend_frames=args.prepend_frames, color_correction=args.color_correction,
               input_noise_scale=args.input_noise_scale, latent_noise_scale=args.latent_noise_scale, seed=args.seed)
+    return runner, text, kw, rank, world
+
+
+def _sync(runner):
+    import torch
+    if runner.dit.device.type == "cuda":
+        torch.cuda.synchronize()
+
+
+def run(args, frames, eng=None, **override):
+    """One rank's work: engines resident on cuda:LOCAL_RANK, single-GPU or sharded pipeline; returns (the full clip, rank) -- with
+    several GPUs the clip on rank 0 and None on every other rank.  ``eng``: engines(args) where the caller already has it;
+    ``override``: pipeline keyword arguments that differ from the flags (run_stream: prepend_frames after the first chunk)."""
+    import importlib
+    dist_mod = importlib.import_module(f"{PKG}.dist")
+    pipeline = importlib.import_module(f"{PKG}.pipeline")
+    runner, text, kw, rank, world = eng if eng is not None else engines(args)
+    kw = {**kw, **override}
     t0 = time.time()
     if world > 1:                                      # only rank 0 writes the result: gather the frames there, not everywhere
         out = dist_mod.upscale_sharded(frames.to(runner.dit.device), runner, text, gather="root", **kw)
     else:
         out = pipeline.upscale(frames.to(runner.dit.device), runner, text, **kw)
-    torch.cuda.synchronize()
+    _sync(runner)
     if rank == 0:
         dt = time.time() - t0
         print(f"Upscaled {out.shape[0]} frames to {out.shape[2]}x{out.shape[1]} in {dt:.2f}s ({out.shape[0] / dt:.2f} FPS, {world} GPU(s))")
     return out, rank
+
+
+def run_stream(args, chunks, eng=None):
+    """--chunk_size: a generator of upscaled chunks.  One GPU: pipeline.upscale_stream.  Several: every rank reads the same chunks
+    and each (context + chunk) goes through run() -- batches sharded over the ranks, frames gathered on rank 0 -- with the same
+    context rule (the previous chunk's last --temporal_overlap raw frames prepended, their output dropped, --prepend_frames on
+    the first chunk only).  Rank 0 is yielded the chunks; every other rank is yielded None per chunk (it has nothing to write, but
+    takes part in every chunk's collectives to the end of the clip)."""
+    import importlib
+    import torch
+    pipeline = importlib.import_module(f"{PKG}.pipeline")
+    eng = eng if eng is not None else engines(args)
+    runner, text, kw, rank, world = eng
+    if world == 1:
+        yield from pipeline.upscale_stream((c.to(runner.dit.device) for c in chunks), runner, text, **kw)
+        return
+    tail, overlap = None, args.temporal_overlap
+    for k, chunk in enumerate(chunks):
+        context = min(overlap, tail.shape[0]) if (tail is not None and overlap > 0) else 0
+        frames = torch.cat([tail[-context:], chunk]) if context else chunk
+        out, _ = run(args, frames, eng, prepend_frames=args.prepend_frames if k == 0 else 0)
+        tail = chunk[-overlap:].clone() if overlap > 0 else None
+        del frames, chunk
+        yield None if out is None else out[context:]             # (gather="root": only rank 0 holds the frames)
+        del out
+
+
+def output_path(args, inp: str, fmt: str, n_jobs: int, single: bool) -> str:
+    path = default_output(inp, fmt if not (fmt == "png" and not single) else "png_dir")
+    if args.output:                                    # one job: the path as given; a folder of jobs: a directory to fill
+        path = args.output if n_jobs == 1 else os.path.join(args.output, os.path.basename(path))
+    return path
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -251,16 +572,46 @@ def main(argv: Optional[List[str]] = None) -> int:
     if len(devices) == 1 and "WORLD_SIZE" not in os.environ and devices[0] != "0":
         os.environ.setdefault("HIP_VISIBLE_DEVICES", devices[0])
     jobs = list_inputs(args.input)
+    ext_of = lambda inp: os.path.splitext(inp)[1].lower()
+    fmt_of = lambda inp: args.output_format or ("mp4" if ext_of(inp) in VIDEO_EXT else "pt" if ext_of(inp) in TENSOR_EXT else "png")
+    # the encoder is looked for ONCE, before any GPU work: a missing executable must not cost a model load or a clip
+    ffmpeg = None
+    if args.video_backend == "ffmpeg" and any(fmt_of(inp) == "mp4" for inp in jobs):
+        ffmpeg = find_ffmpeg()
+    if args.use_10bit and args.video_backend != "ffmpeg":
+        print("Warning: --10bit needs --video_backend ffmpeg; writing 8-bit video", file=sys.stderr)
+    writer_kw = dict(video_backend=args.video_backend, ten_bit=args.use_10bit and args.video_backend == "ffmpeg", ffmpeg=ffmpeg)
     for inp in jobs:                                   # the engines stay resident between jobs (interfaces.get_runner)
+        fmt = fmt_of(inp)
+        eng = engines(args)
+        rank, ops = eng[3], getattr(eng[0].dit, "ops", None)    # (the runner's backend also narrows the frames for the writers)
+        if args.chunk_size > 0 and ext_of(inp) not in IMAGE_EXT:
+            # streaming: read, upscale, pack and write --chunk_size frames at a time
+            chunks, fps = open_chunks(inp, args.chunk_size, args.skip_first_frames, args.load_cap)
+            path = output_path(args, inp, fmt, len(jobs), single=False)
+            sink, t0 = None, time.time()
+            try:
+                for out in run_stream(args, chunks, eng):
+                    if rank == 0:
+                        if sink is None:
+                            sink = FrameSink(open_writer(fmt, path, fps, False, **writer_kw), ops)
+                        sink.put(out)
+                    del out
+            except BaseException:
+                if sink is not None:
+                    sink.close(quiet=True)
+                raise
+            if sink is not None:
+                sink.close()
+                dt = time.time() - t0
+                print(f"Streamed {sink.frames} frames in chunks of {args.chunk_size} in {dt:.2f}s ({sink.frames / dt:.2f} FPS)")
+                print(f"Saved: {path}")
+            continue
         frames, fps = load_frames(inp, args.skip_first_frames, args.load_cap)
-        out, rank = run(args, frames)
+        out, rank = run(args, frames, eng)
         if rank == 0:
-            ext = os.path.splitext(inp)[1].lower()
-            fmt = args.output_format or ("mp4" if ext in VIDEO_EXT else "pt" if ext in TENSOR_EXT else "png")
-            path = default_output(inp, fmt if not (fmt == "png" and out.shape[0] > 1) else "png_dir")
-            if args.output:                            # one job: the path as given; a folder of jobs: a directory to fill
-                path = args.output if len(jobs) == 1 else os.path.join(args.output, os.path.basename(path))
-            save_frames(out, path, fmt, fps)
+            path = output_path(args, inp, fmt, len(jobs), single=out.shape[0] == 1)
+            save_frames(out, path, fmt, fps, ops=ops, **writer_kw)
             print(f"Saved: {path}")
     return 0
 
