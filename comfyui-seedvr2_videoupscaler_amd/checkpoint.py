@@ -15,9 +15,12 @@ and the dtype handling around them for the formats the hot path supports:
     spreads it / depth;
   * RoPE ``freqs`` buffers missing from a checkpoint are zero-filled like the reference's meta-buffer
     initialisation (model_loader.py:777-815), with a warning;
+  * ``.gguf`` (gguf.py): F32 / F16 / BF16 tensors as stored, Q8_0 / Q4_K / Q5_K / Q6_K blocks expanded ONCE at load to
+    bf16(the format's fp32 dequantisation) -- on the device by csrc/svr_gguf.hip when ``ops`` is the HIP backend; the
+    reference keeps the blocks and dequantises per op in fp16 (gguf_ops.py:127-130), a small-VRAM policy: here the
+    weights are resident as bf16 like every other format and nothing is executed quantised;
   * both model families: SeedVR2-3B and -7B (dit_7b) checkpoints are told apart by their tensors.
 
-GGUF (llama.cpp block-quantised) checkpoints are a small-VRAM format and out of scope.
 The engines then pre-tile for the MFMA kernels (packing.py).  Registry names: model_registry.py:34-57.
 """
 import os
@@ -33,15 +36,17 @@ DEFAULT_VAE = "ema_vae_fp16.safetensors"
 BF16 = torch.bfloat16
 
 
-def load_state_dict(path: str, device: str = "cpu") -> Dict[str, torch.Tensor]:
+def load_state_dict(path: str, device: str = "cpu", ops=None) -> Dict[str, torch.Tensor]:
+    """``ops`` matters to ``.gguf`` only: the backend whose ``dequant_gguf`` expands the blocks (gguf.load_state_dict)."""
     if path.endswith(".safetensors"):
         from safetensors.torch import load_file
         return load_file(path, device=str(device))
     if path.endswith(".pth") or path.endswith(".pt"):
         return torch.load(path, map_location=str(device), mmap=True, weights_only=True)
     if path.endswith(".gguf"):
-        raise ValueError("GGUF checkpoints are not supported by the MI355X path (use the fp16 / fp8 safetensors)")
-    raise ValueError(f"Unsupported checkpoint format. Expected .safetensors or .pth, got: {path}")
+        from . import gguf
+        return gguf.load_state_dict(path, device=device, ops=ops)
+    raise ValueError(f"Unsupported checkpoint format. Expected .safetensors, .pth or .gguf, got: {path}")
 
 
 def to_compute_dtype(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
@@ -167,7 +172,7 @@ def build_engines(ops, dit_path: Optional[str] = None, vae_path: Optional[str] =
     from .vae import VideoVAEEngine
     dit = vae = None
     if dit_path:
-        sd = load_state_dict(dit_path)
+        sd = load_state_dict(dit_path, ops=ops)
         cfg = dit_cfg or detect_dit_config(sd, os.path.basename(dit_path))
         dit = NaDiTEngine(cfg, prepare_dit_state_dict(sd, cfg), ops)
     if vae_path:

@@ -17,6 +17,7 @@
 #include "svr_calibrate.hip"
 #include "svr_alpha.hip"
 #include "svr_frame_pack.hip"
+#include "svr_gguf.hip"
 
 using namespace svr;
 
@@ -497,6 +498,42 @@ int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, in
     else { if (swap == 0) SVR_PACK8(SVR_STORE_BF16, 0); else if (swap == 3) SVR_PACK8(SVR_STORE_BF16, 3); else SVR_PACK8(SVR_STORE_BF16, 4); }
 #undef SVR_PACK8
     return check(hipGetLastError(), "svr_pack_frames");
+}
+
+// ---- GGUF blocks expanded at load (svr_gguf.hip)
+int svr_dequant_gguf(const void* blocks, int32_t ggml_type, int64_t n_blocks, void* out, int32_t out_kind, int64_t out_bytes,
+                     void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const bool known = ggml_type == SVR_GGML_Q8_0 || ggml_type == SVR_GGML_Q4_K || ggml_type == SVR_GGML_Q5_K || ggml_type == SVR_GGML_Q6_K;
+    const int64_t per = ggml_type == SVR_GGML_Q8_0 ? 32 : 256;            // elements per block
+    const char* why = nullptr;
+    if (!blocks) why = "blocks is a null pointer";
+    else if (!out) why = "out is a null pointer";
+    else if (!known) why = "ggml_type must be SVR_GGML_Q8_0, SVR_GGML_Q4_K, SVR_GGML_Q5_K or SVR_GGML_Q6_K";
+    else if (out_kind != SVR_STORE_BF16 && out_kind != SVR_STORE_FP32) why = "out_kind must be SVR_STORE_BF16 or SVR_STORE_FP32";
+    else if (n_blocks < 1) why = "need n_blocks >= 1";
+    else if (n_blocks > ((int64_t)1 << 40) / per) why = "n_blocks times the block size must not exceed 2^40 elements";
+    else if ((uintptr_t)blocks % 32) why = "blocks is not aligned to 32 bytes";
+    else if ((uintptr_t)out % 16) why = "out is not aligned to 16 bytes";
+    if (why) { snprintf(g_err, sizeof(g_err), "svr_dequant_gguf: %s", why); return -1; }
+    const int64_t need = n_blocks * per * (out_kind == SVR_STORE_FP32 ? 4 : 2);
+    if (out_bytes != need) {
+        snprintf(g_err, sizeof(g_err), "svr_dequant_gguf: out_bytes is %lld, the type and block count need exactly %lld", (long long)out_bytes, (long long)need);
+        return -1;
+    }
+    const int64_t n_units = n_blocks * (per / 8);                          // eight outputs per lane
+    const unsigned grid = (unsigned)std::min<int64_t>((n_units + 255) / 256, (int64_t)device_cu_count() * 8);
+    const unsigned char* b = (const unsigned char*)blocks;
+    const hipStream_t s = (hipStream_t)stream;
+#define SVR_DEQUANT(TYPE) \
+    if (out_kind == SVR_STORE_FP32) hipLaunchKernelGGL((dequant_gguf_kernel<TYPE, SVR_STORE_FP32>), dim3(grid), dim3(256), 0, s, b, out, n_units); \
+    else hipLaunchKernelGGL((dequant_gguf_kernel<TYPE, SVR_STORE_BF16>), dim3(grid), dim3(256), 0, s, b, out, n_units)
+    if (ggml_type == SVR_GGML_Q8_0) { SVR_DEQUANT(SVR_GGML_Q8_0); }
+    else if (ggml_type == SVR_GGML_Q4_K) { SVR_DEQUANT(SVR_GGML_Q4_K); }
+    else if (ggml_type == SVR_GGML_Q5_K) { SVR_DEQUANT(SVR_GGML_Q5_K); }
+    else { SVR_DEQUANT(SVR_GGML_Q6_K); }
+#undef SVR_DEQUANT
+    return check(hipGetLastError(), "svr_dequant_gguf");
 }
 
 }  // extern "C"

@@ -94,6 +94,7 @@ SYMBOLS = {
     "svr_alpha_edges": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i32, _vp, _i64, _vp]),
     "svr_alpha_refine": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _i64, _vp]),
     "svr_pack_frames": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "svr_dequant_gguf": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp]),
     "svr_set_option": (C.c_int, [C.c_char_p, _i32]),
     "svr_mfma_calibrate_workspace_bytes": (C.c_int64, []),
     "svr_mfma_calibrate": (C.c_int, [_vp, _i32, C.POINTER(C.c_double), _vp]),

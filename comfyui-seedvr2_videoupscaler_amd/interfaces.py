@@ -203,8 +203,6 @@ def resolve_model(name: str, model_dir: Optional[str] = None) -> str:
     if not os.path.exists(path):
         raise FileNotFoundError(f"{path} not found: this backend does not download models (no network on the MI355X hosts); "
                                 "place the checkpoint from the reference's model repositories there")
-    if path.endswith(".gguf"):
-        raise ValueError("GGUF checkpoints are a small-VRAM format and not supported on the MI355X path; use the fp16 / fp8 safetensors")
     return path
 
 

@@ -563,3 +563,32 @@ class HipOps:
         hip_lib.check(self.lib.svr_pack_frames(_ptr(frames), kind, T, H, W, Cn, hip_lib.PACK_FORMATS[fmt], _ptr(out),
                                                out.numel() * out.element_size(), self._stream()), "svr_pack_frames")
         return out
+
+    # ------------------------------------------------------------------ GGUF blocks expanded at load
+    def dequant_gguf(self, blocks, ggml_type, out_dtype=BF16, out=None):
+        """GGUF blocks expanded on the device (gguf.py is the specification, bit for bit; csrc/svr_gguf.hip): ``blocks`` a dense uint8
+        tensor of whole Q8_0 / Q4_K / Q5_K / Q6_K blocks (a storage-offset view is fine; one that does not start on 32 bytes -- GGUF's
+        own alignment makes that the rare case -- is copied to a fresh allocation first) -> [n_blocks, block size] bf16 or fp32.  One
+        launch on the current stream, no host synchronisation.  ``out``: a dense tensor of exactly that shape and dtype."""
+        from . import gguf
+        if ggml_type not in gguf.QUANTISED:
+            raise ValueError(f"dequant_gguf: unsupported ggml type {gguf.type_name(ggml_type)}")
+        if out_dtype not in (BF16, torch.float32):
+            raise ValueError(f"dequant_gguf: out_dtype must be torch.bfloat16 or torch.float32, got {out_dtype}")
+        _, per, size, _ = gguf.TYPES[ggml_type]
+        self._chk(blocks, torch.uint8, "dequant_gguf: blocks")
+        if blocks.numel() == 0 or blocks.numel() % size:
+            raise ValueError(f"dequant_gguf: blocks must hold whole {gguf.type_name(ggml_type)} blocks of {size} bytes, got "
+                             f"{blocks.numel()} bytes")
+        n = blocks.numel() // size
+        if out is None:
+            out = torch.empty((n, per), dtype=out_dtype, device=self.device)
+        self._chk(out, out_dtype, "dequant_gguf: out")
+        if tuple(out.shape) != (n, per):
+            raise ValueError(f"dequant_gguf: out must be {(n, per)}, got {tuple(out.shape)}")
+        if blocks.data_ptr() % 32:
+            blocks = blocks.clone()
+        kind = 1 if out_dtype == torch.float32 else 0                        # SVR_STORE_FP32 / SVR_STORE_BF16
+        hip_lib.check(self.lib.svr_dequant_gguf(_ptr(blocks), int(ggml_type), n, _ptr(out), kind, out.numel() * out.element_size(),
+                                                self._stream()), "svr_dequant_gguf")
+        return out

@@ -49,6 +49,7 @@
  *   svr_pack_frames                            element alignment is enough (frames 4 / 2 bytes for fp32 / bf16, out 2 bytes for
  *                                              yuv420p10); 16-byte loads and stores where frames and out are 16-byte aligned (and,
  *                                              for yuv420p10, W % 16 == 0), element accesses otherwise
+ *   svr_dequant_gguf                           blocks 32 (GGUF's own alignment), out 16; anything else is refused
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -67,6 +68,7 @@ extern "C" {
  * v9, additive: + svr_alpha_workspace_bytes() / svr_alpha_stats() / svr_alpha_edges() / svr_alpha_refine() (edge-guided alpha
  * upscaling).  New symbols only -- nothing that existed changed, so the version number stays 9.
  * v9, additive: + svr_pack_frames() (output frames narrowed to rgb8 / bgr8 / yuv420p10 on the device).  A new symbol only.
+ * v9, additive: + svr_dequant_gguf() (GGUF Q8_0 / Q4_K / Q5_K / Q6_K blocks expanded to bf16 / fp32 on the device).  A new symbol only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -356,6 +358,24 @@ int svr_alpha_refine(const void* rgb, const float* base, float* out, uint8_t* ed
 #define SVR_PACK_YUV420P10 2
 int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t fmt, void* out,
                     int64_t out_bytes, void* stream);
+
+/* ---- GGUF block-quantised weights, expanded at load ------------------------------------------- */
+/* gguf.py (the specification, bit for bit): `n_blocks` consecutive blocks of one ggml type -> n_blocks * block size values, each
+ * the format's fp32 dequantisation, stored as fp32 (out_kind SVR_STORE_FP32) or rounded once to bf16, nearest even (SVR_STORE_BF16).
+ * d / dmin are IEEE fp16, everything little-endian:
+ *   SVR_GGML_Q8_0  34 B / 32    d | int8 q[32]                              x = d * q
+ *   SVR_GGML_Q4_K  144 B / 256  d | dmin | scales[12] | qs[128]             x = (d * sc) * q - dmin * m
+ *   SVR_GGML_Q5_K  176 B / 256  d | dmin | scales[12] | qh[32] | qs[128]    the same, q in 0..31
+ *   SVR_GGML_Q6_K  210 B / 256  ql[128] | qh[64] | int8 scales[16] | d      x = (d * scales[e / 16]) * (q - 32)
+ * (the ggml type ids of the file format).  Every argument is checked before the launch: null pointers, a type outside the four, a
+ * bad out_kind, n_blocks < 1 or more than 2^40 elements, out_bytes other than EXACTLY n_blocks * block size * element size, blocks
+ * not 32-byte aligned or out not 16-byte aligned.  One launch on `stream`, no host synchronisation, no workspace. */
+#define SVR_GGML_Q8_0 8
+#define SVR_GGML_Q4_K 12
+#define SVR_GGML_Q5_K 13
+#define SVR_GGML_Q6_K 14
+int svr_dequant_gguf(const void* blocks, int32_t ggml_type, int64_t n_blocks, void* out, int32_t out_kind, int64_t out_bytes,
+                     void* stream);
 
 /* ---- misc ------------------------------------------------------------------------------------ */
 /* Tuning / measurement knobs (no effect on results):
