@@ -17,6 +17,7 @@
 #include "svr_calibrate.hip"
 #include "svr_alpha.hip"
 #include "svr_frame_pack.hip"
+#include "svr_frame_unpack.hip"
 #include "svr_gguf.hip"
 
 using namespace svr;
@@ -498,6 +499,66 @@ int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, in
     else { if (swap == 0) SVR_PACK8(SVR_STORE_BF16, 0); else if (swap == 3) SVR_PACK8(SVR_STORE_BF16, 3); else SVR_PACK8(SVR_STORE_BF16, 4); }
 #undef SVR_PACK8
     return check(hipGetLastError(), "svr_pack_frames");
+}
+
+// ---- packed input frames (svr_frame_unpack.hip)
+int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,
+                      int32_t matrix, int32_t range, float* out, int64_t out_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const bool yuv = fmt == SVR_UNPACK_YUV420P8 || fmt == SVR_UNPACK_YUV420P10;
+    const bool wide = fmt == SVR_UNPACK_RGB16 || fmt == SVR_UNPACK_YUV420P10;          // 16-bit samples
+    const char* why = nullptr;
+    if (!packed) why = "packed is a null pointer";
+    else if (!out) why = "out is a null pointer";
+    else if (T < 1 || H < 1 || W < 1) why = "need T >= 1, H >= 1, W >= 1";
+    else if ((int64_t)H * W > ((int64_t)1 << 40) / T) why = "T * H * W must not exceed 2^40 pixels";
+    else if (fmt != SVR_UNPACK_RGB8 && fmt != SVR_UNPACK_BGR8 && fmt != SVR_UNPACK_RGB16 && !yuv)
+        why = "fmt must be SVR_UNPACK_RGB8, SVR_UNPACK_BGR8, SVR_UNPACK_RGB16, SVR_UNPACK_YUV420P8 or SVR_UNPACK_YUV420P10";
+    else if (yuv ? C != 3 : (C != 3 && C != 4)) why = yuv ? "C must be 3 for the yuv420p formats" : "C must be 3 or 4";
+    else if (matrix != SVR_MATRIX_BT709 && matrix != SVR_MATRIX_BT601) why = "matrix must be SVR_MATRIX_BT709 or SVR_MATRIX_BT601";
+    else if (range != SVR_RANGE_TV && range != SVR_RANGE_PC) why = "range must be SVR_RANGE_TV or SVR_RANGE_PC";
+    else if (wide && (uintptr_t)packed % 2) why = "packed is not aligned to 2 bytes";
+    else if ((uintptr_t)out % 4) why = "out is not aligned to 4 bytes";
+    if (why) { snprintf(g_err, sizeof(g_err), "svr_unpack_frames: %s", why); return -1; }
+    const int64_t px = (int64_t)T * H * W, h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
+    const int64_t n = yuv ? (int64_t)T * ((int64_t)H * W + 2 * h2 * w2) : px * C;       // samples
+    const int64_t need_in = n * (wide ? 2 : 1), need_out = px * C * 4;
+    if (packed_bytes != need_in) {
+        snprintf(g_err, sizeof(g_err), "svr_unpack_frames: packed_bytes is %lld, the format needs exactly %lld", (long long)packed_bytes, (long long)need_in);
+        return -1;
+    }
+    if (out_bytes != need_out) {
+        snprintf(g_err, sizeof(g_err), "svr_unpack_frames: out_bytes is %lld, fp32 [T, H, W, C] needs exactly %lld", (long long)out_bytes, (long long)need_out);
+        return -1;
+    }
+    const bool aligned = (uintptr_t)packed % 16 == 0 && (uintptr_t)out % 16 == 0;
+    const int64_t cap = (int64_t)device_cu_count() * 8;
+    auto capped = [cap](int64_t work) { return (unsigned)std::min<int64_t>((work + 255) / 256, cap); };
+    const hipStream_t s = (hipStream_t)stream;
+    if (yuv) {
+        // Kr, Kb exact decimals, the four products rounded at 2^16: 2 (1 - Kr), 2 (1 - Kb) Kb / Kg, 2 (1 - Kr) Kr / Kg, 2 (1 - Kb)
+        const YuvCoef k = matrix == SVR_MATRIX_BT709 ? YuvCoef{103206, 12276, 30679, 121609} : YuvCoef{91881, 22553, 46802, 116130};
+        const bool vec = aligned && W % 16 == 0;
+        const unsigned grid = capped(vec ? (int64_t)T * h2 * (W / 16) : px);
+#define SVR_UNPACK_YUV(BITS, PC) \
+        if (vec) hipLaunchKernelGGL((unpack_yuv_vec_kernel<BITS, PC>), dim3(grid), dim3(256), 0, s, packed, out, T, H, W, k); \
+        else hipLaunchKernelGGL((unpack_yuv_kernel<BITS, PC>), dim3(grid), dim3(256), 0, s, packed, out, T, H, W, k)
+        if (fmt == SVR_UNPACK_YUV420P8) { if (range == SVR_RANGE_TV) { SVR_UNPACK_YUV(8, 0); } else { SVR_UNPACK_YUV(8, 1); } }
+        else { if (range == SVR_RANGE_TV) { SVR_UNPACK_YUV(10, 0); } else { SVR_UNPACK_YUV(10, 1); } }
+#undef SVR_UNPACK_YUV
+        return check(hipGetLastError(), "svr_unpack_frames");
+    }
+    const int swap = fmt == SVR_UNPACK_BGR8 ? C : 0;               // unpack_rgb_kernel's C: 0 = samples in place
+    const int unit = wide ? 8 : swap == 3 ? 48 : 16;
+    const int64_t n_units = aligned ? n / unit : 0;
+    const unsigned grid = capped(std::max<int64_t>(n_units, n - n_units * unit));
+#define SVR_UNPACK_RGB(BYTES, CH) hipLaunchKernelGGL((unpack_rgb_kernel<BYTES, CH>), dim3(grid), dim3(256), 0, s, packed, out, n_units, n)
+    if (wide) SVR_UNPACK_RGB(2, 0);
+    else if (swap == 0) SVR_UNPACK_RGB(1, 0);
+    else if (swap == 3) SVR_UNPACK_RGB(1, 3);
+    else SVR_UNPACK_RGB(1, 4);
+#undef SVR_UNPACK_RGB
+    return check(hipGetLastError(), "svr_unpack_frames");
 }
 
 // ---- GGUF blocks expanded at load (svr_gguf.hip)

@@ -21,6 +21,9 @@ HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC",
 EPI_BIAS, EPI_BIAS_SILU, EPI_RESID_GATE, EPI_SWIGLU, EPI_BIAS_GELU = 0, 1, 2, 3, 4
 ABI_VERSION = 9
 PACK_FORMATS = {"rgb8": 0, "bgr8": 1, "yuv420p10": 2}      # SVR_PACK_* (include/seedvr2_hip.h)
+UNPACK_FORMATS = {"rgb8": 0, "bgr8": 1, "yuv420p10": 2, "rgb16": 3, "yuv420p8": 4}      # SVR_UNPACK_*
+YUV_MATRICES = {"bt709": 0, "bt601": 1}                    # SVR_MATRIX_*
+YUV_RANGES = {"tv": 0, "pc": 1}                            # SVR_RANGE_*
 # svr_gemm_kernel_class() codes (include/seedvr2_hip.h)
 KERNEL_CLASSES = {0: "none", 1: "gemm", 2: "gemm_persistent", 3: "conv_halo", 4: "conv_subpixel", 5: "conv_thin_in",
                   6: "conv_thinout", 7: "conv_generic"}
@@ -94,6 +97,7 @@ SYMBOLS = {
     "svr_alpha_edges": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i32, _vp, _i64, _vp]),
     "svr_alpha_refine": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _i64, _vp]),
     "svr_pack_frames": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "svr_unpack_frames": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_dequant_gguf": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp]),
     "svr_set_option": (C.c_int, [C.c_char_p, _i32]),
     "svr_mfma_calibrate_workspace_bytes": (C.c_int64, []),

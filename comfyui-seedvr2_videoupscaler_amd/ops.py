@@ -564,6 +564,27 @@ class HipOps:
                                                out.numel() * out.element_size(), self._stream()), "svr_pack_frames")
         return out
 
+    # ------------------------------------------------------------------ packed input frames
+    def unpack_frames(self, packed, fmt, T, H, W, C, matrix="bt709", range_="tv", out=None):
+        """Input frames widened on the device (frameio_in.py is the specification; csrc/svr_frame_unpack.hip): ``packed`` a dense
+        uint8 ("rgb8", "bgr8", "yuv420p8") or uint16 ("rgb16", "yuv420p10") tensor of exactly the format's samples -> fp32
+        [T, H, W, C].  One launch on the current stream, no host synchronisation.  ``out``: a dense fp32 tensor of that shape."""
+        from . import frameio_in
+        try:
+            frameio_in.check_arguments(packed, fmt, T, H, W, C, matrix, range_)
+        except ValueError as e:
+            raise ValueError(f"unpack_frames: {e}") from None
+        self._chk(packed, None, "unpack_frames: packed")
+        if out is None:
+            out = torch.empty((T, H, W, C), dtype=torch.float32, device=self.device)
+        self._chk(out, torch.float32, "unpack_frames: out")
+        if tuple(out.shape) != (T, H, W, C):
+            raise ValueError(f"unpack_frames: out must be {(T, H, W, C)}, got {tuple(out.shape)}")
+        hip_lib.check(self.lib.svr_unpack_frames(_ptr(packed), packed.numel() * packed.element_size(), hip_lib.UNPACK_FORMATS[fmt],
+                                                 T, H, W, C, hip_lib.YUV_MATRICES[matrix], hip_lib.YUV_RANGES[range_], _ptr(out),
+                                                 out.numel() * out.element_size(), self._stream()), "svr_unpack_frames")
+        return out
+
     # ------------------------------------------------------------------ GGUF blocks expanded at load
     def dequant_gguf(self, blocks, ggml_type, out_dtype=BF16, out=None):
         """GGUF blocks expanded on the device (gguf.py is the specification, bit for bit; csrc/svr_gguf.hip): ``blocks`` a dense uint8

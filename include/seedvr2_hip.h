@@ -49,6 +49,9 @@
  *   svr_pack_frames                            element alignment is enough (frames 4 / 2 bytes for fp32 / bf16, out 2 bytes for
  *                                              yuv420p10); 16-byte loads and stores where frames and out are 16-byte aligned (and,
  *                                              for yuv420p10, W % 16 == 0), element accesses otherwise
+ *   svr_unpack_frames                          element alignment is enough (packed 2 bytes for the 16-bit formats, out 4 bytes);
+ *                                              16-byte loads and stores where packed and out are 16-byte aligned (and, for the
+ *                                              yuv420p formats, W % 16 == 0), element accesses otherwise
  *   svr_dequant_gguf                           blocks 32 (GGUF's own alignment), out 16; anything else is refused
  */
 #ifndef SEEDVR2_HIP_H
@@ -69,6 +72,8 @@ extern "C" {
  * upscaling).  New symbols only -- nothing that existed changed, so the version number stays 9.
  * v9, additive: + svr_pack_frames() (output frames narrowed to rgb8 / bgr8 / yuv420p10 on the device).  A new symbol only.
  * v9, additive: + svr_dequant_gguf() (GGUF Q8_0 / Q4_K / Q5_K / Q6_K blocks expanded to bf16 / fp32 on the device).  A new symbol only.
+ * v9, additive: + svr_unpack_frames() (packed input frames -- rgb8 / bgr8 / rgb16 / yuv420p8 / yuv420p10 as a decoder emits them --
+ * widened to fp32 [T, H, W, C] on the device).  A new symbol only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -358,6 +363,32 @@ int svr_alpha_refine(const void* rgb, const float* base, float* out, uint8_t* ed
 #define SVR_PACK_YUV420P10 2
 int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t fmt, void* out,
                     int64_t out_bytes, void* stream);
+
+/* ---- packed input frames -------------------------------------------------------------------- */
+/* frameio_in.py (the specification, bit for bit), the inverse of svr_pack_frames: packed samples as a decoder emits them -> out
+ * fp32 [T, H, W, C] dense, nominally in [0, 1].  Every value is an integer code q over a full scale D, computed in exact integers,
+ * and ONE fp32 operation: the fp32 value nearest to q / D.
+ *   SVR_UNPACK_RGB8 / _BGR8    uint8 [T, H, W, C], C = 3 or 4, D = 255; BGR8 swaps channels 0 and 2 back, a fourth stays in place.
+ *   SVR_UNPACK_RGB16           uint16 [T, H, W, C], C = 3 or 4, D = 65535 (rgb48le / rgba64le).
+ *   SVR_UNPACK_YUV420P8 / _P10 C = 3 only.  uint8 / uint16 [T, H*W + 2*h2*w2], h2 = ceil(H/2), w2 = ceil(W/2): per frame the Y
+ *                              plane, then Cb, then Cr (svr_pack_frames' layout; a 10-bit sample above 1023 counts as 1023).
+ *                              D = 65535.  `matrix` SVR_MATRIX_BT709 / _BT601, `range` SVR_RANGE_TV / _PC; chroma upsampled
+ *                              bilinearly in integers, co-sited with even luma columns and midway between luma rows, indices
+ *                              clamped to the plane; numerators may be negative: floor division, then clamp to 0..65535.
+ * The RGB formats ignore nothing: `matrix` and `range` must be valid codes there too.  Every argument is checked before the launch
+ * (T * H * W <= 2^40 pixels); packed_bytes and out_bytes (= 4 * T*H*W*C) must be EXACTLY the sizes above.  One launch on `stream`,
+ * no host synchronisation, no workspace. */
+#define SVR_UNPACK_RGB8      0    /* (the three formats svr_pack_frames writes keep its ids) */
+#define SVR_UNPACK_BGR8      1
+#define SVR_UNPACK_YUV420P10 2
+#define SVR_UNPACK_RGB16     3
+#define SVR_UNPACK_YUV420P8  4
+#define SVR_MATRIX_BT709 0
+#define SVR_MATRIX_BT601 1
+#define SVR_RANGE_TV 0
+#define SVR_RANGE_PC 1
+int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,
+                      int32_t matrix, int32_t range, float* out, int64_t out_bytes, void* stream);
 
 /* ---- GGUF block-quantised weights, expanded at load ------------------------------------------- */
 /* gguf.py (the specification, bit for bit): `n_blocks` consecutive blocks of one ggml type -> n_blocks * block size values, each

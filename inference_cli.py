@@ -18,17 +18,24 @@ two parsers by ``ast``), so existing scripts keep working.  What the flags DO is
     so the encoder works while the next chunk computes and neither device nor host memory grows with the clip;
   * media I/O is plumbing, not the hot path: images through PIL, tensors as .pt / .npy, video in through OpenCV when it is
     installed (the reference's own dependency), video out through OpenCV or (--video_backend ffmpeg, with --10bit a real
-    10-bit BT.709 plane) an ffmpeg subprocess fed through stdin.
+    10-bit BT.709 plane) an ffmpeg subprocess fed through stdin;
+  * --video_backend ffmpeg also READS video through ffmpeg (FrameSource): ffprobe names the source's pixel format, an ffmpeg child
+    emits the planes at their native depth, ONE reader thread fills two pinned host buffers while the previous chunk computes, and
+    the packed bytes are widened to fp32 on the device (frameio_in.py / csrc/svr_frame_unpack.hip).  The source's audio stream is
+    copied into an mp4 the ffmpeg writer produces.
 """
 import argparse
+import json
 import os
 import platform
 import queue
+import re
 import shutil
 import subprocess
 import sys
 import threading
 import time
+from fractions import Fraction
 from typing import List, Optional
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -38,6 +45,7 @@ PKG = "comfyui-seedvr2_videoupscaler_amd"
 VIDEO_EXT = {".mp4", ".avi", ".mov", ".mkv", ".webm", ".m4v"}
 IMAGE_EXT = {".png", ".jpg", ".jpeg", ".bmp", ".tif", ".tiff", ".webp"}
 TENSOR_EXT = {".pt", ".npy"}
+WHOLE_CLIP_READ_FRAMES = 8         # without --chunk_size, FrameSource's two host buffers hold this many frames each
 
 
 def _itf():
@@ -223,6 +231,195 @@ def open_chunks(path: str, chunk_size: int, skip: int = 0, cap: int = 0):
 
 
 # ---------------------------------------------------------------------------------------------------------
+# Video in through ffmpeg (--video_backend ffmpeg): ffprobe says what the file holds, an ffmpeg child emits raw planes at the
+# source's depth, frameio_in.py / csrc/svr_frame_unpack.hip widens them to fp32 where the engines live.
+def find_ffprobe() -> str:
+    exe = shutil.which("ffprobe")
+    if exe is None:
+        raise RuntimeError("--video_backend ffmpeg needs the ffprobe executable on PATH to read a video and there is none "
+                           "(install ffmpeg, or use --video_backend opencv)")
+    return exe
+
+
+def _tail(errlog) -> str:
+    errlog.seek(0)
+    return errlog.read()[-2000:].decode(errors="replace").strip()
+
+
+def probe_video(ffprobe: str, path: str) -> dict:
+    """One ffprobe run (JSON) -> width, height, fps (a Fraction, from r_frame_rate), pix_fmt, color_space, color_range (None where
+    the file does not say) and has_audio, of the FIRST video stream -- the one FrameSource maps."""
+    r = subprocess.run([ffprobe, "-v", "error", "-print_format", "json", "-show_streams", path], stdout=subprocess.PIPE,
+                       stderr=subprocess.PIPE)
+    if r.returncode != 0:
+        raise RuntimeError(f"ffprobe exited with status {r.returncode}: {r.stderr[-2000:].decode(errors='replace').strip()}")
+    streams = json.loads(r.stdout.decode() or "{}").get("streams", [])
+    video = [st for st in streams if st.get("codec_type") == "video"]
+    if not video:
+        raise ValueError(f"{path}: ffprobe found no video stream")
+    v = video[0]
+    fps = Fraction(30)
+    for key in ("r_frame_rate", "avg_frame_rate"):
+        try:
+            rate = Fraction(v.get(key, "0/0"))
+        except (ValueError, ZeroDivisionError):
+            continue
+        if rate > 0:
+            fps = rate
+            break
+    named = lambda key: v.get(key) if v.get(key) not in (None, "", "unknown", "unspecified") else None
+    return dict(width=int(v["width"]), height=int(v["height"]), fps=fps, pix_fmt=v.get("pix_fmt"), color_space=named("color_space"),
+                color_range=named("color_range"), has_audio=any(st.get("codec_type") == "audio" for st in streams))
+
+
+# source pix_fmt -> (what ffmpeg is asked for: the planes as they are, packed format, range or None = from color_range)
+PLANAR_420 = {"yuv420p": ("yuv420p", "yuv420p8", None), "yuvj420p": ("yuvj420p", "yuv420p8", "pc"),
+              "yuv420p10le": ("yuv420p10le", "yuv420p10", None)}
+# every other format with at most 8 bits per component is converted by ffmpeg to rgb24 / rgba; everything else -- deeper formats
+# and names this set does not know -- to rgb48le / rgba64le
+EIGHT_BIT = {"yuv410p", "yuv411p", "yuv422p", "yuv440p", "yuv444p", "yuvj411p", "yuvj422p", "yuvj440p", "yuvj444p", "nv12", "nv21",
+             "nv16", "nv24", "nv42", "yuyv422", "uyvy422", "yvyu422", "uyyvyy411", "gray", "monow", "monob", "pal8", "rgb24", "bgr24", "rgb0",
+             "bgr0", "0rgb", "0bgr", "rgb8", "bgr8", "rgb4", "bgr4", "rgb4_byte", "bgr4_byte", "gbrp", "rgba", "bgra", "argb", "abgr",
+             "ya8", "gbrap", "yuva420p", "yuva422p", "yuva444p"}
+HAS_ALPHA = re.compile(r"^(yuva|gbrap|ya\d|rgba|bgra|argb|abgr|ayuv|vuya)")
+MATRIX_OF = {"bt709": "bt709", "smpte170m": "bt601", "bt470bg": "bt601"}
+
+
+def route_input(info: dict):
+    """-> (ffmpeg's -pix_fmt, packed format, C, matrix, range_): planar 4:2:0 of 8 / 10 bits crosses the pipe as it is stored and is
+    converted on the device with the stream's own matrix and range; anything else is converted by ffmpeg to RGB of enough depth."""
+    pix = info.get("pix_fmt") or ""
+    alpha = bool(HAS_ALPHA.match(pix))
+    space = info.get("color_space")
+    matrix = MATRIX_OF.get(space) if space is not None else ("bt709" if info["height"] >= 720 else "bt601")
+    if pix in PLANAR_420 and matrix is not None:
+        raw, fmt, range_ = PLANAR_420[pix]
+        if range_ is None:
+            range_ = "pc" if info.get("color_range") in ("pc", "jpeg") else "tv"
+        return raw, fmt, 3, matrix, range_
+    if pix in EIGHT_BIT:
+        return ("rgba" if alpha else "rgb24"), "rgb8", (4 if alpha else 3), "bt709", "tv"
+    return ("rgba64le" if alpha else "rgb48le"), "rgb16", (4 if alpha else 3), "bt709", "tv"
+
+
+class FrameSource:
+    """Video -> fp32 chunks on ``device``, the counterpart of FrameSink.  One ffmpeg child decodes every frame exactly once, in
+    order (``-f rawvideo`` carries no timestamps, so ffmpeg neither drops nor duplicates frames), at the depth route_input()
+    chose.  ONE reader thread fills one of TWO host buffers (pinned when ``device`` is a GPU) with up to ``chunk_size`` frames while
+    the previous chunk computes; the thread makes no GPU call.  ``chunks()`` -- the caller's thread -- uploads the packed bytes and
+    widens them with frameio_in.unpack_frames(..., ops): [t <= chunk_size, H, W, 3 | 4] fp32 tensors already on the device, which
+    pipeline.upscale_stream takes as they are.  ``skip`` frames are read and dropped, after ``cap`` frames the child is
+    terminated; a short last chunk and an empty stream behave as in open_chunks; a child that exits non-zero raises with the tail
+    of its stderr.  ``exe``: the executable (find_ffmpeg(), resolved before any GPU work; a test passes its own)."""
+
+    def __init__(self, exe: str, path: str, info: dict, chunk_size: int, skip: int = 0, cap: int = 0, ops=None, device="cpu"):
+        import importlib
+        import tempfile
+        import torch
+        if chunk_size <= 0:
+            raise ValueError("chunk_size must be positive")
+        self.frameio_in = importlib.import_module(f"{PKG}.frameio_in")
+        self.raw, self.fmt, self.C, self.matrix, self.range_ = route_input(info)
+        self.H, self.W, self.fps = info["height"], info["width"], info["fps"]
+        self.chunk_size, self.skip, self.cap, self.ops, self.device = chunk_size, skip, cap, ops, torch.device(device)
+        self.frame_bytes = self.frameio_in.frame_bytes(self.H, self.W, self.C, self.fmt)
+        pinned = self.device.type == "cuda"
+        self.buffers = [torch.empty(chunk_size * self.frame_bytes, dtype=torch.uint8, pin_memory=pinned) for _ in range(2)]
+        self.free, self.work = queue.Queue(), queue.Queue()
+        for slot in range(2):
+            self.free.put(slot)
+        self.stopped = False
+        self.errlog = tempfile.TemporaryFile()                   # (a file, not a pipe: nobody drains stderr while frames flow)
+        self.proc = subprocess.Popen(self.command(exe, path), stdin=subprocess.DEVNULL, stdout=subprocess.PIPE, stderr=self.errlog)
+        self.thread = threading.Thread(target=self._fill, name="frame-reader", daemon=True)
+        self.thread.start()
+
+    def command(self, exe, path):
+        return [exe, "-loglevel", "error", "-noautorotate", "-i", path, "-map", "0:v:0", "-f", "rawvideo", "-pix_fmt", self.raw, "-"]
+
+    def _read(self, view) -> int:
+        """fill ``view`` from the child's stdout; -> bytes read (less than asked for: the stream ended)"""
+        got = 0
+        while got < len(view):
+            n = self.proc.stdout.readinto(view[got:])
+            if not n:
+                break
+            got += n
+        return got
+
+    def _fill(self):
+        try:
+            fb, left = self.frame_bytes, (self.cap if self.cap > 0 else None)
+            ended = False
+            if self.skip > 0:                                    # read and dropped, a chunk's worth at a time
+                scratch = memoryview(bytearray(min(self.skip, self.chunk_size) * fb))
+                todo = self.skip * fb
+                while todo > 0 and not ended:
+                    want = min(todo, len(scratch))
+                    ended = self._read(scratch[:want]) < want
+                    todo -= want
+            while not ended and not self.stopped and (left is None or left > 0):
+                slot = self.free.get()
+                if slot is None:
+                    break
+                want = self.chunk_size if left is None else min(self.chunk_size, left)
+                got = self._read(memoryview(self.buffers[slot].numpy())[:want * fb])
+                ended = got < want * fb
+                if got % fb:
+                    raise RuntimeError(f"the decoder's output ended inside a frame ({got % fb} of {fb} bytes)")
+                if left is not None:
+                    left -= got // fb
+                if got:
+                    self.work.put((slot, got // fb))
+            if not ended:                                        # --load_cap reached (or close() early): the rest is not decoded
+                self.stopped = True
+                self.proc.terminate()
+            rc = self.proc.wait()
+            if rc != 0 and not self.stopped:
+                raise RuntimeError(f"ffmpeg exited with status {rc}: {_tail(self.errlog)}")
+            self.work.put(None)
+        except BaseException as e:                               # noqa: BLE001 (handed to the caller's thread)
+            self.work.put(e)
+
+    def chunks(self):
+        import torch
+        first = True
+        try:
+            while True:
+                item = self.work.get()
+                if isinstance(item, RuntimeError):               # (the decoder's own failure: its message as it is)
+                    raise item
+                if isinstance(item, BaseException):
+                    raise RuntimeError(f"reading frames failed: {type(item).__name__}: {item}") from item
+                if item is None:
+                    if first:
+                        raise ValueError("No frames to process")
+                    return
+                slot, t = item
+                first = False
+                host = self.buffers[slot][:t * self.frame_bytes]
+                packed = host.to(self.device) if self.device.type == "cuda" else host.clone()     # (returns when the bytes are there)
+                self.free.put(slot)
+                packed = packed.view(self.frameio_in.packed_dtype(self.fmt))
+                yield self.frameio_in.unpack_frames(packed, self.fmt, t, self.H, self.W, self.C, self.matrix, self.range_, ops=self.ops)
+                del packed
+        finally:
+            self.close()
+
+    def close(self):
+        """Stop the child if it still runs, let the thread end, drop the log (idempotent)."""
+        if not self.stopped:
+            self.stopped = True
+            if self.proc.poll() is None:
+                self.proc.terminate()
+        self.free.put(None)
+        self.thread.join()
+        self.proc.wait()
+        self.proc.stdout.close()
+        self.errlog.close()
+
+
+# ---------------------------------------------------------------------------------------------------------
 # Writers: host code only (no GPU call), fed packed frames (frameio.py) as numpy arrays by FrameSink's thread.  ``fmt`` names the
 # packed format a writer takes (None: the fp32 frames themselves), ``alpha`` whether it keeps a fourth channel.
 class PngWriter:
@@ -279,11 +476,14 @@ def find_ffmpeg() -> str:
 class FFmpegWriter:
     """An ffmpeg subprocess fed raw frames through stdin: bgr24 -> libx264 / yuv420p, or (``ten_bit``) yuv420p10le -> libx265 /
     yuv420p10le -- the planes frameio.py computes from the fp32 frames, not 8-bit frames widened.  The stream is tagged BT.709,
-    tv range.  ``exe``: the executable (find_ffmpeg(), resolved before any GPU work; a test passes its own)."""
+    tv range.  ``exe``: the executable (find_ffmpeg(), resolved before any GPU work; a test passes its own).  ``fps``: a float or a
+    Fraction (passed on as num/den).  ``audio``: (source path, offset in seconds) -- the source as a second input whose audio
+    stream, where it has one, is copied (no re-encoding: a codec the container refuses is ffmpeg's own message); None: the command
+    without it, as it always was."""
     alpha = False
 
-    def __init__(self, exe: str, path: str, fps: float, ten_bit: bool = False):
-        self.exe, self.path, self.fps, self.ten_bit = exe, path, fps, ten_bit
+    def __init__(self, exe: str, path: str, fps, ten_bit: bool = False, audio=None):
+        self.exe, self.path, self.fps, self.ten_bit, self.audio = exe, path, fps, ten_bit, audio
         self.fmt = "yuv420p10" if ten_bit else "bgr8"
         self.proc, self.errlog = None, None
 
@@ -293,8 +493,14 @@ class FFmpegWriter:
         # 8 bits: ffmpeg converts bgr24 itself, and its default RGB -> YUV matrix is BT.601 whatever the output is tagged with:
         # the scale filter is told the matrix and range the tags then state
         convert = [] if self.ten_bit else ["-vf", "scale=out_color_matrix=bt709:out_range=tv"]
-        return ([self.exe, "-y", "-loglevel", "error", "-f", "rawvideo", "-pix_fmt", raw, "-s", f"{width}x{height}", "-r", f"{self.fps:g}"]
-                + (tags if self.ten_bit else []) + ["-i", "-"] + convert
+        rate = f"{self.fps.numerator}/{self.fps.denominator}" if isinstance(self.fps, Fraction) and self.fps.denominator != 1 else f"{float(self.fps):g}"
+        second, mux = [], []
+        if self.audio is not None:
+            src, offset = self.audio
+            second = (["-ss", f"{float(offset):.6f}"] if offset > 0 else []) + ["-i", src]
+            mux = ["-map", "0:v:0", "-map", "1:a?", "-c:a", "copy", "-shortest"]
+        return ([self.exe, "-y", "-loglevel", "error", "-f", "rawvideo", "-pix_fmt", raw, "-s", f"{width}x{height}", "-r", rate]
+                + (tags if self.ten_bit else []) + ["-i", "-"] + second + convert + mux
                 + ["-c:v", codec, "-pix_fmt", pix, "-preset", "medium", "-crf", "12"] + tags + [self.path])
 
     def write(self, arr, height, width):
@@ -428,13 +634,13 @@ class FrameSink:
 
 
 def open_writer(fmt: str, path: str, fps: float, single: bool = False, video_backend: str = "opencv", ten_bit: bool = False,
-                ffmpeg: Optional[str] = None):
+                ffmpeg: Optional[str] = None, audio=None):
     if fmt == "pt":
         return TensorWriter(path)
     if fmt == "png":
         return PngWriter(path, single)
     if video_backend == "ffmpeg":
-        return FFmpegWriter(ffmpeg or find_ffmpeg(), path, fps, ten_bit)
+        return FFmpegWriter(ffmpeg or find_ffmpeg(), path, fps, ten_bit, audio)
     return OpenCVWriter(path, fps)
 
 
@@ -575,26 +781,38 @@ def main(argv: Optional[List[str]] = None) -> int:
     ext_of = lambda inp: os.path.splitext(inp)[1].lower()
     fmt_of = lambda inp: args.output_format or ("mp4" if ext_of(inp) in VIDEO_EXT else "pt" if ext_of(inp) in TENSOR_EXT else "png")
     # the encoder is looked for ONCE, before any GPU work: a missing executable must not cost a model load or a clip
-    ffmpeg = None
-    if args.video_backend == "ffmpeg" and any(fmt_of(inp) == "mp4" for inp in jobs):
+    # ... and so is the decoder: with --video_backend ffmpeg a video input is read through ffmpeg too (FrameSource)
+    via_ffmpeg = lambda inp: args.video_backend == "ffmpeg" and ext_of(inp) in VIDEO_EXT
+    ffmpeg = ffprobe = None
+    if args.video_backend == "ffmpeg" and any(fmt_of(inp) == "mp4" or via_ffmpeg(inp) for inp in jobs):
         ffmpeg = find_ffmpeg()
+    if any(via_ffmpeg(inp) for inp in jobs):
+        ffprobe = find_ffprobe()
     if args.use_10bit and args.video_backend != "ffmpeg":
         print("Warning: --10bit needs --video_backend ffmpeg; writing 8-bit video", file=sys.stderr)
     writer_kw = dict(video_backend=args.video_backend, ten_bit=args.use_10bit and args.video_backend == "ffmpeg", ffmpeg=ffmpeg)
     for inp in jobs:                                   # the engines stay resident between jobs (interfaces.get_runner)
         fmt = fmt_of(inp)
+        info = probe_video(ffprobe, inp) if via_ffmpeg(inp) else None          # (before the engines: a file ffprobe refuses costs no model load)
         eng = engines(args)
         rank, ops = eng[3], getattr(eng[0].dit, "ops", None)    # (the runner's backend also narrows the frames for the writers)
+        job_kw = dict(writer_kw)
+        if info is not None and info["has_audio"] and fmt == "mp4":            # (via_ffmpeg: the writer is FFmpegWriter)
+            job_kw["audio"] = (inp, args.skip_first_frames / float(info["fps"]))
+        source = lambda n: FrameSource(ffmpeg, inp, info, n, args.skip_first_frames, args.load_cap, ops, eng[0].dit.device)
         if args.chunk_size > 0 and ext_of(inp) not in IMAGE_EXT:
             # streaming: read, upscale, pack and write --chunk_size frames at a time
-            chunks, fps = open_chunks(inp, args.chunk_size, args.skip_first_frames, args.load_cap)
+            if info is not None:
+                chunks, fps = source(args.chunk_size).chunks(), info["fps"]
+            else:
+                chunks, fps = open_chunks(inp, args.chunk_size, args.skip_first_frames, args.load_cap)
             path = output_path(args, inp, fmt, len(jobs), single=False)
             sink, t0 = None, time.time()
             try:
                 for out in run_stream(args, chunks, eng):
                     if rank == 0:
                         if sink is None:
-                            sink = FrameSink(open_writer(fmt, path, fps, False, **writer_kw), ops)
+                            sink = FrameSink(open_writer(fmt, path, fps, False, **job_kw), ops)
                         sink.put(out)
                     del out
             except BaseException:
@@ -607,11 +825,15 @@ def main(argv: Optional[List[str]] = None) -> int:
                 print(f"Streamed {sink.frames} frames in chunks of {args.chunk_size} in {dt:.2f}s ({sink.frames / dt:.2f} FPS)")
                 print(f"Saved: {path}")
             continue
-        frames, fps = load_frames(inp, args.skip_first_frames, args.load_cap)
+        if info is not None:                           # the whole clip, read in chunks and concatenated on the device
+            import torch
+            frames, fps = torch.cat(list(source(WHOLE_CLIP_READ_FRAMES).chunks())), info["fps"]
+        else:
+            frames, fps = load_frames(inp, args.skip_first_frames, args.load_cap)
         out, rank = run(args, frames, eng)
         if rank == 0:
             path = output_path(args, inp, fmt, len(jobs), single=out.shape[0] == 1)
-            save_frames(out, path, fmt, fps, ops=ops, **writer_kw)
+            save_frames(out, path, fmt, fps, ops=ops, **job_kw)
             print(f"Saved: {path}")
     return 0
 
