@@ -17,6 +17,7 @@
 #include "svr_calibrate.hip"
 #include "svr_alpha.hip"
 #include "svr_frame_pack.hip"
+#include "svr_frame_pack_colour.hip"
 #include "svr_frame_unpack.hip"
 #include "svr_gguf.hip"
 
@@ -499,6 +500,49 @@ int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, in
     else { if (swap == 0) SVR_PACK8(SVR_STORE_BF16, 0); else if (swap == 3) SVR_PACK8(SVR_STORE_BF16, 3); else SVR_PACK8(SVR_STORE_BF16, 4); }
 #undef SVR_PACK8
     return check(hipGetLastError(), "svr_pack_frames");
+}
+
+// ---- yuv420p10 planes with a chosen matrix, range and chroma siting (svr_frame_pack_colour.hip)
+int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t matrix, int32_t range,
+                       int32_t siting, void* out, int64_t out_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const char* why = nullptr;
+    if (!frames) why = "frames is a null pointer";
+    else if (!out) why = "out is a null pointer";
+    else if (x_kind != SVR_STORE_BF16 && x_kind != SVR_STORE_FP32) why = "x_kind must be SVR_STORE_BF16 or SVR_STORE_FP32";
+    else if (T < 1 || H < 1 || W < 1) why = "need T >= 1, H >= 1, W >= 1";
+    else if ((int64_t)H * W > ((int64_t)1 << 40) / T) why = "T * H * W must not exceed 2^40 pixels";
+    else if (matrix != SVR_COLOUR_MATRIX_BT709 && matrix != SVR_COLOUR_MATRIX_BT601 && matrix != SVR_COLOUR_MATRIX_BT2020)
+        why = "matrix must be SVR_COLOUR_MATRIX_BT709, SVR_COLOUR_MATRIX_BT601 or SVR_COLOUR_MATRIX_BT2020";
+    else if (range != SVR_COLOUR_RANGE_TV && range != SVR_COLOUR_RANGE_PC) why = "range must be SVR_COLOUR_RANGE_TV or SVR_COLOUR_RANGE_PC";
+    else if (siting != SVR_COLOUR_SITING_CENTER && siting != SVR_COLOUR_SITING_LEFT) why = "siting must be SVR_COLOUR_SITING_CENTER or SVR_COLOUR_SITING_LEFT";
+    else if ((uintptr_t)frames % (x_kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
+    else if ((uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
+    if (why) { snprintf(g_err, sizeof(g_err), "svr_pack_yuv420p10: %s", why); return -1; }
+    const int64_t h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
+    const int64_t need = 2 * (int64_t)T * ((int64_t)H * W + 2 * h2 * w2);
+    if (out_bytes != need) {
+        snprintf(g_err, sizeof(g_err), "svr_pack_yuv420p10: out_bytes is %lld, the planes need exactly %lld", (long long)out_bytes, (long long)need);
+        return -1;
+    }
+    // Kr, Kb exact decimals, every weight rounded at 2^16, luma deficit to green (frameio.yuv_matrix): wr, wg, wb | cb_r, cb_g | cr_g, cr_b
+    PackCoef k = matrix == SVR_COLOUR_MATRIX_BT709 ? PackCoef{0, 0, 0, 13933, 46871, 4732, -7509, -25259, -29763, -3005}
+               : matrix == SVR_COLOUR_MATRIX_BT601 ? PackCoef{0, 0, 0, 19595, 38470, 7471, -11058, -21710, -27439, -5329}
+                                                   : PackCoef{0, 0, 0, 17216, 44434, 3886, -9151, -23617, -30133, -2635};
+    if (range == SVR_COLOUR_RANGE_TV) { k.y0 = 64; k.ys = 876; k.cs = 896; } else { k.y0 = 0; k.ys = 1023; k.cs = 1023; }
+    const bool vec = (uintptr_t)frames % 16 == 0 && (uintptr_t)out % 16 == 0 && W % 16 == 0;
+    const int64_t cap = (int64_t)device_cu_count() * 8;
+    const unsigned grid = (unsigned)std::min<int64_t>(((vec ? (int64_t)T * h2 * (W / 16) : (int64_t)T * h2 * w2) + 255) / 256, cap);
+    const hipStream_t s = (hipStream_t)stream;
+    unsigned short* o = (unsigned short*)out;
+#define SVR_PACK_COLOUR(KIND, LEFT) \
+    if (vec) hipLaunchKernelGGL((pack_colour_vec_kernel<KIND, LEFT>), dim3(grid), dim3(256), 0, s, frames, o, T, H, W, k); \
+    else hipLaunchKernelGGL((pack_colour_kernel<KIND, LEFT>), dim3(grid), dim3(256), 0, s, frames, o, T, H, W, k)
+    const bool left = siting == SVR_COLOUR_SITING_LEFT;
+    if (x_kind == SVR_STORE_FP32) { if (left) { SVR_PACK_COLOUR(SVR_STORE_FP32, true); } else { SVR_PACK_COLOUR(SVR_STORE_FP32, false); } }
+    else { if (left) { SVR_PACK_COLOUR(SVR_STORE_BF16, true); } else { SVR_PACK_COLOUR(SVR_STORE_BF16, false); } }
+#undef SVR_PACK_COLOUR
+    return check(hipGetLastError(), "svr_pack_yuv420p10");
 }
 
 // ---- packed input frames (svr_frame_unpack.hip)

@@ -24,6 +24,9 @@ PACK_FORMATS = {"rgb8": 0, "bgr8": 1, "yuv420p10": 2}      # SVR_PACK_* (include
 UNPACK_FORMATS = {"rgb8": 0, "bgr8": 1, "yuv420p10": 2, "rgb16": 3, "yuv420p8": 4}      # SVR_UNPACK_*
 YUV_MATRICES = {"bt709": 0, "bt601": 1}                    # SVR_MATRIX_*
 YUV_RANGES = {"tv": 0, "pc": 1}                            # SVR_RANGE_*
+COLOUR_MATRICES = {"bt709": 0, "bt601": 1, "bt2020": 2}    # SVR_COLOUR_MATRIX_* (svr_pack_yuv420p10 only)
+COLOUR_RANGES = {"tv": 0, "pc": 1}                         # SVR_COLOUR_RANGE_*
+COLOUR_SITINGS = {"center": 0, "left": 1}                  # SVR_COLOUR_SITING_*
 # svr_gemm_kernel_class() codes (include/seedvr2_hip.h)
 KERNEL_CLASSES = {0: "none", 1: "gemm", 2: "gemm_persistent", 3: "conv_halo", 4: "conv_subpixel", 5: "conv_thin_in",
                   6: "conv_thinout", 7: "conv_generic"}
@@ -97,6 +100,7 @@ SYMBOLS = {
     "svr_alpha_edges": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _i32, _vp, _i64, _vp]),
     "svr_alpha_refine": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i64, _i32, _i64, _vp, _i64, _vp]),
     "svr_pack_frames": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "svr_pack_yuv420p10": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_unpack_frames": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_dequant_gguf": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp]),
     "svr_set_option": (C.c_int, [C.c_char_p, _i32]),

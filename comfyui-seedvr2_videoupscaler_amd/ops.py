@@ -564,6 +564,34 @@ class HipOps:
                                                out.numel() * out.element_size(), self._stream()), "svr_pack_frames")
         return out
 
+    def pack_yuv420p10(self, frames, matrix="bt709", range_="tv", siting="center", out=None):
+        """yuv420p10 planes with a chosen matrix ("bt709" | "bt601" | "bt2020"), range ("tv" | "pc") and chroma siting ("center" |
+        "left") on the device (frameio.pack_yuv420p10_torch is the specification; csrc/svr_frame_pack_colour.hip): frames
+        [T, H, W, 3] fp32 / bf16, dense -> uint16 [T, H*W + 2*h2*w2].  One launch on the current stream, no host synchronisation.
+        ``out``: a dense tensor of exactly that shape and dtype."""
+        from . import frameio
+        if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
+            raise ValueError(f"pack_yuv420p10: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
+        T, H, W, Cn = frames.shape
+        try:
+            frameio.check_colour(matrix, range_, siting)
+            shape = frameio.packed_shape(T, H, W, Cn, "yuv420p10")
+        except ValueError as e:
+            raise ValueError(f"pack_yuv420p10: {e}") from None
+        if T < 1 or H < 1 or W < 1:
+            raise ValueError(f"pack_yuv420p10: frames must hold at least one pixel, got {tuple(frames.shape)}")
+        self._chk(frames, None, "pack_yuv420p10: frames")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.uint16, device=self.device)
+        self._chk(out, torch.uint16, "pack_yuv420p10: out")
+        if tuple(out.shape) != tuple(shape):
+            raise ValueError(f"pack_yuv420p10: out must be {tuple(shape)}, got {tuple(out.shape)}")
+        kind = 1 if frames.dtype == torch.float32 else 0                     # SVR_STORE_FP32 / SVR_STORE_BF16
+        hip_lib.check(self.lib.svr_pack_yuv420p10(_ptr(frames), kind, T, H, W, hip_lib.COLOUR_MATRICES[matrix],
+                                                  hip_lib.COLOUR_RANGES[range_], hip_lib.COLOUR_SITINGS[siting], _ptr(out),
+                                                  out.numel() * out.element_size(), self._stream()), "svr_pack_yuv420p10")
+        return out
+
     # ------------------------------------------------------------------ packed input frames
     def unpack_frames(self, packed, fmt, T, H, W, C, matrix="bt709", range_="tv", out=None):
         """Input frames widened on the device (frameio_in.py is the specification; csrc/svr_frame_unpack.hip): ``packed`` a dense

@@ -49,6 +49,8 @@
  *   svr_pack_frames                            element alignment is enough (frames 4 / 2 bytes for fp32 / bf16, out 2 bytes for
  *                                              yuv420p10); 16-byte loads and stores where frames and out are 16-byte aligned (and,
  *                                              for yuv420p10, W % 16 == 0), element accesses otherwise
+ *   svr_pack_yuv420p10                         as svr_pack_frames' yuv420p10: element alignment is enough; 16-byte loads and stores where
+ *                                              frames and out are 16-byte aligned and W % 16 == 0, element accesses otherwise
  *   svr_unpack_frames                          element alignment is enough (packed 2 bytes for the 16-bit formats, out 4 bytes);
  *                                              16-byte loads and stores where packed and out are 16-byte aligned (and, for the
  *                                              yuv420p formats, W % 16 == 0), element accesses otherwise
@@ -74,6 +76,8 @@ extern "C" {
  * v9, additive: + svr_dequant_gguf() (GGUF Q8_0 / Q4_K / Q5_K / Q6_K blocks expanded to bf16 / fp32 on the device).  A new symbol only.
  * v9, additive: + svr_unpack_frames() (packed input frames -- rgb8 / bgr8 / rgb16 / yuv420p8 / yuv420p10 as a decoder emits them --
  * widened to fp32 [T, H, W, C] on the device).  A new symbol only.
+ * v9, additive: + svr_pack_yuv420p10() (yuv420p10 planes with a chosen matrix -- BT.709 / BT.601 / BT.2020 --, range and chroma
+ * siting: what an HDR source is written with).  A new symbol only; svr_pack_frames and its bytes are untouched.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -363,6 +367,34 @@ int svr_alpha_refine(const void* rgb, const float* base, float* out, uint8_t* ed
 #define SVR_PACK_YUV420P10 2
 int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t fmt, void* out,
                     int64_t out_bytes, void* stream);
+
+/* ---- yuv420p10 planes with a chosen matrix, range and chroma siting ----------------------------- */
+/* frameio.pack_yuv420p10_torch (the specification, bit for bit): frames [T, H, W, 3] dense, fp32 or bf16 (x_kind SVR_STORE_FP32 /
+ * SVR_STORE_BF16), nominally in [0, 1] -> out uint16 [T, H*W + 2*h2*w2] in SVR_PACK_YUV420P10's plane layout (Y, Cb, Cr per frame;
+ * h2 = ceil(H/2), w2 = ceil(W/2)).  Exact integers from q = rint(clamp(x, 0, 1) * 65535), D = 65535 * 65536:
+ *   range   SVR_COLOUR_RANGE_TV: y0 = 64, ys = 876, cs = 896;  SVR_COLOUR_RANGE_PC: y0 = 0, ys = cs = 1023.
+ *   matrix  Kr / Kb 0.2126 / 0.0722 (BT709), 0.299 / 0.114 (BT601), 0.2627 / 0.0593 (BT2020), every weight rounded to nearest at 2^16,
+ *           the luma deficit to green; as wr, wg, wb | cb_r, cb_g | cr_g, cr_b:
+ *             BT709   13933, 46871, 4732 |  -7509, -25259 | -29763, -3005
+ *             BT601   19595, 38470, 7471 | -11058, -21710 | -27439, -5329
+ *             BT2020  17216, 44434, 3886 |  -9151, -23617 | -30133, -2635
+ *   luma    Y = y0 + (ys * (wr r + wg g + wb b) + D/2) / D.
+ *   siting  sr, sg, sb = weighted sums of q, total weight S, indices clamped to the frame.  SVR_COLOUR_SITING_CENTER: the 2 x 2
+ *           block, weights 1, S = 4.  SVR_COLOUR_SITING_LEFT: rows 2j, 2j+1, columns 2k-1, 2k, 2k+1 with weights 1, 2, 1, S = 8
+ *           (chroma co-sited with even luma columns: the H.264 / HEVC default, what svr_unpack_frames assumes).
+ *   chroma  Cb = min((S * 512 * D + cs * (cb_r sr + cb_g sg + 32768 sb) + S * D/2) / (S * D), 1023), Cr with (32768, cr_g, cr_b).
+ * (BT709, TV, CENTER) gives the bytes of svr_pack_frames' SVR_PACK_YUV420P10.  NaN -> code 0, +inf -> full scale, -inf -> 0.
+ * Every argument is checked before the launch (T * H * W <= 2^40 pixels); out_bytes must be EXACTLY 2 * T * (H*W + 2*h2*w2).  One
+ * launch on `stream`, no host synchronisation, no workspace. */
+#define SVR_COLOUR_MATRIX_BT709  0
+#define SVR_COLOUR_MATRIX_BT601  1
+#define SVR_COLOUR_MATRIX_BT2020 2
+#define SVR_COLOUR_RANGE_TV 0
+#define SVR_COLOUR_RANGE_PC 1
+#define SVR_COLOUR_SITING_CENTER 0
+#define SVR_COLOUR_SITING_LEFT   1
+int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t matrix, int32_t range,
+                       int32_t siting, void* out, int64_t out_bytes, void* stream);
 
 /* ---- packed input frames -------------------------------------------------------------------- */
 /* frameio_in.py (the specification, bit for bit), the inverse of svr_pack_frames: packed samples as a decoder emits them -> out

@@ -18,7 +18,9 @@ two parsers by ``ast``), so existing scripts keep working.  What the flags DO is
     so the encoder works while the next chunk computes and neither device nor host memory grows with the clip;
   * media I/O is plumbing, not the hot path: images through PIL, tensors as .pt / .npy, video in through OpenCV when it is
     installed (the reference's own dependency), video out through OpenCV or (--video_backend ffmpeg, with --10bit a real
-    10-bit BT.709 plane) an ffmpeg subprocess fed through stdin;
+    10-bit BT.709 plane) an ffmpeg subprocess fed through stdin.  An HDR / wide-gamut source (BT.2020 primaries or matrix, a PQ
+    or HLG transfer) read through ffmpeg leaves --10bit as BT.2020 planes with left-sited chroma, tagged with the source's
+    primaries and transfer (output_colour, DESIGN.md 7.3c); every other source is written as it always was;
   * --video_backend ffmpeg also READS video through ffmpeg (FrameSource): ffprobe names the source's pixel format, an ffmpeg child
     emits the planes at their native depth, ONE reader thread fills two pinned host buffers while the previous chunk computes, and
     the packed bytes are widened to fp32 on the device (frameio_in.py / csrc/svr_frame_unpack.hip).  The source's audio stream is
@@ -246,9 +248,12 @@ def _tail(errlog) -> str:
     return errlog.read()[-2000:].decode(errors="replace").strip()
 
 
-def probe_video(ffprobe: str, path: str) -> dict:
-    """One ffprobe run (JSON) -> width, height, fps (a Fraction, from r_frame_rate), pix_fmt, color_space, color_range (None where
-    the file does not say) and has_audio, of the FIRST video stream -- the one FrameSource maps."""
+COLOUR_FIELDS = ("color_space", "color_primaries", "color_transfer", "color_range", "chroma_location")
+
+
+def probe_source(ffprobe: str, path: str):
+    """One ffprobe run (JSON) -> (probe_video's dictionary, probe_colour's dictionary) of the FIRST video stream -- the one
+    FrameSource maps."""
     r = subprocess.run([ffprobe, "-v", "error", "-print_format", "json", "-show_streams", path], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE)
     if r.returncode != 0:
@@ -268,8 +273,47 @@ def probe_video(ffprobe: str, path: str) -> dict:
             fps = rate
             break
     named = lambda key: v.get(key) if v.get(key) not in (None, "", "unknown", "unspecified") else None
-    return dict(width=int(v["width"]), height=int(v["height"]), fps=fps, pix_fmt=v.get("pix_fmt"), color_space=named("color_space"),
+    info = dict(width=int(v["width"]), height=int(v["height"]), fps=fps, pix_fmt=v.get("pix_fmt"), color_space=named("color_space"),
                 color_range=named("color_range"), has_audio=any(st.get("codec_type") == "audio" for st in streams))
+    return info, {key: named(key) for key in COLOUR_FIELDS}
+
+
+def probe_video(ffprobe: str, path: str) -> dict:
+    """-> width, height, fps (a Fraction, from r_frame_rate), pix_fmt, color_space, color_range (None where the file does not say)
+    and has_audio."""
+    return probe_source(ffprobe, path)[0]
+
+
+def probe_colour(ffprobe: str, path: str) -> dict:
+    """-> color_space, color_primaries, color_transfer, color_range, chroma_location as ffprobe names them; None where the field is
+    absent, ``unknown`` or ``unspecified``."""
+    return probe_source(ffprobe, path)[1]
+
+
+HDR_TRANSFERS = ("smpte2084", "arib-std-b67")                # PQ, HLG
+
+
+def output_colour(colour: Optional[dict], video_backend: str = "ffmpeg", ten_bit: bool = True):
+    """What an mp4 written from a source with these colour tags (probe_colour's dictionary; None: not read through ffprobe) is
+    written as -> (colour for FFmpegWriter or None = BT.709 as always, one warning line or None).  HDR / wide gamut: a PQ or HLG
+    transfer, BT.2020 primaries or the bt2020nc matrix.  Such a source leaves --video_backend ffmpeg --10bit as BT.2020
+    non-constant-luminance planes, tv range, chroma co-sited with even luma columns ("left": what a decoder assumes and
+    frameio_in.upsample_chroma inverts), tagged with the source's own primaries and transfer; anything else -- and bt2020c, which
+    no kernel here writes -- gets the BT.709 output with a warning."""
+    if colour is None:
+        return None, None
+    if colour.get("color_space") == "bt2020c":
+        return None, "Warning: the source is BT.2020 constant-luminance (bt2020c), which is not written; writing BT.709 video"
+    hdr = (colour.get("color_transfer") in HDR_TRANSFERS or colour.get("color_primaries") == "bt2020"
+           or colour.get("color_space") == "bt2020nc")
+    if not hdr:
+        return None, None
+    if video_backend != "ffmpeg":
+        return None, "Warning: the source is HDR / BT.2020 and the OpenCV writer has no colour tags; writing 8-bit BT.709 video (use --video_backend ffmpeg --10bit)"
+    if not ten_bit:
+        return None, "Warning: the source is HDR / BT.2020 and is written as 8-bit BT.709 video without --10bit (use --10bit to keep BT.2020)"
+    return dict(matrix="bt2020", range_="tv", siting="left", primaries=colour.get("color_primaries") or "bt2020",
+                trc=colour.get("color_transfer") or "bt709"), None
 
 
 # source pix_fmt -> (what ffmpeg is asked for: the planes as they are, packed format, range or None = from color_range)
@@ -476,20 +520,27 @@ def find_ffmpeg() -> str:
 class FFmpegWriter:
     """An ffmpeg subprocess fed raw frames through stdin: bgr24 -> libx264 / yuv420p, or (``ten_bit``) yuv420p10le -> libx265 /
     yuv420p10le -- the planes frameio.py computes from the fp32 frames, not 8-bit frames widened.  The stream is tagged BT.709,
-    tv range.  ``exe``: the executable (find_ffmpeg(), resolved before any GPU work; a test passes its own).  ``fps``: a float or a
+    tv range; with ``colour`` (output_colour's dictionary, ``ten_bit`` only) the planes are BT.2020 tv with left-sited chroma --
+    ``pack`` tells FrameSink so: the (matrix, range_, siting) of frameio.pack_yuv420p10, None: ``fmt`` as always -- and the stream is
+    tagged bt2020nc, the dictionary's primaries and transfer, tv range and that chroma location.  ``exe``: the executable (find_ffmpeg(), resolved before any GPU work; a test passes its own).  ``fps``: a float or a
     Fraction (passed on as num/den).  ``audio``: (source path, offset in seconds) -- the source as a second input whose audio
     stream, where it has one, is copied (no re-encoding: a codec the container refuses is ffmpeg's own message); None: the command
     without it, as it always was."""
     alpha = False
 
-    def __init__(self, exe: str, path: str, fps, ten_bit: bool = False, audio=None):
+    def __init__(self, exe: str, path: str, fps, ten_bit: bool = False, audio=None, colour=None):
         self.exe, self.path, self.fps, self.ten_bit, self.audio = exe, path, fps, ten_bit, audio
         self.fmt = "yuv420p10" if ten_bit else "bgr8"
+        self.colour = colour if ten_bit else None
+        self.pack = (self.colour["matrix"], self.colour["range_"], self.colour["siting"]) if self.colour else None
         self.proc, self.errlog = None, None
 
     def command(self, height, width):
         raw, codec, pix = ("yuv420p10le", "libx265", "yuv420p10le") if self.ten_bit else ("bgr24", "libx264", "yuv420p")
         tags = ["-colorspace", "bt709", "-color_primaries", "bt709", "-color_trc", "bt709", "-color_range", "tv"]
+        if self.colour:
+            tags = ["-colorspace", "bt2020nc", "-color_primaries", self.colour["primaries"], "-color_trc", self.colour["trc"],
+                    "-color_range", self.colour["range_"], "-chroma_sample_location", self.colour["siting"]]
         # 8 bits: ffmpeg converts bgr24 itself, and its default RGB -> YUV matrix is BT.601 whatever the output is tagged with:
         # the scale filter is told the matrix and range the tags then state
         convert = [] if self.ten_bit else ["-vf", "scale=out_color_matrix=bt709:out_range=tv"]
@@ -553,7 +604,8 @@ class TensorWriter:
 
 
 class FrameSink:
-    """Frames -> writer.  ``put(frames)`` narrows a chunk to the writer's format where the frames live (``ops.pack_frames`` on the
+    """Frames -> writer.  ``put(frames)`` narrows a chunk to the writer's format -- or, for a writer whose ``pack`` attribute names
+    a (matrix, range_, siting), to those yuv420p10 planes (frameio.pack_yuv420p10) -- where the frames live (``ops.pack_frames`` on the
     device, ``ops`` being the resident runner's backend; frameio's torch statement for a backend without one and for host frames),
     copies the result into one of TWO host buffers (pinned for device frames) and hands it to ONE writer thread through a queue of depth 2, so the encoder works while the next chunk computes.  The thread makes no GPU
     call.  An exception of the writer is raised in the caller's thread at the next put() or at close()."""
@@ -610,7 +662,11 @@ class FrameSink:
             frames = frames.float()
         if frames.is_cuda and self.ops is None:
             raise ValueError("FrameSink: frames on a GPU need the backend that narrows them there (ops=runner.dit.ops)")
-        packed = frameio.pack_frames(frames.contiguous(), self.writer.fmt, self.ops if frames.is_cuda else None)
+        how, ops = getattr(self.writer, "pack", None), self.ops if frames.is_cuda else None
+        if how is None:
+            packed = frameio.pack_frames(frames.contiguous(), self.writer.fmt, ops)
+        else:
+            packed = frameio.pack_yuv420p10(frames.contiguous(), *how, ops=ops)
         nbytes = packed.numel() * packed.element_size()
         slot = self.free.get()                                   # waits until the writer is done with one of the two buffers
         self._raise_pending()
@@ -634,13 +690,13 @@ class FrameSink:
 
 
 def open_writer(fmt: str, path: str, fps: float, single: bool = False, video_backend: str = "opencv", ten_bit: bool = False,
-                ffmpeg: Optional[str] = None, audio=None):
+                ffmpeg: Optional[str] = None, audio=None, colour=None):
     if fmt == "pt":
         return TensorWriter(path)
     if fmt == "png":
         return PngWriter(path, single)
     if video_backend == "ffmpeg":
-        return FFmpegWriter(ffmpeg or find_ffmpeg(), path, fps, ten_bit, audio)
+        return FFmpegWriter(ffmpeg or find_ffmpeg(), path, fps, ten_bit, audio, colour)
     return OpenCVWriter(path, fps)
 
 
@@ -793,12 +849,18 @@ def main(argv: Optional[List[str]] = None) -> int:
     writer_kw = dict(video_backend=args.video_backend, ten_bit=args.use_10bit and args.video_backend == "ffmpeg", ffmpeg=ffmpeg)
     for inp in jobs:                                   # the engines stay resident between jobs (interfaces.get_runner)
         fmt = fmt_of(inp)
-        info = probe_video(ffprobe, inp) if via_ffmpeg(inp) else None          # (before the engines: a file ffprobe refuses costs no model load)
+        info, colour = probe_source(ffprobe, inp) if via_ffmpeg(inp) else (None, None)      # (before the engines: a file ffprobe refuses costs no model load)
         eng = engines(args)
         rank, ops = eng[3], getattr(eng[0].dit, "ops", None)    # (the runner's backend also narrows the frames for the writers)
         job_kw = dict(writer_kw)
         if info is not None and info["has_audio"] and fmt == "mp4":            # (via_ffmpeg: the writer is FFmpegWriter)
             job_kw["audio"] = (inp, args.skip_first_frames / float(info["fps"]))
+        if fmt == "mp4":                               # an HDR source keeps its colour through --10bit; anything else: BT.709 as always
+            out_colour, warning = output_colour(colour, args.video_backend, writer_kw["ten_bit"])
+            if warning and rank == 0:
+                print(warning, file=sys.stderr)
+            if out_colour is not None:
+                job_kw["colour"] = out_colour
         source = lambda n: FrameSource(ffmpeg, inp, info, n, args.skip_first_frames, args.load_cap, ops, eng[0].dit.device)
         if args.chunk_size > 0 and ext_of(inp) not in IMAGE_EXT:
             # streaming: read, upscale, pack and write --chunk_size frames at a time
