@@ -5,7 +5,8 @@
 // (profiles/r1_halo_experiments.txt): that kernel is limited by the LDS port -- per 16 MFMAs a wave
 // reads 16 KiB of fragments and the DMA writes 2.6 KiB -- not by its schedule.  Here
 //   * a workgroup owns a 16 x 32 patch (512 voxels) x 128 couts, every wave 128 voxels x 64 couts
-//     (4 x 2 accumulators of v_mfma_f32_32x32x16_bf16): weight fragments are shared by 4 voxel rows;
+//     (4 x 2 blocks of 32 voxels x 32 couts, each four accumulators of v_mfma_f32_16x16x32_bf16): weight fragments are
+//     shared by 4 voxel rows;
 //   * the K slice per interval is 32 channels, so the halo image (18 x 34 pixels x 64 B = 38 KiB) still
 //     double-buffers next to an 8-deep ring of 8 KiB weight units: 1.5 KiB of DMA per wave-interval;
 //   * taps run dx-major and the halo-row fragments are kept across dy (tap (dy, dx) multiplies output
@@ -17,6 +18,12 @@
 // lanes of a ds_read_b128 group (rows distinct mod 16, same chunk) the pair (row & 3, (row >> 2) & 3)
 // is a bijection -> conflict-free for any halo column shift (halo rows are 34 apart, 34 = 2 mod 4 keeps it
 // a bijection per image row).
+// Matrix instruction: v_mfma_f32_16x16x32_bf16 in every mode (the whole 32-channel slice in ONE instruction per accumulator and
+// interval; lane l holds voxel / cout l & 15, chunk l >> 4 = channels 8 (l >> 4) .. + 7 of the slice).  A 32-voxel patch row is two
+// B fragments, 16 pixels = 1024 bytes apart -- (hx >> 2) & 3 is the same for both, so one address register and an offset -- and a
+// 32-cout block two A fragments; the accumulator of a fragment pair is voxel l & 15 x couts 4 (l >> 4) .. + 3.  The 32x32x16 form
+// it replaces measured 13 % (two workgroups per CU) / 3 % (one wave per SIMD) slower on this operand mix
+// (tools/ubench/operand_cost both; profiles/r7_operand_cost_mfma_shape.txt).
 // Pipeline as in the first kernel: one interval per tap, one raw s_barrier per interval, loads issued
 // CG_D intervals ahead with counted vmcnt, the two waves of a SIMD in opposite order.
 //
@@ -67,10 +74,25 @@ template <int N> SVR_DEVICE void cg_wait_vmcnt() { asm volatile("s_waitcnt vmcnt
 // MODE 3 helpers.  Fragment reads are issued from inline asm so that they can be in flight under MFMAs (hipcc's own schedule is
 // read -> s_waitcnt -> MFMA); hipcc does not count asm loads, so every consumer sits behind a counted wait that names the
 // destination registers "+v" (cdna_hip_programming.md 5.7 form (ii)) followed by a sched_barrier.
-template <int OFF> SVR_DEVICE void cg_rd2(bf16x8 (&r)[2], unsigned a0) {   // both k-steps of one halo row: chunk c and c ^ 2
-    const unsigned a1 = a0 ^ 32u;
-    asm volatile("ds_read_b128 %0, %2 offset:%4\n\tds_read_b128 %1, %3 offset:%4"
-                 : "=&v"(r[0]), "=&v"(r[1]) : "v"(a0), "v"(a1), "n"(OFF) : "memory");
+template <int OFF> SVR_DEVICE void cg_rd2(bf16x8 (&r)[2], unsigned a0) {   // both 16-voxel halves of one halo row
+    asm volatile("ds_read_b128 %0, %2 offset:%3\n\tds_read_b128 %1, %2 offset:%4"
+                 : "=&v"(r[0]), "=&v"(r[1]) : "v"(a0), "n"(OFF), "n"(OFF + 1024) : "memory");
+}
+// one 32-voxel x 32-cout block of an interval: [voxel half][cout half] accumulators, weights w[cout half], halo row r[voxel half]
+SVR_DEVICE void cg_mm4(f32x4 (&c)[2][2], const bf16x8 (&w)[2], const bf16x8 (&r)[2]) {
+    c[0][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], r[0], c[0][0], 0, 0, 0);
+    c[0][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], r[0], c[0][1], 0, 0, 0);
+    c[1][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[0], r[1], c[1][0], 0, 0, 0);
+    c[1][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[1], r[1], c[1][1], 0, 0, 0);
+}
+// The same block with the accumulators updated in place by inline asm: MODE 1's form.  Left to itself hipcc writes these MFMAs'
+// results to fresh registers there (64 accumulators renamed inside a 256-register budget) and spills accumulators in the K loop;
+// in the other modes the builtins compile to in-place updates already.
+SVR_DEVICE void cg_mm4_inplace(f32x4 (&c)[2][2], const bf16x8 (&w)[2], const bf16x8 (&r)[2]) {
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c[0][0]) : "v"(w[0]), "v"(r[0]));
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c[0][1]) : "v"(w[1]), "v"(r[0]));
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c[1][0]) : "v"(w[0]), "v"(r[1]));
+    asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+v"(c[1][1]) : "v"(w[1]), "v"(r[1]));
 }
 template <int N> SVR_DEVICE void cg_wait_rows(bf16x8 (&a)[2]) {
     asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(a[0]), "+v"(a[1]) : "n"(N));
@@ -110,7 +132,6 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
                   CG_BOFF = G::BOFF, NT = G::NT;
     constexpr int MTW = G::MTW, NTW = 2;                  // 32-voxel rows / 32-cout blocks per wave
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 
     const svr_conv_geom& g = a.conv;
     const int tid = threadIdx.x;
@@ -203,23 +224,23 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
         glds16(wbase + koff, wave_dst + CG_BOFF + slot * CG_BUNIT);
     };
 
-    // ---- fragment addressing: byte offset of k-step 0 for halo column shift dx / for the weight rows;
-    // k-step 1 is `^ 32` (chunk bits 4..5 never carry: buffer / slot bases are multiples of 64 B)
-    const int l31 = lane & 31, hi = lane >> 5;
+    // ---- fragment addressing: byte offset of the first 16-voxel half for halo column shift dx / of the first 16 weight rows of
+    // a 32-cout block; the second half is 16 pixels / rows = 1024 bytes further on with the same swizzle key
+    const int l15 = lane & 15, c4 = lane >> 4;
     int rd_a0[3], rd_b0;
 #pragma unroll
     for (int dx = 0; dx < 3; ++dx)
-        rd_a0[dx] = (wm * MTW * CG_HX + l31) * 64 + ((hi ^ (((dx + l31) >> 2) & 3)) << 4);
-    rd_b0 = CG_BOFF + (wn * 64 + l31) * 64 + ((hi ^ ((l31 >> 2) & 3)) << 4);
+        rd_a0[dx] = (wm * MTW * CG_HX + l15) * 64 + ((c4 ^ (((dx + l15) >> 2) & 3)) << 4);
+    rd_b0 = CG_BOFF + (wn * 64 + l15) * 64 + ((c4 ^ ((l15 >> 2) & 3)) << 4);
 
-    f32x16_t acc[MTW][NTW];
+    f32x4 acc[MTW][NTW][2][2];                            // [patch row][32-cout block][voxel half][cout half]
 #pragma unroll
     for (int y = 0; y < MTW; ++y)
 #pragma unroll
         for (int z = 0; z < NTW; ++z)
 #pragma unroll
-            for (int e = 0; e < 16; ++e) acc[y][z][e] = 0.f;
-    // halo-row fragments [k-step]; row r = wave row 0..5 (separate small arrays: a [6][2] array lands in scratch)
+            for (int e = 0; e < 16; ++e) acc[y][z][e >> 3][(e >> 2) & 1][e & 3] = 0.f;
+    // halo-row fragments [voxel half]; row r = wave row 0..5 (separate small arrays: a [6][2] array lands in scratch)
     bf16x8 ar0[2], ar1[2], ar2[2], ar3[2], ar4[2], ar5[2], wf[NTW][2];
     bf16x8 ar6[2], ar7[2], ar8[2], ar9[2];                // MODE 3: ten halo rows per column shift
 
@@ -232,9 +253,9 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
         int rb = rd_b0 + (k & (CG_NB - 1)) * CG_BUNIT;
         asm volatile("" : "+v"(ra), "+v"(rb));            // opaque: keeps hipcc from hoisting the address registers
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            const char* pa = smem + (ra ^ (ks << 5));
-            const char* pb = smem + (rb ^ (ks << 5));
+        for (int ks = 0; ks < 2; ++ks) {                  // voxel half / cout half
+            const char* pa = smem + ra + ks * 1024;
+            const char* pb = smem + rb + ks * 1024;
             if constexpr (DY == 0) {
                 ar0[ks] = *(const bf16x8*)(pa + (0 * CG_HX + DX) * 64);
                 ar1[ks] = *(const bf16x8*)(pa + (1 * CG_HX + DX) * 64);
@@ -250,15 +271,10 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
         }
     };
     auto mfma_core = [&](const bf16x8 (&r0)[2], const bf16x8 (&r1)[2], const bf16x8 (&r2)[2], const bf16x8 (&r3)[2]) {
-#define SVR_MM(KS, R, MT, NT) \
-        acc[MT][NT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[NT][KS], R[KS], acc[MT][NT], 0, 0, 0)
         __builtin_amdgcn_s_setprio(1);
-        SVR_MM(0, r0, 0, 0); SVR_MM(0, r0, 0, 1); SVR_MM(0, r1, 1, 0); SVR_MM(0, r1, 1, 1);
-        SVR_MM(0, r2, 2, 0); SVR_MM(0, r2, 2, 1); SVR_MM(0, r3, 3, 0); SVR_MM(0, r3, 3, 1);
-        SVR_MM(1, r0, 0, 0); SVR_MM(1, r0, 0, 1); SVR_MM(1, r1, 1, 0); SVR_MM(1, r1, 1, 1);
-        SVR_MM(1, r2, 2, 0); SVR_MM(1, r2, 2, 1); SVR_MM(1, r3, 3, 0); SVR_MM(1, r3, 3, 1);
+        cg_mm4(acc[0][0], wf[0], r0); cg_mm4(acc[0][1], wf[1], r0); cg_mm4(acc[1][0], wf[0], r1); cg_mm4(acc[1][1], wf[1], r1);
+        cg_mm4(acc[2][0], wf[0], r2); cg_mm4(acc[2][1], wf[1], r2); cg_mm4(acc[3][0], wf[0], r3); cg_mm4(acc[3][1], wf[1], r3);
         __builtin_amdgcn_s_setprio(0);
-#undef SVR_MM
     };
     auto mfmas = [&](auto jc) {
         constexpr int DY = decltype(jc)::value % 3;       // output row mt x halo row mt + dy
@@ -270,7 +286,7 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
     if constexpr (THIN) {
         // ---- thin input (Cin = 4: RGB padded; encoder conv_in): the whole K = kt * 9 * 4 <= 128 fits one im2col image of
         // the patch in LDS ([256 voxels][128 k], 272-byte rows); one thread gathers one voxel's taps (8 bytes each, the
-        // input is tiny and L2-resident), then 4 x 2 x (K / 16) MFMAs per wave with the weights read straight from
+        // input is tiny and L2-resident), then 4 x 2 x 4 x (K / 32) MFMAs per wave with the weights read straight from
         // their [N, 128] rows.  HBM-bound on the 128-channel output, which leaves through the shared epilogue below
         // (fused GroupNorm statistics included) -- replaces an im2col pass + a K = 128 GEMM.
         constexpr int TP = G::THIN_PITCH;
@@ -306,19 +322,23 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
                 *(uint4*)(rowp + tap * 8) = make_uint4(vv[tap].x, vv[tap].y, vv[tap + 1].x, vv[tap + 1].y);
         }
         __syncthreads();
-        const int nks = (taps * 4 + 15) >> 4;             // 16-wide k steps that hold real taps (7 for 3x3x3)
-        const char* wrow0 = (const char*)a.W + ((int64_t)(n0 + wn * 64 + l31) * a.K + hi * 8) * 2;
-        const char* arow0 = smem + ((wm * MTW) * 32 + l31) * TP + hi * 16;
+        const int nks = (taps * 4 + 31) >> 5;             // 32-wide k steps that hold real taps (4 for 3x3x3; the rows are
+                                                          // zero-filled up to K = 128)
+        const char* wrow0 = (const char*)a.W + ((int64_t)(n0 + wn * 64 + l15) * a.K + c4 * 8) * 2;
+        const char* arow0 = smem + ((wm * MTW) * 32 + l15) * TP + c4 * 16;
 #pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
+        for (int ks = 0; ks < 4; ++ks) {
             if (ks < nks) {
-                const bf16x8 b0 = *(const bf16x8*)(wrow0 + ks * 32);
-                const bf16x8 b1 = *(const bf16x8*)(wrow0 + (int64_t)32 * a.K * 2 + ks * 32);
+                bf16x8 b[NTW][2];
+#pragma unroll
+                for (int q = 0; q < 2 * NTW; ++q) b[q >> 1][q & 1] = *(const bf16x8*)(wrow0 + (int64_t)(16 * q) * a.K * 2 + ks * 64);
 #pragma unroll
                 for (int mt = 0; mt < MTW; ++mt) {
-                    const bf16x8 av = *(const bf16x8*)(arow0 + mt * 32 * TP + ks * 32);
-                    acc[mt][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b0, av, acc[mt][0], 0, 0, 0);
-                    acc[mt][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b1, av, acc[mt][1], 0, 0, 0);
+                    bf16x8 av[2];
+                    av[0] = *(const bf16x8*)(arow0 + mt * 32 * TP + ks * 64);
+                    av[1] = *(const bf16x8*)(arow0 + (mt * 32 + 16) * TP + ks * 64);
+                    cg_mm4(acc[mt][0], b[0], av);
+                    cg_mm4(acc[mt][1], b[1], av);
                 }
             }
         }
@@ -329,8 +349,10 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
         const int64_t nstride = (int64_t)P * 2048;                                          // bytes per 32-cout block
         const char* wp0 = (const char*)a.W_frag + (int64_t)(n0 / 32 + wn * 2) * nstride;   // wave-uniform (SGPR pair)
         const char* wp1 = wp0 + nstride;
-        const int voff = lane * 16;
-        bf16x8 w0[NTW][2], w1[NTW][2], w2[NTW][2];          // weights of intervals k = 0, 1, 2 (mod 3)
+        // the fragment-ordered unit of a 32-cout block and interval is [chunk 4][cout 32][16 B] (svr_conv_pack_frag): lane l takes
+        // cout l & 15 (+ 16: the second load, 256 bytes on) of chunk l >> 4 -- four 256-byte runs per wave instruction
+        const int voff = c4 * 512 + l15 * 16;
+        bf16x8 w0[NTW][2], w1[NTW][2], w2[NTW][2];          // weights of intervals k = 0, 1, 2 (mod 3): [32-cout block][cout half]
         // issued as inline asm: hipcc's own waitcnt insertion falls back to vmcnt(0) around the conditional LDS-DMA
         // issues, which would expose the full load latency; the waits below are counted by hand instead
         // (vmcnt retires in issue order)
@@ -353,9 +375,9 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
                 return;
             }
             asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(w[0][0]) : "v"(voff), "s"(p0) : "memory");
-            asm volatile("global_load_dwordx4 %0, %1, %2 offset:1024" : "=v"(w[0][1]) : "v"(voff), "s"(p0) : "memory");
+            asm volatile("global_load_dwordx4 %0, %1, %2 offset:256" : "=v"(w[0][1]) : "v"(voff), "s"(p0) : "memory");
             asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(w[1][0]) : "v"(voff), "s"(p1) : "memory");
-            asm volatile("global_load_dwordx4 %0, %1, %2 offset:1024" : "=v"(w[1][1]) : "v"(voff), "s"(p1) : "memory");
+            asm volatile("global_load_dwordx4 %0, %1, %2 offset:256" : "=v"(w[1][1]) : "v"(voff), "s"(p1) : "memory");
         };
         auto reads_a = [&](auto jc, int s) {
             constexpr int J = decltype(jc)::value;
@@ -364,8 +386,8 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
             int ra = rd_a0[DX] + (s & 1) * CG_ABUF;
             asm volatile("" : "+v"(ra));
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                const char* pa = smem + (ra ^ (ks << 5));
+            for (int ks = 0; ks < 2; ++ks) {              // voxel half
+                const char* pa = smem + ra + ks * 1024;
                 if constexpr (DY == 0) {
                     ar0[ks] = *(const bf16x8*)(pa + (0 * CG_HX + DX) * 64);
                     ar1[ks] = *(const bf16x8*)(pa + (1 * CG_HX + DX) * 64);
@@ -380,16 +402,13 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
         };
         auto mfma_w = [&](const bf16x8 (&w)[NTW][2], const bf16x8 (&r0)[2], const bf16x8 (&r1)[2],
                           const bf16x8 (&r2)[2], const bf16x8 (&r3)[2]) {
-#define SVR_MM(KS, R, MT, NT) \
-            acc[MT][NT] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w[NT][KS], R[KS], acc[MT][NT], 0, 0, 0)
-            SVR_MM(0, r0, 0, 0); SVR_MM(0, r0, 0, 1); SVR_MM(0, r1, 1, 0); SVR_MM(0, r1, 1, 1);
-            SVR_MM(0, r2, 2, 0); SVR_MM(0, r2, 2, 1); SVR_MM(0, r3, 3, 0); SVR_MM(0, r3, 3, 1);
-            SVR_MM(1, r0, 0, 0); SVR_MM(1, r0, 0, 1); SVR_MM(1, r1, 1, 0); SVR_MM(1, r1, 1, 1);
-            SVR_MM(1, r2, 2, 0); SVR_MM(1, r2, 2, 1); SVR_MM(1, r3, 3, 0); SVR_MM(1, r3, 3, 1);
-#undef SVR_MM
+            cg_mm4_inplace(acc[0][0], w[0], r0); cg_mm4_inplace(acc[0][1], w[1], r0);
+            cg_mm4_inplace(acc[1][0], w[0], r1); cg_mm4_inplace(acc[1][1], w[1], r1);
+            cg_mm4_inplace(acc[2][0], w[0], r2); cg_mm4_inplace(acc[2][1], w[1], r2);
+            cg_mm4_inplace(acc[3][0], w[0], r3); cg_mm4_inplace(acc[3][1], w[1], r3);
         };
         if constexpr (W8) {
-        // ---- MODE 3: 8 patch rows x 64 couts per wave (16 accumulators = 256 registers), ONE wave per SIMD.
+        // ---- MODE 3: 8 patch rows x 64 couts per wave (64 accumulators of four = 256 registers), ONE wave per SIMD.
         // Why: the kernel is bound by the power-managed clock, not by issue slots (profiles/r2_conv_experiments.txt: half the
         // resident waves or a stall-free schedule change nothing), and tools/ubench/operand_cost prices the operand paths of
         // the 4-row kernel at 24 % of a bare MFMA loop -- weight fragments from L1 7 %, fragment reads from LDS 5 %, halo
@@ -419,11 +438,9 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
         // the loop -- the counted waits that would then be wrong are dropped with them)
         constexpr bool ABL_NO_DMA = (DBG & 16) != 0, ABL_NO_W = (DBG & 1) != 0, ABL_NO_RD = (DBG & 64) != 0;
 #define SVR_RD(ROW, R, DXV, BUFOFF) do { if constexpr (!ABL_NO_RD) cg_rd2<((R) * CG_HX + (DXV)) * 64>(ROW, fa[DXV] + (BUFOFF)); } while (0)
-#define SVR_MM(W, KS, ROW, MT, NTI) \
-        acc[MT][NTI] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(W[NTI][KS], ROW[KS], acc[MT][NTI], 0, 0, 0)
+        // a quarter burst: two patch rows x two 32-cout blocks = 16 matrix instructions
 #define SVR_MM8(W, RA, MA, RB, MB) \
-        SVR_MM(W, 0, RA, MA, 0); SVR_MM(W, 0, RA, MA, 1); SVR_MM(W, 0, RB, MB, 0); SVR_MM(W, 0, RB, MB, 1); \
-        SVR_MM(W, 1, RA, MA, 0); SVR_MM(W, 1, RA, MA, 1); SVR_MM(W, 1, RB, MB, 0); SVR_MM(W, 1, RB, MB, 1)
+        cg_mm4(acc[MA][0], W[0], RA); cg_mm4(acc[MA][1], W[1], RA); cg_mm4(acc[MB][0], W[0], RB); cg_mm4(acc[MB][1], W[1], RB)
         // (The last A step runs the same code: its "next halo" pieces stage the zero page into the idle buffer and its
         // look-ahead reads fetch those zeros -- one code path keeps every vmcnt count a compile-time constant, and a peeled
         // copy made hipcc shuffle the 256 accumulators between register files at its entry.)
@@ -523,7 +540,8 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
 #pragma unroll
             for (int y = 0; y < MTW; ++y)
 #pragma unroll
-                for (int z = 0; z < NTW; ++z) asm volatile("" : "+a"(acc[y][z]));
+                for (int z = 0; z < NTW; ++z)
+                    asm volatile("" : "+a"(acc[y][z][0][0]), "+a"(acc[y][z][0][1]), "+a"(acc[y][z][1][0]), "+a"(acc[y][z][1][1]));
             cg_wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             __builtin_amdgcn_sched_barrier(0);
@@ -553,7 +571,6 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
 #undef SVR_RD
-#undef SVR_MM
 #undef SVR_MM8
         } else {
         bool a_prev3 = false;
@@ -630,6 +647,9 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
             interval3(std::integral_constant<int, 7>{}, s, fnext, w1, w0);
             interval3(std::integral_constant<int, 8>{}, s, fnext, w2, w1);
         }
+        // (the accumulators' last writers are inline asm, which hipcc's hazard pass does not look into: let the last MFMAs retire
+        // before compiler-scheduled code reads them)
+        asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");
         }
     } else {
     // ---- prologue: halo of step 0, weight units 0 .. CG_D-1
@@ -714,7 +734,6 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
     // tile is parked in LDS [voxels][132 floats] and written back row-contiguous, bias / residual added on the way out
     // (16 lanes cover one voxel's 128 couts; every global access is a full 16-byte lane / 256-byte row).
     constexpr int EP_PITCH = 528;                         // 128 floats + 16 B pad: conflict-free b128 writes
-    const int hi4 = hi * 4;
     // bias of the 8 couts this thread stores (every store iteration has the same chunk tid & 15): loaded now, used after
     // the first barrier -- the latency hides under the LDS write phase
     f32x4 bias_lo = {0.f, 0.f, 0.f, 0.f}, bias_hi = {0.f, 0.f, 0.f, 0.f};
@@ -776,16 +795,16 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
             // every wave parks two of its MTW rows per pass (all waves write in every pass): LDS slot row wm * 2 + j
             // holds patch row wm * MTW + 2 * pass + j
 #pragma unroll
+            // (an accumulator is four consecutive couts of one voxel: one 16-byte write each)
             for (int j = 0; j < 2; ++j) {
-                char* row = smem + ((wm * 2 + j) * 32 + l31) * EP_PITCH;
 #pragma unroll
-                for (int nt = 0; nt < NTW; ++nt) {
-                    const f32x16_t v = acc[2 * pass + j][nt];
+                for (int vh = 0; vh < 2; ++vh) {
+                    char* row = smem + ((wm * 2 + j) * 32 + vh * 16 + l15) * EP_PITCH;
 #pragma unroll
-                    for (int gq = 0; gq < 4; ++gq) {
-                        const f32x4 o = {v[4 * gq], v[4 * gq + 1], v[4 * gq + 2], v[4 * gq + 3]};
-                        *(f32x4*)(row + (wn * 64 + nt * 32 + 8 * gq + hi4) * 4) = o;
-                    }
+                    for (int nt = 0; nt < NTW; ++nt)
+#pragma unroll
+                        for (int ch = 0; ch < 2; ++ch)
+                            *(f32x4*)(row + (wn * 64 + nt * 32 + ch * 16 + c4 * 4) * 4) = acc[2 * pass + j][nt][vh][ch];
                 }
             }
             SVR_EP_STAMP(1 + 3 * pass)                     // LDS writes issued
@@ -1031,8 +1050,9 @@ static bool conv_halo2_eligible(const svr_gemm_args& a) {
 
 // ------------------------------------------------------------------------------------------------
 // Weight re-pack for the WREG variant: W [N, K = (dt, dy, dx, c)] -> [N / 32][k = (dt * Cin/32 + slice) * 9 + dx * 3 + dy]
-// [k-step 2][lane 64][8 bf16]; lane l of a v_mfma_f32_32x32x16_bf16 operand holds cout (l & 31), k (l >> 5) * 8 .. + 8.
-// One thread per 16-byte chunk; done once per checkpoint.
+// [k-step 2][lane 64][8 bf16] with cout (l & 31), k (l >> 5) * 8 .. + 8 -- the operand order of v_mfma_f32_32x32x16_bf16, which
+// conv_sub_kernel still issues; as bytes the 2-KiB unit is [channel chunk 4][cout 32][16 B], which is how conv_halo2_kernel's
+// 16x16x32 fragments read it.  One thread per 16-byte chunk; done once per checkpoint.
 // ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void conv_pack_frag_kernel(const bf16_t* __restrict__ W, uint4* __restrict__ out, int N, int K,
                                                              int kt, int Cin) {

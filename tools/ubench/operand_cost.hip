@@ -5,6 +5,9 @@
 //   NL  x 1 KiB ds_read_b128, consumed as MFMA B operands                                    (its halo-row fragments: 4 on average)
 //   ND3 x 1 KiB global_load_lds per THREE iterations from a cache-resident or an HBM-sized buffer   (its halo staging: 2 per 3)
 // Loads are issued one iteration ahead (register double buffer), two workgroups of four waves per CU like the conv kernel.
+// MFMA shape switch (S16 / argv[1] = "16"): the same FLOPs, operand registers and traffic per iteration issued as 32
+// v_mfma_f32_16x16x32_bf16 into 32 four-register accumulators instead of 16 v_mfma_f32_32x32x16_bf16 into 8 of sixteen --
+// every (weight, row) operand pair still feeds two matrix instructions; "both" runs the conv kernels' mixes on either shape.
 // (measurement aid for DESIGN.md section 3.1; not part of the product)
 #include <hip/hip_runtime.h>
 #include <cstdio>
@@ -14,6 +17,7 @@
 #include <vector>
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(16))) float f32x16;
+typedef __attribute__((ext_vector_type(4))) float f32x4;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
 __device__ __forceinline__ void glds16(const void* g, void* l) {
@@ -34,8 +38,10 @@ __device__ __forceinline__ float silu(float x) { return x * __builtin_amdgcn_rcp
 // NG3 > 0: instead of LDS-DMA the halo chunk is loaded into registers (16 bytes per lane), normalised (x * a + b per channel),
 // SiLU'd, rounded to bf16 and written to LDS with ds_write_b128 one G-phase later -- what fusing GroupNorm-apply + SiLU into the
 // conv kernel's halo staging would add to a wave; the VALU work is interleaved with the MFMAs by sched_group_barrier.
-template <int NW, int NL, int ND3, int WPS, int NG3 = 0>
-__global__ __launch_bounds__(256, WPS) void loop(const uint4* __restrict__ wbuf, const uint4* __restrict__ hbuf, size_t hmask,
+template <int NW, int NL, int ND3, int WPS, int NG3 = 0, bool S16 = false>
+// (WPS = 1 is enforced by the LDS request alone: with a 512-register budget hipcc splits the accumulators over both register
+// files and copies them back and forth inside the loop -- 128 v_accvgpr moves per three iterations on 32x32x16, 256 on 16x16x32)
+__global__ __launch_bounds__(256, 2) void loop(const uint4* __restrict__ wbuf, const uint4* __restrict__ hbuf, size_t hmask,
                                                  float* __restrict__ out, int iters) {
     extern __shared__ __attribute__((aligned(16))) char smem[];          // 64 KiB: 16 KiB per wave
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -49,11 +55,18 @@ __global__ __launch_bounds__(256, WPS) void loop(const uint4* __restrict__ wbuf,
         w1[i] = w0[i]; w2[i] = w0[i];
         a[i] = *(const bf16x8*)(mine + i * 1024 + lane * 16);
     }
-    f32x16 acc[8];
+    // the same 128 accumulator registers either way
+    constexpr int NACC = S16 ? 32 : 8, NEL = S16 ? 4 : 16, NMM = S16 ? 32 : 16;
+    typedef typename std::conditional<S16, f32x4, f32x16>::type acc_t;
+    acc_t acc[NACC];
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < NACC; ++i)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) acc[i][e] = 0.f;
+        for (int e = 0; e < NEL; ++e) acc[i][e] = 0.f;
+    auto mm = [&](int j, bf16x8 (&wc)[4]) {
+        if constexpr (S16) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wc[j & 3], a[(j >> 2) & 3], acc[j], 0, 0, 0);
+        else acc[j & 7] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wc[j & 3], a[(j >> 2) & 3], acc[j & 7], 0, 0, 0);
+    };
     size_t hpos = ((size_t)blockIdx.x * 4 + wave) * 977 * 64 + lane;    // 16-byte units; every wave streams its own region
     const unsigned lds_mine = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)mine + lane * 16;
     const int voff = lane * 16;
@@ -107,15 +120,15 @@ __global__ __launch_bounds__(256, WPS) void loop(const uint4* __restrict__ wbuf,
             asm("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(o.w) : "v"(f[6]), "v"(f[7]));
             *(uint4*)(mine + 8192 + (it & 7) * 1024 + lane * 16) = o;
 #pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j & 7] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wc[j & 3], a[(j >> 2) & 3], acc[j & 7], 0, 0, 0);
+            for (int j = 0; j < NMM; ++j) mm(j, wc);
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);     // one MFMA
+                __builtin_amdgcn_sched_group_barrier(0x008, NMM / 16, 0);   // one MFMA (two of the short shape)
                 __builtin_amdgcn_sched_group_barrier(0x006, 5, 0);     // five VALU / SALU
             }
         } else {
 #pragma unroll
-            for (int j = 0; j < 16; ++j) acc[j & 7] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wc[j & 3], a[(j >> 2) & 3], acc[j & 7], 0, 0, 0);
+            for (int j = 0; j < NMM; ++j) mm(j, wc);
         }
         __builtin_amdgcn_sched_barrier(0);
     };
@@ -129,19 +142,19 @@ __global__ __launch_bounds__(256, WPS) void loop(const uint4* __restrict__ wbuf,
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(w2[0]), "+v"(w2[1]), "+v"(w2[2]), "+v"(w2[3]));
     float s = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
+    for (int i = 0; i < NACC; ++i)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) s += acc[i][e];
+        for (int e = 0; e < NEL; ++e) s += acc[i][e];
     out[blockIdx.x * 256 + threadIdx.x] = s;
 }
 
 static uint4* d_w; static uint4* d_h; static float* d_out;
 static hipEvent_t e0, e1;
 
-template <int NW, int NL, int ND3, int WPS, int NG3 = 0>
+template <int NW, int NL, int ND3, int WPS, int NG3 = 0, bool S16 = false>
 static void run(const char* label, size_t hmask) {
     const int blocks = 256 * 2 * 8, iters = 3000;
-    auto kern = loop<NW, NL, ND3, WPS, NG3>;
+    auto kern = loop<NW, NL, ND3, WPS, NG3, S16>;
     const int lds = WPS == 1 ? 100000 : 65536;
     hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     float best = 1e9f;
@@ -153,11 +166,21 @@ static void run(const char* label, size_t hmask) {
         if (rep > 0 && ms < best) best = ms;
     }
     const double fl = 16.0 * 2 * 32 * 32 * 16 * iters * (double)blocks * 4;
-    printf("%-64s NW=%d NL=%d ND=%d/3 NG=%d/3 wg/CU=%d  %8.2f ms  %6.0f TFLOP/s\n", label, NW, NL, ND3, NG3, WPS, best, fl / best / 1e9);
+    printf("%-64s %s NW=%d NL=%d ND=%d/3 NG=%d/3 wg/CU=%d  %8.2f ms  %6.0f TFLOP/s\n", label, S16 ? "16x16x32" : "32x32x16", NW, NL, ND3, NG3,
+           WPS, best, fl / best / 1e9);
     fflush(stdout);
 }
 
-int main() {
+// the mixes that reproduce the two register-streamed conv kernels, and the bare loop, on one shape
+template <bool S16> static void run_conv_mixes(size_t HBM, size_t L2) {
+    run<0, 0, 0, 2, 0, S16>("pure MFMA loop (random operands)", L2);
+    run<0, 0, 0, 1, 0, S16>("pure MFMA loop, one workgroup per CU", L2);
+    run<4, 4, 2, 2, 0, S16>("the conv kernel's mix: 4 W + 4 LDS + 2/3 DMA (HBM)", HBM);
+    run<2, 3, 2, 1, 0, S16>("8-row kernel's mix: 2 W + 3 LDS + 2/3 DMA (HBM), 1 wg/CU", HBM);
+}
+
+int main(int argc, char** argv) {
+    const char* mode = argc > 1 ? argv[1] : "32";      // "32" (the table of DESIGN.md 3.1) | "16" | "both" (conv mixes, alternating)
     const size_t hbytes = (size_t)2 << 30;
     std::vector<uint16_t> h(32 << 20);
     for (auto& v : h) { float f = (float)rand() / RAND_MAX * 2.f - 1.f; uint32_t u; memcpy(&u, &f, 4); v = u >> 16; }
@@ -166,6 +189,11 @@ int main() {
     for (size_t off = 0; off < hbytes; off += h.size() * 2) hipMemcpy((char*)d_h + off, h.data(), h.size() * 2, hipMemcpyHostToDevice);
     hipEventCreate(&e0); hipEventCreate(&e1);
     const size_t HBM = (hbytes / 16) - 1, L2 = ((size_t)4 << 20) / 16 - 1;
+    if (!strcmp(mode, "both")) {
+        for (int rep = 0; rep < 3; ++rep) { run_conv_mixes<false>(HBM, L2); run_conv_mixes<true>(HBM, L2); }
+        return 0;
+    }
+    if (!strcmp(mode, "16")) { run_conv_mixes<true>(HBM, L2); return 0; }
     run<0, 0, 0, 2>("pure MFMA loop (random operands)", L2);
     run<0, 0, 0, 1>("pure MFMA loop, one workgroup per CU", L2);
     run<4, 0, 0, 2>("+ 4 weight fragments from L1 (the conv kernel's)", L2);
