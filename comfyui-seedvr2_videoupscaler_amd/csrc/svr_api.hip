@@ -19,6 +19,7 @@
 #include "svr_frame_pack.hip"
 #include "svr_frame_pack_colour.hip"
 #include "svr_frame_unpack.hip"
+#include "svr_png.hip"
 #include "svr_gguf.hip"
 
 using namespace svr;
@@ -74,6 +75,7 @@ int svr_set_option(const char* key, int32_t value) {
     if (!strcmp(key, "conv_thinout4")) { g_conv_thinout4 = value; return 0; }
     if (!strcmp(key, "attn_impl")) { g_attn_impl = value; return 0; }
     if (!strcmp(key, "attn_variant")) { g_attn_variant = value; return 0; }
+    if (!strcmp(key, "png_passes")) { if (value < 1 || value > 3) return fail("svr_set_option: png_passes is 1, 2 or 3"); g_png_passes = value; return 0; }
     return fail("svr_set_option: unknown key");
 }
 
@@ -543,6 +545,69 @@ int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H,
     else { if (left) { SVR_PACK_COLOUR(SVR_STORE_BF16, true); } else { SVR_PACK_COLOUR(SVR_STORE_BF16, false); } }
 #undef SVR_PACK_COLOUR
     return check(hipGetLastError(), "svr_pack_yuv420p10");
+}
+
+// ---- PNG streams encoded on the device (svr_png.hip)
+static const char* png_geometry_refusal(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth) {
+    if (C != 3 && C != 4) return "C must be 3 or 4";
+    if (depth != 8 && depth != 16) return "depth must be 8 or 16";
+    if (T < 1 || H < 1 || W < 1) return "need T >= 1, H >= 1, W >= 1";
+    if (H > (1 << 24)) return "H must not exceed 2^24 rows";
+    if ((int64_t)W * (C * depth / 8) >= (1 << 24)) return "W must stay below 2^24 bytes per row";
+    if ((int64_t)T * H > 0x7FFFFFFFll) return "T * H must stay below 2^31 rows";
+    return nullptr;
+}
+
+int svr_png_encode_bytes(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes, int64_t* capacity) {
+    const char* why = png_geometry_refusal(T, H, W, C, depth);
+    if (why) { snprintf(g_err, sizeof(g_err), "svr_png_encode_bytes: %s", why); return -1; }
+    const PngLayout L = png_layout(T, H, W, C, depth);
+    if (scratch_bytes) *scratch_bytes = L.scratch_bytes;
+    if (capacity) *capacity = L.capacity;
+    return 0;
+}
+
+int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, void* scratch,
+                   int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const char* why = nullptr;
+    if (!frames) why = "frames is a null pointer";
+    else if (!scratch) why = "scratch is a null pointer";
+    else if (!out) why = "out is a null pointer";
+    else if (!sizes) why = "sizes is a null pointer";
+    else if (x_kind != SVR_STORE_BF16 && x_kind != SVR_STORE_FP32) why = "x_kind must be SVR_STORE_BF16 or SVR_STORE_FP32";
+    else if ((why = png_geometry_refusal(T, H, W, C, depth))) {}
+    else if ((uintptr_t)frames % (x_kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
+    else if ((uintptr_t)scratch % 16) why = "scratch is not aligned to 16 bytes";
+    else if ((uintptr_t)sizes % 8) why = "sizes is not aligned to 8 bytes";
+    if (why) { snprintf(g_err, sizeof(g_err), "svr_png_encode: %s", why); return -1; }
+    const PngLayout L = png_layout(T, H, W, C, depth);
+    if (scratch_bytes < L.scratch_bytes) {
+        snprintf(g_err, sizeof(g_err), "svr_png_encode: scratch_bytes is %lld, the geometry needs at least %lld", (long long)scratch_bytes, (long long)L.scratch_bytes);
+        return -1;
+    }
+    if (out_capacity < L.capacity) {
+        snprintf(g_err, sizeof(g_err), "svr_png_encode: out_capacity is %lld per frame, the geometry needs at least %lld", (long long)out_capacity, (long long)L.capacity);
+        return -1;
+    }
+    const hipStream_t s = (hipStream_t)stream;
+    unsigned char* base = (unsigned char*)scratch;
+    unsigned char* filt = base + L.filt_off;
+    uint32_t* table = (uint32_t*)(base + L.table_off);
+    uint32_t* meta = (uint32_t*)(base + L.meta_off);
+    int64_t* segoff = (int64_t*)(base + L.segoff_off);
+    const dim3 grid((unsigned)((int64_t)T * L.nseg)), block(256);
+#define SVR_PNG_FILTER(KIND, DEPTH, CH) hipLaunchKernelGGL((png_filter_kernel<KIND, DEPTH, CH>), grid, block, 0, s, frames, filt, table, meta, H, W, L.R, L.nseg)
+#define SVR_PNG_FILTER_KIND(KIND) \
+    if (depth == 8) { if (C == 3) SVR_PNG_FILTER(KIND, 8, 3); else SVR_PNG_FILTER(KIND, 8, 4); } \
+    else { if (C == 3) SVR_PNG_FILTER(KIND, 16, 3); else SVR_PNG_FILTER(KIND, 16, 4); }
+    if (x_kind == SVR_STORE_FP32) { SVR_PNG_FILTER_KIND(SVR_STORE_FP32) } else { SVR_PNG_FILTER_KIND(SVR_STORE_BF16) }
+#undef SVR_PNG_FILTER_KIND
+#undef SVR_PNG_FILTER
+    // (g_png_passes < 3, tools/png_encode_timing.py only: the launches up to that pass, to time them by difference)
+    if (g_png_passes >= 2) hipLaunchKernelGGL(png_scan_kernel, dim3((unsigned)T), block, 0, s, meta, segoff, (unsigned char*)out, out_capacity, sizes, H, L.stride, L.R, L.nseg);
+    if (g_png_passes >= 3) hipLaunchKernelGGL(png_pack_kernel, grid, block, 0, s, filt, table, segoff, (unsigned char*)out, out_capacity, H, L.stride, L.R, L.nseg);
+    return check(hipGetLastError(), "svr_png_encode");
 }
 
 // ---- packed input frames (svr_frame_unpack.hip)

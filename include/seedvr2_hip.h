@@ -55,6 +55,7 @@
  *                                              16-byte loads and stores where packed and out are 16-byte aligned (and, for the
  *                                              yuv420p formats, W % 16 == 0), element accesses otherwise
  *   svr_dequant_gguf                           blocks 32 (GGUF's own alignment), out 16; anything else is refused
+ *   svr_png_encode                             frames element alignment, scratch 16, sizes 8, out any (byte stores)
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -78,6 +79,8 @@ extern "C" {
  * widened to fp32 [T, H, W, C] on the device).  A new symbol only.
  * v9, additive: + svr_pack_yuv420p10() (yuv420p10 planes with a chosen matrix -- BT.709 / BT.601 / BT.2020 --, range and chroma
  * siting: what an HDR source is written with).  A new symbol only; svr_pack_frames and its bytes are untouched.
+ * v9, additive: + svr_png_encode() / svr_png_encode_bytes() (output frames encoded as PNG zlib streams, 8 or 16 bits, on the
+ * device).  New symbols only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -395,6 +398,24 @@ int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, in
 #define SVR_COLOUR_SITING_LEFT   1
 int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t matrix, int32_t range,
                        int32_t siting, void* out, int64_t out_bytes, void* stream);
+
+/* ---- PNG streams encoded on the device ------------------------------------------------------- */
+/* pngenc.py (the specification, byte for byte): frames [T, H, W, C] dense, fp32 or bf16 (x_kind SVR_STORE_FP32 / SVR_STORE_BF16),
+ * C = 3 or 4, depth 8 or 16 -> per frame ONE zlib stream, out + t * out_capacity, of sizes[t] bytes (int64 [T], on the device):
+ * samples q = rint(clamp(x, 0, 1) * 255 | 65535) (NaN -> 0; 16-bit samples big-endian), each row filtered with the PNG filter type
+ * 0..4 of least sum of (f < 128 ? f : 256 - f), a tie to the lowest type; segments of R = max(1, 65536 / stride) rows, stride =
+ * 1 + W * C * depth / 8, each ONE dynamic-Huffman deflate block of literals only (lengths by the two-queue construction, counts
+ * halved -- (c + 1) >> 1 -- while the tree is deeper than 15; 1106 header bits) followed by an empty stored block; 78 01 in front,
+ * 03 00 and the big-endian Adler-32 behind.  pngenc.png_file() frames a stream as a file on the host.
+ * svr_png_encode_bytes(): the scratch bytes a call needs and the capacity every frame's slot of `out` must have: 2 + 6 + the sum
+ * over the frame's segments of n filtered bytes each of 139 + ceil(15 (n + 1) / 8) + 5 (pngenc.frame_bound).
+ * svr_png_encode(): every argument is checked before the first launch (C, depth, T / H / W >= 1, H <= 2^24, W * bytes per pixel
+ * < 2^24, T * H < 2^31, scratch 16-byte and sizes 8-byte aligned, scratch_bytes and out_capacity at least what
+ * svr_png_encode_bytes() says).  Three launches on `stream`, no host synchronisation.  Bytes of a frame's slot past sizes[t] are
+ * not written.  Vector stores and LDS integer atomics only; the result does not depend on scheduling. */
+int svr_png_encode_bytes(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes, int64_t* capacity);
+int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, void* scratch,
+                   int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream);
 
 /* ---- packed input frames -------------------------------------------------------------------- */
 /* frameio_in.py (the specification, bit for bit), the inverse of svr_pack_frames: packed samples as a decoder emits them -> out

@@ -24,7 +24,10 @@ two parsers by ``ast``), so existing scripts keep working.  What the flags DO is
   * --video_backend ffmpeg also READS video through ffmpeg (FrameSource): ffprobe names the source's pixel format, an ffmpeg child
     emits the planes at their native depth, ONE reader thread fills two pinned host buffers while the previous chunk computes, and
     the packed bytes are widened to fp32 on the device (frameio_in.py / csrc/svr_frame_unpack.hip).  The source's audio stream is
-    copied into an mp4 the ffmpeg writer produces.
+    copied into an mp4 the ffmpeg writer produces;
+  * png output of frames on the device is encoded there (pngenc.py / csrc/svr_png.hip; the writer thread does CRCs and file I/O),
+    as 16-bit files where the source is deeper than 8 bits (output_depth: a video read through ffmpeg as rgb16 / yuv420p10, a
+    16-bit RGB / RGBA png still, which load_frames reads with its 16 bits), as 8-bit files otherwise.
 """
 import argparse
 import json
@@ -53,6 +56,23 @@ WHOLE_CLIP_READ_FRAMES = 8         # without --chunk_size, FrameSource's two hos
 def _itf():
     import importlib
     return importlib.import_module(f"{PKG}.interfaces")
+
+
+def _pngenc():
+    import importlib
+    return importlib.import_module(f"{PKG}.pngenc")
+
+
+def output_depth(inp: str, info: Optional[dict] = None) -> int:
+    """Bits per sample of the png files written for this input: 16 where the source is deeper than 8 bits -- a video read through
+    ffmpeg whose route is rgb16 / yuv420p10, a 16-bit RGB / RGBA png still --, 8 for everything else (.pt / .npy tensors, the
+    OpenCV reader, 8-bit stills)."""
+    if info is not None:
+        return 16 if route_input(info)[1] in ("rgb16", "yuv420p10") else 8
+    if os.path.splitext(inp)[1].lower() == ".png":
+        head = _pngenc().png_header(inp)
+        return 16 if head is not None and head[2] == 16 and head[3] in (2, 6) and head[4] == 0 else 8
+    return 8
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -139,9 +159,14 @@ def load_frames(path: str, skip: int = 0, cap: int = 0):
             frames = frames[None]
     elif ext in IMAGE_EXT:
         from PIL import Image
-        img = Image.open(path)
-        has_alpha = img.mode in ("RGBA", "LA", "PA") or "transparency" in img.info
-        frames = torch.from_numpy(np.asarray(img.convert("RGBA" if has_alpha else "RGB"), dtype=np.float32) / 255.0)[None]
+        deep = _pngenc().read_png16(path) if ext == ".png" else None
+        if deep is not None:                           # a 16-bit RGB / RGBA png keeps its 16 bits (PIL would reduce it to 8) and its alpha
+            import importlib
+            frames = importlib.import_module(f"{PKG}.frameio_in").unit(torch.from_numpy(deep.astype(np.int64)), 65535)[None]
+        else:
+            img = Image.open(path)
+            has_alpha = img.mode in ("RGBA", "LA", "PA") or "transparency" in img.info
+            frames = torch.from_numpy(np.asarray(img.convert("RGBA" if has_alpha else "RGB"), dtype=np.float32) / 255.0)[None]
     elif ext in VIDEO_EXT:
         try:
             import cv2  # type: ignore
@@ -466,13 +491,25 @@ class FrameSource:
 # ---------------------------------------------------------------------------------------------------------
 # Writers: host code only (no GPU call), fed packed frames (frameio.py) as numpy arrays by FrameSink's thread.  ``fmt`` names the
 # packed format a writer takes (None: the fp32 frames themselves), ``alpha`` whether it keeps a fourth channel.
+class EncodedFrames:
+    """What FrameSink hands a writer that takes streams: per frame the bytes of its zlib stream (views of a host buffer)."""
+
+    def __init__(self, streams, channels: int):
+        self.streams, self.channels = streams, channels
+
+
 class PngWriter:
     """rgb8 (RGBA for four channels): one file per frame, frame_%06d.png, the index continuing across chunks; ``single``: the one
-    frame of an image job goes to ``path`` itself."""
-    fmt, alpha = "rgb8", True
+    frame of an image job goes to ``path`` itself.  ``depth`` 8 or 16 bits per sample.  ``streams`` tells FrameSink that the writer
+    also takes frames already encoded where they live (pngenc.py / csrc/svr_png.hip): write_streams() frames each zlib stream as a
+    file -- chunk CRCs and file I/O, no deflate on this thread.  write() takes uint8 frames (through PIL, as always) or uint16
+    frames (16-bit files through pngenc.write_png)."""
+    fmt, alpha, streams = "rgb8", True, True
 
-    def __init__(self, path: str, single: bool = False):
-        self.path, self.single, self.index = path, single, 0
+    def __init__(self, path: str, single: bool = False, depth: int = 8):
+        if depth not in (8, 16):
+            raise ValueError(f"depth must be 8 or 16, got {depth}")
+        self.path, self.single, self.index, self.depth = path, single, 0, depth
 
     def write(self, arr, height, width):
         from PIL import Image
@@ -481,7 +518,25 @@ class PngWriter:
         else:
             os.makedirs(self.path, exist_ok=True)
         for a in arr:
-            Image.fromarray(a).save(self.path if self.single else os.path.join(self.path, f"frame_{self.index:06d}.png"))
+            target = self.path if self.single else os.path.join(self.path, f"frame_{self.index:06d}.png")
+            if a.dtype.itemsize == 2:
+                _pngenc().write_png(target, a)
+            else:
+                Image.fromarray(a).save(target)
+            self.index += 1
+
+    def write_streams(self, streams, height, width, channels):
+        pngenc = _pngenc()
+        if self.single:
+            os.makedirs(os.path.dirname(os.path.abspath(self.path)), exist_ok=True)
+        else:
+            os.makedirs(self.path, exist_ok=True)
+        for s in streams:
+            head, tail = pngenc.png_parts(s, width, height, channels, self.depth)
+            with open(self.path if self.single else os.path.join(self.path, f"frame_{self.index:06d}.png"), "wb") as f:
+                f.write(head)
+                f.write(s)
+                f.write(tail)
             self.index += 1
 
     def close(self):
@@ -608,7 +663,11 @@ class FrameSink:
     a (matrix, range_, siting), to those yuv420p10 planes (frameio.pack_yuv420p10) -- where the frames live (``ops.pack_frames`` on the
     device, ``ops`` being the resident runner's backend; frameio's torch statement for a backend without one and for host frames),
     copies the result into one of TWO host buffers (pinned for device frames) and hands it to ONE writer thread through a queue of depth 2, so the encoder works while the next chunk computes.  The thread makes no GPU
-    call.  An exception of the writer is raised in the caller's thread at the next put() or at close()."""
+    call.  An exception of the writer is raised in the caller's thread at the next put() or at close().
+    A writer whose ``streams`` attribute is true (PngWriter) and a backend with ``encode_png`` on the frames' device: the frames are
+    ENCODED there (pngenc.py / csrc/svr_png.hip, at the writer's ``depth``), only the bytes produced are copied to the host buffer
+    and the thread frames and writes them (EncodedFrames -> write_streams).  A writer of ``depth`` 16 without such a backend is
+    handed uint16 samples (frameio.codes(., 65535)); every other case is as above, byte for byte."""
 
     def __init__(self, writer, ops=None):
         self.writer, self.ops = writer, ops
@@ -631,7 +690,10 @@ class FrameSink:
             slot, arr, height, width = item
             try:
                 if self.error is None:                           # (after a failure: keep returning buffers, write nothing)
-                    self.writer.write(arr, height, width)
+                    if isinstance(arr, EncodedFrames):
+                        self.writer.write_streams(arr.streams, height, width, arr.channels)
+                    else:
+                        self.writer.write(arr, height, width)
             except BaseException as e:                           # noqa: BLE001 (handed to the caller's thread)
                 self.error = e
             finally:
@@ -662,6 +724,28 @@ class FrameSink:
             frames = frames.float()
         if frames.is_cuda and self.ops is None:
             raise ValueError("FrameSink: frames on a GPU need the backend that narrows them there (ops=runner.dit.ops)")
+        depth = getattr(self.writer, "depth", 8)
+        if getattr(self.writer, "streams", False) and hasattr(self.ops, "encode_png") and \
+                frames.device.type == torch.device(getattr(self.ops, "device", "cuda")).type:
+            # encoded where the frames live: only the bytes produced cross to the host, the writer thread frames and writes them
+            out, sizes = self.ops.encode_png(frames.contiguous(), depth)
+            sizes = [int(n) for n in sizes.cpu().tolist()]       # (returns when the streams are there)
+            nbytes = sum(sizes)
+            slot = self.free.get()
+            self._raise_pending()
+            if self.buffers[slot] is None or self.buffers[slot].numel() < nbytes:
+                self.buffers[slot] = torch.empty(nbytes, dtype=torch.uint8, pin_memory=out.is_cuda)
+            host, at, streams = self.buffers[slot], 0, []
+            for t, n in enumerate(sizes):
+                host[at:at + n].copy_(out[t, :n])
+                streams.append(host[at:at + n].numpy())
+                at += n
+            self.work.put((slot, EncodedFrames(streams, frames.shape[-1]), height, width))
+            return
+        if depth == 16:                                          # no encoder where the frames live: 16-bit samples to the host writer
+            q = frameio.codes(frames, 65535.0).to(torch.int32).cpu().numpy().astype("uint16")
+            self.work.put((None, q, height, width))
+            return
         how, ops = getattr(self.writer, "pack", None), self.ops if frames.is_cuda else None
         if how is None:
             packed = frameio.pack_frames(frames.contiguous(), self.writer.fmt, ops)
@@ -690,11 +774,11 @@ class FrameSink:
 
 
 def open_writer(fmt: str, path: str, fps: float, single: bool = False, video_backend: str = "opencv", ten_bit: bool = False,
-                ffmpeg: Optional[str] = None, audio=None, colour=None):
+                ffmpeg: Optional[str] = None, audio=None, colour=None, depth: int = 8):
     if fmt == "pt":
         return TensorWriter(path)
     if fmt == "png":
-        return PngWriter(path, single)
+        return PngWriter(path, single, depth)
     if video_backend == "ffmpeg":
         return FFmpegWriter(ffmpeg or find_ffmpeg(), path, fps, ten_bit, audio, colour)
     return OpenCVWriter(path, fps)
@@ -853,6 +937,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         eng = engines(args)
         rank, ops = eng[3], getattr(eng[0].dit, "ops", None)    # (the runner's backend also narrows the frames for the writers)
         job_kw = dict(writer_kw)
+        if fmt == "png":                               # a source deeper than 8 bits leaves as 16-bit files
+            job_kw["depth"] = output_depth(inp, info)
         if info is not None and info["has_audio"] and fmt == "mp4":            # (via_ffmpeg: the writer is FFmpegWriter)
             job_kw["audio"] = (inp, args.skip_first_frames / float(info["fps"]))
         if fmt == "mp4":                               # an HDR source keeps its colour through --10bit; anything else: BT.709 as always
