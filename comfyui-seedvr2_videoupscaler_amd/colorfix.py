@@ -14,8 +14,10 @@ upscaled frames.  Restated from src/utils/color_fix.py (results identical on the
   wavelet_adaptive_color_correction :772-856  wavelet base, HSV result blended in where content is oversaturated
                                                (sigmoid(5 (dS - 0.15)), gated by the wavelet result's own excess)
 
-All tensors are [B, C, H, W] in [-1, 1]; the work is HBM / sort bound (no MFMA), so it stays torch glue on
-the device.
+All tensors are [B, C, H, W] in [-1, 1]; the work is HBM / sort bound (no MFMA).  The functions below are torch and run on
+whatever device their inputs live on: they are the specification.  ``correct`` (at the end) is what the pipeline calls: on a
+HIP backend it hands the wavelet pyramid, the CIELAB conversions and AdaIN to csrc/svr_colorfix.hip (HipOps.wavelet_reconstruct /
+lab_planes / lab_merge / adain); the rank matching (torch's sort and scatter) and the HSV mode stay here.
 """
 import torch
 import torch.nn.functional as F
@@ -226,3 +228,53 @@ METHODS = {
     "wavelet": wavelet_reconstruction,
     "adain": adaptive_instance_normalization,
 }
+
+# ---- the device route (csrc/svr_colorfix.hip through HipOps): METHODS above stay the specification
+DEVICE_METHODS = ("wavelet", "lab", "adain", "wavelet_adaptive")
+_DEVICE_OPS = ("wavelet_reconstruct", "lab_planes", "lab_merge", "adain")
+
+
+def routes_to_device(content: torch.Tensor, style: torch.Tensor, method: str, ops=None) -> bool:
+    """True where ``correct`` hands the method to ``ops``' kernels: a method they serve, ops that offer them, and two cuda fp32
+    [T, 3, H, W] tensors of equal shape (bf16 frames of ``output_dtype=None``, CPU tensors, the torch double of the ops and a style
+    that still needs resizing all stay on METHODS)."""
+    return (method in DEVICE_METHODS and ops is not None and all(hasattr(ops, n) for n in _DEVICE_OPS)
+            and content.is_cuda and style.is_cuda and content.dtype == torch.float32 and style.dtype == torch.float32
+            and content.dim() == 4 and content.shape[1] == 3 and content.numel() > 0 and content.shape == style.shape)
+
+
+def _lab_on_device(content, style, ops, luminance_weight: float = 0.8):
+    """lab_color_transfer with the wavelet base and both colour-space conversions as kernels; the rank matching between them is
+    histogram_match (torch's sort and scatter) on the planes."""
+    t, _, h, w = content.shape
+    c_lab, s_lab = ops.lab_planes(ops.wavelet_reconstruct(content, style), style)
+    a = histogram_match(c_lab[1], s_lab[1])
+    b = histogram_match(c_lab[2], s_lab[2])
+    m_l = histogram_match(c_lab[0], s_lab[0]) if luminance_weight < 1.0 else None
+    return ops.lab_merge(c_lab[0], m_l, a, b, luminance_weight, (t, h, w))
+
+
+def _wavelet_adaptive_on_device(content, style, ops, threshold: float = 0.15, sharpness: float = 5.0):
+    """wavelet_adaptive_color_correction with its wavelet base from the kernel; the HSV half and the blend stay torch."""
+    base = ops.wavelet_reconstruct(content, style)
+    hsv = hsv_saturation_histogram_match(content, style)
+    s_sat = saturation_map(style)
+    w = torch.sigmoid(sharpness * (saturation_map(content) - s_sat - threshold))
+    w = (w * ((saturation_map(base) - s_sat) > threshold * 0.5).float()).clamp(0.0, 1.0)
+    return base * (1.0 - w) + hsv * w
+
+
+def correct(content: torch.Tensor, style: torch.Tensor, method: str, ops=None, impl: str = "auto") -> torch.Tensor:
+    """``METHODS[method](content, style)``, on ``ops``' kernels where ``routes_to_device`` says so (``impl="torch"``: never).  A
+    failing library call raises; nothing falls back."""
+    if impl not in ("auto", "torch"):
+        raise ValueError(f"impl must be 'auto' or 'torch', got {impl!r}")
+    if impl == "torch" or not routes_to_device(content, style, method, ops):
+        return METHODS[method](content, style)
+    if method == "wavelet":
+        return ops.wavelet_reconstruct(content, style)
+    if method == "adain":
+        return ops.adain(content, style, 1e-5)
+    if method == "lab":
+        return _lab_on_device(content, style, ops)
+    return _wavelet_adaptive_on_device(content, style, ops)

@@ -20,6 +20,7 @@
 #include "svr_frame_pack_colour.hip"
 #include "svr_frame_unpack.hip"
 #include "svr_png.hip"
+#include "svr_colorfix.hip"
 #include "svr_gguf.hip"
 
 using namespace svr;
@@ -609,6 +610,134 @@ int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int
     if (g_png_passes >= 3) hipLaunchKernelGGL(png_pack_kernel, grid, block, 0, s, filt, table, segoff, (unsigned char*)out, out_capacity, H, L.stride, L.R, L.nseg);
     return check(hipGetLastError(), "svr_png_encode");
 }
+
+// ---- colour correction (svr_colorfix.hip).  Every argument is checked here, before any launch.
+static const char* colorfix_strides(const int64_t* st, bool is_output, PixStrides& s) {
+    if (!st) return "is a null pointer";
+    for (int i = 0; i < 4; ++i)
+        if (st[i] < (is_output ? 1 : 0)) return is_output ? "holds a stride below 1" : "holds a negative stride";
+    s = PixStrides{st[0], st[1], st[2], st[3]};
+    return nullptr;
+}
+static const char* colorfix_geometry(int32_t T, int32_t H, int32_t W, int32_t kind) {
+    if (kind != SVR_STORE_FP32) return "kind must be SVR_STORE_FP32";
+    if (T < 1 || T > 21845) return "need 1 <= T <= 21845";
+    if (H < 1 || W < 1) return "need H >= 1 and W >= 1";
+    // (a launch's threads per grid dimension are a 32-bit count: 2^24 workgroups of 256)
+    if ((int64_t)T * H * (((int64_t)W + COLORFIX_ROW_PIXELS - 1) / COLORFIX_ROW_PIXELS) >= (1ll << 24)) return "T * H * ceil(W / 256) must stay below 2^24";
+    if (((int64_t)H + WAVELET_TILE - 1) / WAVELET_TILE > 65535) return "H beyond 65535 tiles";
+    return nullptr;
+}
+#define SVR_COLORFIX_REFUSE(name, arg, why) do { snprintf(g_err, sizeof(g_err), "%s: %s%s%s", name, arg, *(arg) ? " " : "", why); return -1; } while (0)
+#define SVR_COLORFIX_PTR(name, p) do { if (!(p)) SVR_COLORFIX_REFUSE(name, #p, "is a null pointer"); } while (0)
+#define SVR_COLORFIX_STRIDES(name, st, is_output, dst) do { if (const char* w_ = colorfix_strides(st, is_output, dst)) SVR_COLORFIX_REFUSE(name, #st, w_); } while (0)
+#define SVR_COLORFIX_GEOMETRY(name) do { if (const char* w_ = colorfix_geometry(T, H, W, kind)) SVR_COLORFIX_REFUSE(name, "", w_); } while (0)
+
+int64_t svr_colorfix_workspace_bytes(int32_t T) {
+    if (T < 1 || T > 21845) return 0;
+    return (int64_t)2 * T * 3 * CHAN_STATS_PARTS * 2 * (int64_t)sizeof(double);
+}
+
+int svr_wavelet_reconstruct(const void* content, const int64_t* content_strides, const void* style, const int64_t* style_strides,
+                            void* out, const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    PixStrides cs, ss, os;
+    SVR_COLORFIX_PTR("svr_wavelet_reconstruct", content);
+    SVR_COLORFIX_PTR("svr_wavelet_reconstruct", style);
+    SVR_COLORFIX_PTR("svr_wavelet_reconstruct", out);
+    SVR_COLORFIX_STRIDES("svr_wavelet_reconstruct", content_strides, false, cs);
+    SVR_COLORFIX_STRIDES("svr_wavelet_reconstruct", style_strides, false, ss);
+    SVR_COLORFIX_STRIDES("svr_wavelet_reconstruct", out_strides, true, os);
+    SVR_COLORFIX_GEOMETRY("svr_wavelet_reconstruct");
+    WaveletRadii radii;
+    int halo = 0;
+    for (int i = 0; i < WAVELET_LEVELS; ++i) halo += radii.r[i] = std::min(1 << i, std::max(1, std::min(H, W) / 8));
+    static uint64_t lds_attr_done = 0;               // per device (svr_common.h)
+    if (int e = set_max_dynamic_lds((const void*)wavelet_kernel, WAVELET_LDS_BYTES, lds_attr_done)) return check(e, "svr_wavelet_reconstruct");
+    const dim3 grid(blocks_for(W, WAVELET_TILE), blocks_for(H, WAVELET_TILE), (unsigned)T * 3);
+    hipLaunchKernelGGL(wavelet_kernel, grid, dim3(WAVELET_THREADS), WAVELET_LDS_BYTES, (hipStream_t)stream, (const float*)content, cs,
+                       (const float*)style, ss, (float*)out, os, H, W, radii, halo);
+    return check(hipGetLastError(), "svr_wavelet_reconstruct");
+}
+
+int svr_lab_planes(const void* base, const int64_t* base_strides, const void* style, const int64_t* style_strides, void* c_lab,
+                   void* s_lab, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    PixStrides bs, ss;
+    SVR_COLORFIX_PTR("svr_lab_planes", base);
+    SVR_COLORFIX_PTR("svr_lab_planes", style);
+    SVR_COLORFIX_PTR("svr_lab_planes", c_lab);
+    SVR_COLORFIX_PTR("svr_lab_planes", s_lab);
+    SVR_COLORFIX_STRIDES("svr_lab_planes", base_strides, false, bs);
+    SVR_COLORFIX_STRIDES("svr_lab_planes", style_strides, false, ss);
+    SVR_COLORFIX_GEOMETRY("svr_lab_planes");
+    const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
+    const dim3 grid((unsigned)((int64_t)T * H * chunks), 2);
+    hipLaunchKernelGGL(lab_planes_kernel, grid, dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream, (const float*)base, bs,
+                       (const float*)style, ss, (float*)c_lab, (float*)s_lab, H, W, chunks, (int64_t)T * H * W);
+    return check(hipGetLastError(), "svr_lab_planes");
+}
+
+int svr_lab_merge(const void* c_L, const void* m_L, const void* m_a, const void* m_b, double luminance_weight, void* out,
+                  const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    PixStrides os;
+    const bool blend = luminance_weight < 1.0;
+    SVR_COLORFIX_PTR("svr_lab_merge", c_L);
+    if (blend) SVR_COLORFIX_PTR("svr_lab_merge", m_L);
+    SVR_COLORFIX_PTR("svr_lab_merge", m_a);
+    SVR_COLORFIX_PTR("svr_lab_merge", m_b);
+    SVR_COLORFIX_PTR("svr_lab_merge", out);
+    SVR_COLORFIX_STRIDES("svr_lab_merge", out_strides, true, os);
+    if (!(luminance_weight == luminance_weight)) SVR_COLORFIX_REFUSE("svr_lab_merge", "luminance_weight", "is not a number");
+    SVR_COLORFIX_GEOMETRY("svr_lab_merge");
+    const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
+    // (both factors rounded from fp64 once, as torch rounds the Python scalars luminance_weight and 1.0 - luminance_weight)
+    hipLaunchKernelGGL(lab_merge_kernel, dim3((unsigned)((int64_t)T * H * chunks)), dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream,
+                       (const float*)c_L, blend ? (const float*)m_L : nullptr, (const float*)m_a, (const float*)m_b,
+                       (float)luminance_weight, (float)(1.0 - luminance_weight), (float*)out, os, H, W, chunks);
+    return check(hipGetLastError(), "svr_lab_merge");
+}
+
+int svr_chan_stats(const void* content, const int64_t* content_strides, const void* style, const int64_t* style_strides, void* stats,
+                   int32_t T, int32_t H, int32_t W, int32_t kind, void* workspace, int64_t workspace_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    PixStrides cs, ss;
+    SVR_COLORFIX_PTR("svr_chan_stats", content);
+    SVR_COLORFIX_PTR("svr_chan_stats", style);
+    SVR_COLORFIX_PTR("svr_chan_stats", stats);
+    SVR_COLORFIX_PTR("svr_chan_stats", workspace);
+    SVR_COLORFIX_STRIDES("svr_chan_stats", content_strides, false, cs);
+    SVR_COLORFIX_STRIDES("svr_chan_stats", style_strides, false, ss);
+    SVR_COLORFIX_GEOMETRY("svr_chan_stats");
+    if ((uintptr_t)workspace % 8) SVR_COLORFIX_REFUSE("svr_chan_stats", "workspace", "is not aligned to 8 bytes");
+    if (workspace_bytes < svr_colorfix_workspace_bytes(T)) SVR_COLORFIX_REFUSE("svr_chan_stats", "workspace_bytes", "is below svr_colorfix_workspace_bytes(T)");
+    hipLaunchKernelGGL(chan_stats_kernel, dim3(CHAN_STATS_PARTS, (unsigned)T * 3, 2), dim3(256), 0, (hipStream_t)stream,
+                       (const float*)content, cs, (const float*)style, ss, H, W, (double*)workspace);
+    hipLaunchKernelGGL(chan_stats_finish_kernel, dim3(blocks_for((int64_t)2 * T * 3, 256)), dim3(256), 0, (hipStream_t)stream,
+                       (const double*)workspace, T * 3, (double)H * (double)W, (float*)stats);
+    return check(hipGetLastError(), "svr_chan_stats");
+}
+
+int svr_adain_apply(const void* content, const int64_t* content_strides, const void* stats, float eps, void* out,
+                    const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    PixStrides cs, os;
+    SVR_COLORFIX_PTR("svr_adain_apply", content);
+    SVR_COLORFIX_PTR("svr_adain_apply", stats);
+    SVR_COLORFIX_PTR("svr_adain_apply", out);
+    SVR_COLORFIX_STRIDES("svr_adain_apply", content_strides, false, cs);
+    SVR_COLORFIX_STRIDES("svr_adain_apply", out_strides, true, os);
+    SVR_COLORFIX_GEOMETRY("svr_adain_apply");
+    const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
+    hipLaunchKernelGGL(adain_apply_kernel, dim3((unsigned)((int64_t)T * H * chunks)), dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream,
+                       (const float*)content, cs, (const float*)stats, eps, (float*)out, os, H, W, chunks);
+    return check(hipGetLastError(), "svr_adain_apply");
+}
+#undef SVR_COLORFIX_GEOMETRY
+#undef SVR_COLORFIX_STRIDES
+#undef SVR_COLORFIX_PTR
+#undef SVR_COLORFIX_REFUSE
 
 // ---- packed input frames (svr_frame_unpack.hip)
 int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,

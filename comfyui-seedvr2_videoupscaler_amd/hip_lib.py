@@ -71,6 +71,7 @@ class GemmArgs(C.Structure):
 
 # name -> (restype, argtypes); must list every symbol declared in include/seedvr2_hip.h
 _vp, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
+_strides = C.POINTER(C.c_int64)                            # int64 [4] on the host: the (T, C, H, W) element strides of a pixel operand
 SYMBOLS = {
     "svr_gemm_bf16": (C.c_int, [C.POINTER(GemmArgs), _vp]),
     "svr_gemm_pack_frag": (C.c_int, [_vp, _vp, _i32, _i32, _vp]),
@@ -103,6 +104,12 @@ SYMBOLS = {
     "svr_pack_yuv420p10": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_png_encode_bytes": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "svr_png_encode": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "svr_colorfix_workspace_bytes": (C.c_int64, [_i32]),
+    "svr_wavelet_reconstruct": (C.c_int, [_vp, _strides, _vp, _strides, _vp, _strides, _i32, _i32, _i32, _i32, _vp]),
+    "svr_lab_planes": (C.c_int, [_vp, _strides, _vp, _strides, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "svr_lab_merge": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, _vp, _strides, _i32, _i32, _i32, _i32, _vp]),
+    "svr_chan_stats": (C.c_int, [_vp, _strides, _vp, _strides, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "svr_adain_apply": (C.c_int, [_vp, _strides, _vp, _f, _vp, _strides, _i32, _i32, _i32, _i32, _vp]),
     "svr_unpack_frames": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_dequant_gguf": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp]),
     "svr_set_option": (C.c_int, [C.c_char_p, _i32]),

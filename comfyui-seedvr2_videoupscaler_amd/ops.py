@@ -633,6 +633,106 @@ class HipOps:
                                               out.shape[1], _ptr(sizes), self._stream()), "svr_png_encode")
         return out, sizes
 
+    # ------------------------------------------------------------------ colour correction
+    # (colorfix.py is the specification; csrc/svr_colorfix.hip.)  Pixel operands are fp32 [T, 3, H, W]-SHAPED tensors of any
+    # strides -- the pipeline's channels-last frames and its sliced [C, T, H, W] reference are read where they lie.  A result
+    # allocated here is a dense [T, H, W, 3] buffer returned as its [T, 3, H, W] view.
+    def _pixels(self, t, name, shape=None, output=False):
+        if t.dim() != 4 or t.shape[1] != 3 or t.dtype != torch.float32 or (shape is not None and tuple(t.shape) != tuple(shape)):
+            want = "[T, 3, H, W]" if shape is None else str(tuple(shape))
+            raise ValueError(f"{name} must be fp32 {want}, got {t.dtype} {tuple(t.shape)}")
+        if t.device != self.device and not (t.device.type == "cuda" and t.device.index == (self.device.index or 0)):
+            raise ValueError(f"{name} must live on {self.device}, got {t.device}")
+        if t.numel() == 0:
+            raise ValueError(f"{name} must hold at least one pixel, got {tuple(t.shape)}")
+        if output and min(t.stride()) < 1:
+            raise ValueError(f"{name} must not be an expanded view (strides {t.stride()})")
+        return (C.c_int64 * 4)(*t.stride())
+
+    def _pixels_out(self, out, like, name, *inputs):
+        if out is None:
+            T, _, H, W = like.shape
+            out = torch.empty((T, H, W, 3), dtype=torch.float32, device=self.device).permute(0, 3, 1, 2)
+        strides = self._pixels(out, name, like.shape, output=True)
+        if any(out.untyped_storage().data_ptr() == x.untyped_storage().data_ptr() for x in inputs):
+            raise ValueError(f"{name} must not share its storage with an input")
+        return out, strides
+
+    def wavelet_reconstruct(self, content, style, out=None):
+        """clamp(high5(content) + low5(style), -1, 1): colorfix.wavelet_reconstruction bit for bit, in one launch."""
+        cs = self._pixels(content, "wavelet_reconstruct: content")
+        ss = self._pixels(style, "wavelet_reconstruct: style", content.shape)
+        out, os_ = self._pixels_out(out, content, "wavelet_reconstruct: out", content, style)
+        T, _, H, W = content.shape
+        hip_lib.check(self.lib.svr_wavelet_reconstruct(_ptr(content), cs, _ptr(style), ss, _ptr(out), os_, T, H, W, 1, self._stream()),
+                      "svr_wavelet_reconstruct")
+        return out
+
+    def lab_planes(self, base, style, c_lab=None, s_lab=None):
+        """[-1, 1] frames -> CIELAB planes (colorfix.rgb_to_lab of ((x + 1) * 0.5).clamp(0, 1)): two dense fp32 [3, T*H*W]."""
+        bs = self._pixels(base, "lab_planes: base")
+        ss = self._pixels(style, "lab_planes: style", base.shape)
+        T, _, H, W = base.shape
+        planes = []
+        for t, name in ((c_lab, "lab_planes: c_lab"), (s_lab, "lab_planes: s_lab")):
+            if t is None:
+                t = torch.empty((3, T * H * W), dtype=torch.float32, device=self.device)
+            self._chk(t, torch.float32, name)
+            if tuple(t.shape) != (3, T * H * W):
+                raise ValueError(f"{name} must be fp32 {(3, T * H * W)}, got {tuple(t.shape)}")
+            planes.append(t)
+        hip_lib.check(self.lib.svr_lab_planes(_ptr(base), bs, _ptr(style), ss, _ptr(planes[0]), _ptr(planes[1]), T, H, W, 1,
+                                              self._stream()), "svr_lab_planes")
+        return planes[0], planes[1]
+
+    def lab_merge(self, c_L, m_L, m_a, m_b, luminance_weight, shape, out=None):
+        """L = c_L * w + m_L * (1 - w) (w >= 1: c_L alone, ``m_L`` may be None), matched a and b -> colorfix.lab_to_rgb, clamped,
+        * 2 - 1.  The planes are dense fp32 [T*H*W]; ``shape`` = (T, H, W); -> [T, 3, H, W]."""
+        T, H, W = (int(v) for v in shape)
+        w = float(luminance_weight)
+        if w >= 1.0:
+            m_L = None
+        elif m_L is None:
+            raise ValueError("lab_merge: m_L is needed for luminance_weight < 1")
+        for t, name in ((c_L, "c_L"), (m_L, "m_L"), (m_a, "m_a"), (m_b, "m_b")):
+            if t is not None:
+                self._chk(t, torch.float32, f"lab_merge: {name}")
+                if t.numel() != T * H * W:
+                    raise ValueError(f"lab_merge: {name} must hold T * H * W = {T * H * W} values, got {tuple(t.shape)}")
+        like = torch.empty((T, 3, H, W), dtype=torch.float32, device="meta")
+        out, os_ = self._pixels_out(out, like, "lab_merge: out")
+        hip_lib.check(self.lib.svr_lab_merge(_ptr(c_L), _ptr(m_L), _ptr(m_a), _ptr(m_b), w, _ptr(out), os_, T, H, W, 1, self._stream()),
+                      "svr_lab_merge")
+        return out
+
+    def chan_stats(self, content, style, stats=None):
+        """-> fp32 [T, 3, 4]: mean and unbiased variance of content, then of style, per frame and channel (fp64 sums, fixed order)."""
+        cs = self._pixels(content, "chan_stats: content")
+        ss = self._pixels(style, "chan_stats: style", content.shape)
+        T, _, H, W = content.shape
+        if stats is None:
+            stats = torch.empty((T, 3, 4), dtype=torch.float32, device=self.device)
+        self._chk(stats, torch.float32, "chan_stats: stats")
+        if tuple(stats.shape) != (T, 3, 4):
+            raise ValueError(f"chan_stats: stats must be fp32 {(T, 3, 4)}, got {tuple(stats.shape)}")
+        nbytes = int(self.lib.svr_colorfix_workspace_bytes(T))
+        if nbytes <= 0:
+            raise ValueError(f"chan_stats: at most 21845 frames per call, got {T}")
+        ws = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
+        hip_lib.check(self.lib.svr_chan_stats(_ptr(content), cs, _ptr(style), ss, _ptr(stats), T, H, W, 1, _ptr(ws), nbytes,
+                                              self._stream()), "svr_chan_stats")
+        return stats
+
+    def adain(self, content, style, eps=1e-5, out=None):
+        """colorfix.adaptive_instance_normalization: per frame and channel, content moved to the style's mean and deviation."""
+        stats = self.chan_stats(content, style)
+        cs = self._pixels(content, "adain: content")
+        out, os_ = self._pixels_out(out, content, "adain: out")
+        T, _, H, W = content.shape
+        hip_lib.check(self.lib.svr_adain_apply(_ptr(content), cs, _ptr(stats), float(eps), _ptr(out), os_, T, H, W, 1, self._stream()),
+                      "svr_adain_apply")
+        return out
+
     # ------------------------------------------------------------------ packed input frames
     def unpack_frames(self, packed, fmt, T, H, W, C, matrix="bt709", range_="tv", out=None):
         """Input frames widened on the device (frameio_in.py is the specification; csrc/svr_frame_unpack.hip): ``packed`` a dense

@@ -240,7 +240,7 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
             ref = ref[:sample.shape[0], :, :true_h, :true_w]
             if color_correction not in colorfix.METHODS:
                 raise ValueError(f"Unknown color correction method: {color_correction}")
-            sample = colorfix.METHODS[color_correction](sample, ref)
+            sample = colorfix.correct(sample, ref, color_correction, ops=getattr(runner.dit, "ops", None))
         final[w0:w1] = sample.permute(0, 2, 3, 1).clamp(-1, 1).mul(0.5).add(0.5).to(odt)
     if alpha_out is not None:
         final = torch.cat([final, alpha_out.unsqueeze(-1)], dim=-1)

@@ -56,6 +56,8 @@
  *                                              yuv420p formats, W % 16 == 0), element accesses otherwise
  *   svr_dequant_gguf                           blocks 32 (GGUF's own alignment), out 16; anything else is refused
  *   svr_png_encode                             frames element alignment, scratch 16, sizes 8, out any (byte stores)
+ *   svr_wavelet_reconstruct, svr_lab_*,        element accesses only: pixel operands by four element strides (input >= 0, output
+ *     svr_chan_stats, svr_adain_apply          >= 1), planes and stats dense fp32; svr_chan_stats' workspace 8
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -81,6 +83,8 @@ extern "C" {
  * siting: what an HDR source is written with).  A new symbol only; svr_pack_frames and its bytes are untouched.
  * v9, additive: + svr_png_encode() / svr_png_encode_bytes() (output frames encoded as PNG zlib streams, 8 or 16 bits, on the
  * device).  New symbols only.
+ * v9, additive: + svr_wavelet_reconstruct() / svr_lab_planes() / svr_lab_merge() / svr_chan_stats() / svr_adain_apply() and
+ * svr_colorfix_workspace_bytes() (colour correction after the decode: wavelet, LAB and AdaIN on the device).  New symbols only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -416,6 +420,39 @@ int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H,
 int svr_png_encode_bytes(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes, int64_t* capacity);
 int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, void* scratch,
                    int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream);
+
+/* ---- colour correction ------------------------------------------------------------------------ */
+/* colorfix.py (the specification; src/utils/color_fix.py).  Pixel operands are fp32 (kind = SVR_STORE_FP32, the only kind served)
+ * and indexed [T, 3, H, W]: element (t, c, y, x) lies at strides[0] * t + strides[1] * c + strides[2] * y + strides[3] * x ELEMENTS
+ * from the pointer (`*_strides`: int64 [4] on the host), so channels-last frames ({H*W*3, 1, W*3, 3}) and a slice of a [C, T, H, W]
+ * buffer are read where they lie.  Input strides are >= 0, output strides >= 1; an output's elements must not overlap and only
+ * its T * 3 * H * W addressed elements are written.  Every argument is checked before the first launch (a null pointer or stride
+ * array, a bad stride, kind, 1 <= T <= 21845, H >= 1, W >= 1, T * H * ceil(W / 256) < 2^24, a short workspace) and
+ * svr_last_error() names it.  All launches go to `stream`, none synchronises with the host; plain vector stores, no atomics: the
+ * same bits on every run.
+ * svr_wavelet_reconstruct(): out = clamp(high5(content) + low5(style), -1, 1), colorfix.wavelet_reconstruction BIT FOR BIT: five
+ *   levels, level i with radius min(2^i, max(1, min(H, W) / 8)), each blur (x[y - r] + x[y + r]) * 0.25 + 0.5 * x[y] down the
+ *   rows, then the same along them, indices clamped to the image; high = (high + image) - low from zero.  One launch.
+ * svr_lab_planes(): base, style in [-1, 1] -> ((x + 1) * 0.5) clamped to [0, 1] -> CIELAB (D65) as colorfix.rgb_to_lab orders it
+ *   -> c_lab, s_lab: dense planar fp32 [3, T*H*W] (L, a, b).  One launch.
+ * svr_lab_merge(): c_L, m_L, m_a, m_b dense fp32 [T*H*W]; L = c_L * w + m_L * (1 - w) with w = luminance_weight (both factors
+ *   rounded to fp32 from fp64); for w >= 1, L = c_L and m_L is not read (may be NULL); colorfix.lab_to_rgb, clamped to [0, 1],
+ *   * 2 - 1 -> out.  One launch.
+ * svr_chan_stats(): stats fp32 [T, 3, 4] = {mean, unbiased variance} of content, then of style, per frame and channel; fp64 sums in
+ *   a fixed order.  workspace: svr_colorfix_workspace_bytes(T) bytes of device memory, 8-byte aligned.  Two launches.
+ * svr_adain_apply(): out = (content - mean_c) / sqrt(var_c + eps) * sqrt(var_s + eps) + mean_s with svr_chan_stats()'s stats.
+ *   One launch. */
+int64_t svr_colorfix_workspace_bytes(int32_t T);
+int svr_wavelet_reconstruct(const void* content, const int64_t* content_strides, const void* style, const int64_t* style_strides,
+                            void* out, const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream);
+int svr_lab_planes(const void* base, const int64_t* base_strides, const void* style, const int64_t* style_strides, void* c_lab,
+                   void* s_lab, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream);
+int svr_lab_merge(const void* c_L, const void* m_L, const void* m_a, const void* m_b, double luminance_weight, void* out,
+                  const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream);
+int svr_chan_stats(const void* content, const int64_t* content_strides, const void* style, const int64_t* style_strides, void* stats,
+                   int32_t T, int32_t H, int32_t W, int32_t kind, void* workspace, int64_t workspace_bytes, void* stream);
+int svr_adain_apply(const void* content, const int64_t* content_strides, const void* stats, float eps, void* out,
+                    const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream);
 
 /* ---- packed input frames -------------------------------------------------------------------- */
 /* frameio_in.py (the specification, bit for bit), the inverse of svr_pack_frames: packed samples as a decoder emits them -> out
