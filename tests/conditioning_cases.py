@@ -4,7 +4,12 @@
   * offset_groups: GroupNorm inputs whose groups sit at mean / std = rho (the variance E[x^2] - mean^2 loses rho^2 of its digits);
   * scaled_rows: rows of a row-normalising kernel at the magnitudes the wide residual stream allows;
   * bias_sweep / act_sweep: fp32 values at which a store or a fast activation can go wrong (rounding ties, overflow, the
-    subnormal range of a format, exp2 saturating)."""
+    subnormal range of a format, exp2 saturating);
+  * attn_score_cases: (q, k, v) of one attention window whose SCORES are steered tile by tile -- growth of the running maximum
+    just under and just over the deferral threshold of the window kernel's online softmax, rows of one query block that disagree
+    about rescaling, weight on the keys the ragged last tile duplicates, exponents far from 0."""
+import math
+
 import torch
 
 from ops_reference import H16, H16_SCALE, EPI_BIAS_GELU, EPI_BIAS_SILU, _st
@@ -83,6 +88,92 @@ def act_sweep(device="cpu"):
     denormal range."""
     v = torch.tensor(ACT_ARGS, dtype=torch.float64, device=device).to(F32)
     return torch.cat([v, -v, v[:1], -v[:1]])
+
+
+# ------------------------------------------------------------------------------------------------ attention: steered score ranges
+LOG2E = 1.4426950408889634
+TEXT_ROWS = 58                          # the text rows that close every production window
+ATTN_SCORE_CASES = ("step_below", "step_above", "stairs", "rows_disagree", "one_row_votes", "ramp_down", "tail_pair", "flat_high",
+                    "flat_low", "hot_gauss", "text_tail")
+
+
+def attn_log2_scores(q, k, scale):
+    """fp64 scores of the stored values in log2 units: [L, L]"""
+    return (q.double() @ k.double().t()) * (scale * LOG2E)
+
+
+def attn_score_cases(L, D, kt, device="cpu", seed=0):
+    """name -> (q, k, v), bf16 [L, D], for one attention window with scale = 1 / sqrt(D) over ``kt``-key tiles (tile = key // kt).
+
+    The steered cases put the score into coordinate 0: q[:, 0] = a_i and k[:, 0] = g_j sqrt(D) / log2(e), so that pair (i, j) scores
+    a_i g_j in LOG2 units (the unit of the kernels' exponent and of the window kernel's deferral threshold); every other coordinate
+    of q and k is N(0, 0.05^2) (0.004 log2 units of score), v is N(0, 1): every key has a value row of its own.
+
+      step_below     a 1, g 5.75 [tile >= 1]      the maximum grows by just under 2^6 at tile 1 and stays: a deferred rescale, P up
+                                                  to 2^5.75 for the rest of the window
+      step_above     a 1, g 6.25 [tile >= 1]      just over 2^6: a rescale at tile 1
+      stairs         a 1, g 5.75 tile             deferred and forced tiles in turn (growth counts from the kept maximum, not from
+                                                  the previous tile)
+      rows_disagree  a +1 even / -1 odd rows, g 9 tile     half of a query block's rows force every rescale, the other half get
+                                                  alpha = 1 and vanishing P
+      one_row_votes  a 1 on rows 13 mod 32 else 0, g 30 [tile >= 2]     one row (one lane pair) decides the block's vote
+      ramp_down      a 1, g -20 tile              no rescale after tile 0, exponents down to -20 (tiles - 1)
+      tail_pair      a 1, g 12 at key L - 2, 10 at key L - 1, else 0    the weight sits on the key a ragged tile duplicates (and
+                                                  on its neighbour: duplicates of a ONE-hot key would change nothing)
+      flat_high / flat_low   a 1, g +-115         s c - m c cancels at a large magnitude; uniform softmax
+      hot_gauss      q, k ~ N(0, 4^2) in every coordinate     scores about +-100 log2 units, near one-hot, rescales at random rows
+      text_tail      q, k, v ~ N(0, 1), the last 58 rows of q and k times 6     the production pattern (L >= 64 only)
+
+    The premises the cases exist for are asserted here, on the fp64 scores of the STORED bf16 values (the rounding of k[:, 0]
+    included): step_below / step_above -- every row's (tile-1 maximum - tile-0 maximum) lies in (5.0, 5.9) / (6.1, 7.0); tail_pair
+    -- the last two keys hold more than 0.9 of every row's softmax mass (windows of more than 512 keys: the other L - 2 keys, at
+    weight 1 each, outweigh that by count -- there more than 0.9 of (2^12 + 2^10) / (2^12 + 2^10 + L - 2), the share the stated g
+    gives)."""
+    gen = torch.Generator().manual_seed(seed + 131 * L + D + kt)         # (drawn on the host: the same data on every device)
+    randn = lambda *s: torch.randn(*s, generator=gen)
+    scale = 1.0 / math.sqrt(D)
+    key = torch.arange(L)
+    tile = (key // kt).float()
+    one = torch.ones(L)
+    row = torch.arange(L)
+    tail = torch.zeros(L)
+    tail[L - 1] = 10.0
+    if L >= 2:
+        tail[L - 2] = 12.0
+    steered = {
+        "step_below": (one, 5.75 * (tile >= 1)),
+        "step_above": (one, 6.25 * (tile >= 1)),
+        "stairs": (one, 5.75 * tile),
+        "rows_disagree": (1.0 - 2.0 * (row % 2), 9.0 * tile),
+        "one_row_votes": ((row % 32 == 13).float(), 30.0 * (tile >= 2)),
+        "ramp_down": (one, -20.0 * tile),
+        "tail_pair": (one, tail),
+        "flat_high": (one, 115.0 * one),
+        "flat_low": (one, -115.0 * one),
+    }
+    cases = {}
+    for name, (a, g) in steered.items():
+        q, k = randn(L, D) * 0.05, randn(L, D) * 0.05
+        q[:, 0] = a
+        k[:, 0] = g * (math.sqrt(D) / LOG2E)
+        cases[name] = (q.to(torch.bfloat16), k.to(torch.bfloat16), randn(L, D).to(torch.bfloat16))
+    cases["hot_gauss"] = ((randn(L, D) * 4.0).to(torch.bfloat16), (randn(L, D) * 4.0).to(torch.bfloat16), randn(L, D).to(torch.bfloat16))
+    if L >= 64:
+        q, k = randn(L, D), randn(L, D)
+        q[L - TEXT_ROWS:] *= 6.0
+        k[L - TEXT_ROWS:] *= 6.0
+        cases["text_tail"] = (q.to(torch.bfloat16), k.to(torch.bfloat16), randn(L, D).to(torch.bfloat16))
+
+    if L > kt:
+        for name, lo, hi in (("step_below", 5.0, 5.9), ("step_above", 6.1, 7.0)):
+            s = attn_log2_scores(*cases[name][:2], scale)
+            growth = s[:, kt:min(2 * kt, L)].amax(dim=1) - s[:, :kt].amax(dim=1)
+            assert bool(((growth > lo) & (growth < hi)).all()), (name, float(growth.min()), float(growth.max()))
+    if L >= 2:
+        mass = torch.softmax(attn_log2_scores(*cases["tail_pair"][:2], scale) * math.log(2.0), dim=1)[:, L - 2:].sum(dim=1)
+        floor = 0.9 if L <= 512 else 0.9 * 5120.0 / (5120.0 + L - 2)
+        assert bool((mass > floor).all()), ("tail_pair", float(mass.min()), floor)
+    return {name: tuple(t.to(device) for t in qkv) for name, qkv in cases.items()}
 
 
 # ------------------------------------------------------------------------------------------------ zero-operand launches, one per kernel class

@@ -5,12 +5,15 @@ lane reads (ds_read_b128 / ds_read_b64_tr_b16), and how v_mfma_f32_32x32x16_bf16
 the 64 lanes.  This test restates exactly those formulas (same names as the kernel) in numpy on top of the documented
 instruction semantics (cdna_hip_programming.md section 2 "ds_read_b64_tr_b16", section 3 "Fragment layout") and checks
 that one (window, head) comes out as softmax(q k^T) v -- including a ragged last key tile, clamped query rows and the
-16-byte widened output store.  It cannot prove the hardware semantics, only that the kernel is consistent with them;
+16-byte widened output store.  The online softmax is the kernel's too: the rescale of O and l is DEFERRED while no row of the wave
+has grown by more than 2^AW_DEFER over the kept m_run (one vote per wave), and run_wave reports the decision of every tile.
+It cannot prove the hardware semantics, only that the kernel is consistent with them;
 the -m gpu tests do the rest.
 """
 import numpy as np
 
 KT, D, TILE = 64, 128, 64 * 128 * 2
+AW_DEFER = 6.0                                           # log2 units a row's maximum may grow over m_run before the block rescales
 
 
 def mfma_32x32x16(A, B, C):
@@ -42,8 +45,10 @@ def tr16_b64(lds, addr):
     return out
 
 
-def run_wave(q, k, v, L, q0, wave, scale, NW=4):
-    """q,k,v: [L, 128] float (bf16-representable not required).  Returns {qpos: out row} for this wave's valid queries."""
+def run_wave(q, k, v, L, q0, wave, scale, NW=4, return_decisions=False):
+    """q,k,v: [L, 128] float (bf16-representable not required).  Returns {qpos: out row} for this wave's valid queries; with
+    ``return_decisions`` also the wave's rescale decision of every key tile (True = O and l rescaled, False = deferred)."""
+    decisions = []
     nk = (L + KT - 1) // KT
     lds = np.zeros(4 * TILE // 2)                        # element (2-byte) addressed
     lanes = np.arange(64)
@@ -89,19 +94,25 @@ def run_wave(q, k, v, L, q0, wave, scale, NW=4):
                     sacc[kb][keyi >= L, r] = -np.inf
         mx = np.maximum(sacc[0].max(1), sacc[1].max(1))
         mx = np.maximum(mx, mx[lanes ^ 32])
-        m_new = np.maximum(m_run, mx)
-        alpha = np.exp2(m_run * c - m_new * c)
-        m_run = m_new
+        # deferred rescale: one decision for the wave (the kernel's __all vote over its 64 lanes); m_run moves only when it is taken
+        rescale = not bool(np.all((mx - m_run) * c <= AW_DEFER))     # (first tile: m_run = -inf, the difference is +inf)
+        decisions.append(rescale)
+        if rescale:
+            m_new = np.maximum(m_run, mx)
+            alpha = np.exp2((m_run - m_new) * c)
+            m_run = m_new
+            l_run = l_run * alpha
+            for m in range(4):
+                o[m] *= alpha[:, None]
+        mc = m_run * c
         pf = {}
         psum = np.zeros(64)
         for kb in range(2):
             for u in range(2):
-                p = np.exp2(sacc[kb][:, 8 * u:8 * u + 8] * c - (m_new * c)[:, None])
+                p = np.exp2(sacc[kb][:, 8 * u:8 * u + 8] * c - mc[:, None])
                 psum += p.sum(1)
                 pf[kb, u] = p
-        l_run = l_run * alpha + psum
-        for m in range(4):
-            o[m] *= alpha[:, None]
+        l_run = l_run + psum
         for kb in range(2):
             for u in range(2):
                 OFF = (2 * kb + u) * 4096
@@ -124,7 +135,7 @@ def run_wave(q, k, v, L, q0, wave, scale, NW=4):
                 if qpos[lane] < L:
                     d0 = 32 * m + 8 * rq + 8 * hi[lane]
                     rows.setdefault(int(qpos[lane]), np.full(128, np.nan))[d0:d0 + 8] = np.concatenate([a2[lane], b2[lane]])
-    return rows
+    return (rows, decisions) if return_decisions else rows
 
 
 import pytest
@@ -143,6 +154,35 @@ def test_attn_win_index_algebra(NW):
     for q0, wave in (((0, 0), (0, 3), (128, 0)) if NW == 4 else ((0, 0), (0, 3), (0, 4))):
         got.update(run_wave(q, k, v, L, q0, wave, scale, NW))
     assert set(got) == set(range(0, 32)) | set(range(96, 128)) | set(range(128, 150))
+    for r, row in got.items():
+        assert not np.isnan(row).any()
+        np.testing.assert_allclose(row, want[r], rtol=1e-9, atol=1e-9)
+
+
+@pytest.mark.parametrize("NW", [4, 8])
+@pytest.mark.parametrize("case,want_decisions", [("step_below", [True, False, False]), ("step_above", [True, True, False]),
+                                                 ("rows_disagree", [True, True, True])])
+def test_attn_win_deferred_rescale(case, want_decisions, NW):
+    """The deferred rescale on steered scores (conditioning_cases.attn_score_cases, L = 150: tiles of 64, 64 and 22 keys).  The maximum
+    grows by 5.75 log2 units at tile 1 and stays (deferred twice: P up to 2^5.75 against the kept m_run), by 6.25 (rescaled at tile
+    1, deferred at tile 2), or by 9 per tile on the even rows while it FALLS by 9 on the odd ones (the even rows force every
+    rescale; the odd rows get alpha = 1).  The wave's decisions are the expected ones and every row equals the fp64 softmax --
+    rising and falling rows alike, a full wave and the ragged one with clamped queries."""
+    import math
+    import torch
+    from conditioning_cases import attn_score_cases
+    L = 150
+    q, k, v = (t.double().numpy() for t in attn_score_cases(L, D, KT)[case])
+    scale = 1 / math.sqrt(D)
+    s = (q @ k.T) * scale
+    p = np.exp(s - s.max(1, keepdims=True))
+    want = (p / p.sum(1, keepdims=True)) @ v
+    got = {}
+    for q0, wave in (((0, 1), (128, 0)) if NW == 4 else ((0, 1), (0, 4))):
+        rows, decisions = run_wave(q, k, v, L, q0, wave, scale, NW, return_decisions=True)
+        assert decisions == want_decisions, (q0, wave, decisions)
+        got.update(rows)
+    assert set(got) == set(range(32, 64)) | set(range(128, 150))
     for r, row in got.items():
         assert not np.isnan(row).any()
         np.testing.assert_allclose(row, want[r], rtol=1e-9, atol=1e-9)

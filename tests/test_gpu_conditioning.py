@@ -8,17 +8,24 @@
      stated exactly here, swept over rounding ties, overflow, the subnormal range of h16 and the saturation points of the fast
      activations, on every kernel class (asserted through record_kernel_class).
   C. The row-normalising kernels and the row softmax at the magnitudes the wide residual stream allows.
+  D. Both window-attention kernels on STEERED scores (attn_score_cases): the running maximum growing by just under and just over
+     the 2^6 of the window kernel's deferred rescale, rows of one query block that disagree about rescaling, weight on the key the
+     ragged last tile duplicates, exponents down to -80 and scores of +-115 log2 units, the text rows' norm at the window's end --
+     at lengths on both sides of a key tile and of the row table, head_dim 128 and 512, against le.check_attn per element.
+     tests/test_local_error.py proves on the CPU that the correct algorithm passes these cases and a missing mask, a stale O and a
+     stale l fail them.
 
 Every tensor a svr_* entry point writes comes from tests/guarded_out.py: guard bytes around a payload poisoned with NaN (``init=``
 where the launch gets a view that leaves the buffer's last row out, or works in place)."""
+import functools
 import math
 
 import pytest
 import torch
 
 import local_error as le
-from conditioning_cases import (offset_groups, scaled_rows, bias_sweep, act_sweep, zero_operand_problem, ROW_KINDS, OPTION_DEFAULTS,
-                                STORE_KINDS, ZERO_OPERAND_CASES)
+from conditioning_cases import (offset_groups, scaled_rows, bias_sweep, act_sweep, zero_operand_problem, attn_score_cases, ROW_KINDS,
+                                OPTION_DEFAULTS, STORE_KINDS, ZERO_OPERAND_CASES, ATTN_SCORE_CASES)
 from conftest import sub
 from guarded_out import Pool, guarded
 from ops_reference import H16, H16_SCALE, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_RESID_GATE, EPI_SWIGLU, _ld, _st
@@ -537,3 +544,77 @@ def test_softmax_rows_wide_score_ranges(hip, cols):
     g.assert_guards("softmax_rows")
     le.check_softmax_rows(P[:6], S, scale, name=f"softmax_rows cols {cols}")
     assert torch.equal(P[2], P[3]) and float(P[4, -1]) == 1.0 and float(P[4, :-1].float().abs().max()) == 0.0
+
+
+# ================================================================== D. window attention on steered score ranges
+@pytest.fixture(params=[0, pytest.param(1, marks=pytest.mark.variants)], ids=["attn_win", "attn_gen1"])
+def attn_impl(request, hip):
+    """0 = the second-generation window kernel wherever it applies (head_dim 128, windows <= 2048 rows), 1 = the first kernel
+    everywhere (as in tests/test_gpu_kernels.py)."""
+    hip.set_option("attn_impl", request.param)
+    yield request.param
+    hip.set_option("attn_impl", 0)
+
+
+@functools.lru_cache(maxsize=None)
+def _score_cases(L, D):
+    return attn_score_cases(L, D, 64 if D == 128 else 32, "cuda")
+
+
+def _score_launch(hip, request, case, L, D, heads, attn_impl=None):
+    """One launch of two windows: the case, and the case with its key and value rows in reversed order (a rising profile falls, the
+    tail's weight moves to the head of the window).  Head 0 carries the case, a second head plain N(0, 1) data: state leaking between
+    (window, head) pairs of very different range shows.  seq_rows and out_rows are permutations (a real gather and scatter).
+    check_attn on every element (a non-finite one fails in it), three more launches bit-identical, guards and poison; under
+    -m variants the window kernel's build variants store the same bits."""
+    q, k, v = _score_cases(L, D)[case]
+    plain = lambda j: rnd(2 * L, D, seed=17 * j + L)
+    cols = [torch.cat([q, q]), torch.cat([k, k.flip(0)]), torch.cat([v, v.flip(0)])]
+    logical = torch.cat([torch.stack([c] + [plain(3 * j + h) for h in range(1, heads)], dim=1).reshape(2 * L, heads * D)
+                         for j, c in enumerate(cols)], dim=1)                       # [2 L, (q | k | v) x heads x D]
+    g = torch.Generator().manual_seed(L + D)
+    seq_rows = torch.randperm(2 * L, generator=g).to(torch.int32).cuda()
+    out_rows = torch.randperm(2 * L, generator=g).to(torch.int32).cuda()
+    qkv = torch.empty_like(logical)
+    qkv[seq_rows.long()] = logical
+    cu = torch.tensor([0, L, 2 * L], dtype=torch.int32, device="cuda")
+    scale = 1.0 / math.sqrt(D)
+    gout = Pool()
+    out = gout(2 * L, heads * D, dtype=BF16)
+    launch = lambda o: hip.attn_varlen(qkv, o, seq_rows, out_rows, cu, L, heads, D, scale)
+    launch(out)
+    for _ in range(3):
+        assert torch.equal(launch(gout.like(out)), out)
+    gout.check(f"attn_varlen {case}")
+    if attn_impl == 0 and D == 128 and "variants" in (request.config.getoption("-m") or ""):
+        for variant in (1, 3, 4):
+            hip.set_option("attn_variant", variant)
+            try:
+                other = launch(gout.like(out))
+            finally:
+                hip.set_option("attn_variant", 0)
+            assert torch.equal(other, out), variant
+            gout.check(f"attn_varlen {case} variant {variant}")
+    le.check_attn(out, qkv, seq_rows, out_rows, cu, heads, D, scale, name=f"attn_varlen {case} L {L} D {D}")
+
+
+@pytest.mark.parametrize("case", ATTN_SCORE_CASES)
+def test_attn_steered_scores(hip, request, attn_impl, case):
+    """D = 128, L = 259 (four full key tiles and one of 3 keys; two 128-query tiles and a ragged one): every case of
+    attn_score_cases, on both kernels."""
+    _score_launch(hip, request, case, 259, 128, 2, attn_impl)
+
+
+# 67: one full tile + 3 keys; 33: one ragged tile, the waves past the first two hold only clamped queries; 2048: the longest row
+# table, 32 tiles; 2049: one row more -- served by the first-generation kernel whatever attn_impl says
+@pytest.mark.parametrize("case,L", [(c, L) for L in (67, 33, 2048, 2049) for c in ("stairs", "tail_pair", "text_tail")
+                                    if c != "text_tail" or L >= 64])
+def test_attn_steered_scores_other_lengths(hip, request, attn_impl, case, L):
+    _score_launch(hip, request, case, L, 128, 2, attn_impl)
+
+
+@pytest.mark.parametrize("case,L", [(c, L) for L in (131, 35) for c in ATTN_SCORE_CASES if c != "text_tail" or L >= 64])
+def test_attn_steered_scores_head_dim_512(hip, request, case, L):
+    """The VAE form: one head of 512, the first-generation kernel's <512, 1, 32> instantiation (32-key tiles, 64-query blocks):
+    131 = four tiles + 3 keys, 35 = one tile + 3."""
+    _score_launch(hip, request, case, L, 512, 1)

@@ -4,14 +4,19 @@
     storage format -- stays inside every bound, for every op family, at the launch-geometry shapes of tests/test_gpu_side_kernels.py
     scaled to CPU size and at the small GEMM / conv / attention cases of tests/test_gpu_kernels.py.
   * Fault injection: a local fault put into a correct result fails the checker while the global metric the kernel tests used alone so
-    far (||got - want|| / ||want|| < 2.5e-3, 4e-3 for attention) still passes -- the gap this checker closes."""
+    far (||got - want|| / ||want|| < 2.5e-3, 4e-3 for attention) still passes -- the gap this checker closes.
+  * Attention on steered score ranges (conditioning_cases.attn_score_cases): the flash ALGORITHM of both kernels
+    (tests/attn_emulation.py: key tiles, clamped and masked tail, one rescale vote per query block, deferral) is inside the bound on
+    every case, and with the mask missing, O stale or l stale it is rejected on every case that can see the fault."""
+import functools
 import math
 
 import pytest
 import torch
 
 import local_error as le
-from conditioning_cases import offset_groups, scaled_rows, act_sweep, ROW_KINDS
+from attn_emulation import flash_emulation
+from conditioning_cases import offset_groups, scaled_rows, act_sweep, attn_score_cases, ROW_KINDS, ATTN_SCORE_CASES
 from conftest import sub, rel_err
 from ops_reference import TorchOps, EPI_BIAS, EPI_BIAS_GELU, EPI_BIAS_SILU, EPI_RESID_GATE, EPI_SWIGLU, H16, H16_SCALE, _ld, _st
 
@@ -159,6 +164,72 @@ def test_attention_is_inside_its_bounds(lens, heads, D):
     before = out.clone()
     ref.attn_varlen(qkv, out, seq_rows, out_rows, cu, max(lens), heads, D, 1.0 / math.sqrt(D))
     assert le.check_attn(out, qkv, seq_rows, out_rows, cu, heads, D, 1.0 / math.sqrt(D), before=before) <= 1.0
+
+
+# (kt, qblock, defer, D, L): the second-generation window kernel (one vote per 32-query wave, deferral 2^6), the first-generation
+# kernel (no deferral) at head_dim 128 and in its head_dim 512 instantiation (32-key tiles); then two more lengths of the first:
+# 32 tiles, and one full tile plus 3 keys
+ATTN_GEOMETRIES = {"win": (64, 32, 6.0, 128, 259), "gen1": (64, 128, None, 128, 259), "gen1_d512": (32, 64, None, 512, 131),
+                   "win_2048": (64, 32, 6.0, 128, 2048), "win_67": (64, 32, 6.0, 128, 67)}
+ATTN_SCORE_ITEMS = [(g, c) for g in ("win", "gen1", "gen1_d512") for c in ATTN_SCORE_CASES] + [("win_2048", "stairs"), ("win_67", "step_above")]
+STALE_VISIBLE = ("step_above", "stairs", "rows_disagree", "one_row_votes", "tail_pair", "hot_gauss", "text_tail")
+
+
+@functools.lru_cache(maxsize=None)
+def _score_cases(geometry):
+    kt, _, _, D, L = ATTN_GEOMETRIES[geometry]
+    return attn_score_cases(L, D, kt)
+
+
+@functools.lru_cache(maxsize=None)
+def score_problem(geometry, case):
+    """-> (q, k, v, scale, (want, bound, mask)): the fp64 reference of one case, computed once and shared by the tests below"""
+    _, _, _, D, L = ATTN_GEOMETRIES[geometry]
+    q, k, v = _score_cases(geometry)[case]
+    rows, cu, scale = torch.arange(L, dtype=torch.int32), torch.tensor([0, L], dtype=torch.int32), 1.0 / math.sqrt(D)
+    return q, k, v, scale, le.attn_reference(torch.cat([q, k, v], dim=1), torch.empty(L, D, dtype=BF16), rows, rows, cu, 1, D, scale)
+
+
+def emulate(geometry, case, fault=None, decisions=None):
+    kt, qblock, defer, _, _ = ATTN_GEOMETRIES[geometry]
+    q, k, v, scale, _ = score_problem(geometry, case)
+    return flash_emulation(q, k, v, scale, kt=kt, qblock=qblock, defer=defer, fault=fault, decisions=decisions)
+
+
+@pytest.mark.parametrize("geometry,case", ATTN_SCORE_ITEMS)
+def test_attention_algorithm_is_inside_its_bounds_on_steered_scores(geometry, case):
+    """The flash algorithm of both kernels (tests/attn_emulation.py) on the score-range cases of conditioning_cases.attn_score_cases:
+    inside attn_reference's bound on every element -- the bound itself, not a measured share of it.  The deferred and the forced
+    branch are both taken where the case says so (step_below: [rescale, defer, ...]; step_above: [rescale, rescale, defer, ...];
+    stairs: in turn)."""
+    decisions = []
+    out = emulate(geometry, case, decisions=decisions)
+    assert le.check(f"attention emulation {geometry} {case}", out, *score_problem(geometry, case)[4]) <= 1.0
+    if ATTN_GEOMETRIES[geometry][2] is not None:
+        took = ["rescale" if bool(d.all()) else "defer" if not bool(d.any()) else "mixed" for d in decisions]
+        want = {"step_below": ["rescale"] + ["defer"] * (len(took) - 1), "step_above": ["rescale", "rescale"] + ["defer"] * (len(took) - 2),
+                "stairs": ["rescale", "defer"] * (len(took) // 2) + ["rescale"] * (len(took) % 2), "rows_disagree": ["rescale"] * len(took)}
+        # (the first 8 tiles: bf16 moves g = 5.75 tile by up to 5.75 tile 2^-9, so from tile 11 on a step may measure more than 6)
+        if case in want:
+            assert took[:8] == want[case][:8], (case, took)
+
+
+@pytest.mark.parametrize("geometry,case", ATTN_SCORE_ITEMS)
+def test_attention_faults_are_rejected_on_steered_scores(geometry, case):
+    """Each way the online softmax can be broken fails the per-element check on the cases that can see it:
+      * the -inf mask of the ragged tile missing: every case but ramp_down (whose last tile weighs 2^-80), wherever L has a ragged tile;
+      * O, or l, not multiplied by alpha at a rescale: every case whose running maximum moves after tile 0 (a first-generation
+        geometry rescales on every tile, but with alpha = 1 on the flat cases).
+    At deferral 2^6, step_below with a stale O PASSES (no rescale after tile 0: the fault has nothing to act on) while step_above
+    fails: the two cases differ in the branch the block takes."""
+    kt, _, defer, _, L = ATTN_GEOMETRIES[geometry]
+    ref3 = score_problem(geometry, case)[4]
+    visible = {"nomask": case != "ramp_down" and L % kt != 0, "stale_o": case in STALE_VISIBLE, "stale_l": case in STALE_VISIBLE}
+    for fault, seen in visible.items():
+        if seen:
+            must_fail(lambda: le.check(f"{geometry} {case} {fault}", emulate(geometry, case, fault), *ref3))
+    if defer is not None and case == "step_below":
+        assert le.check(f"{geometry} step_below stale_o", emulate(geometry, case, "stale_o"), *ref3) <= 1.0
 
 
 @pytest.mark.parametrize("kind", STORES, ids=["bf16", "h16", "fp32"])
@@ -485,3 +556,17 @@ def test_fault_attention_row_without_its_last_key_tile():
     assert rel_err(out.float(), want32) < TOL_ATTN
     msg = must_fail(lambda: le.check_attn(out, qkv, rows, rows, cu, heads, D, scale))
     assert "in 1 rows" in msg and f"row {r} " in msg
+
+
+def test_fault_attention_ragged_tile_unmasked_in_one_query_block():
+    """hot_gauss (scores of +-100 log2 units, near one-hot rows), L = 259: ONE 32-query block -- one wave of the window kernel, rows
+    160 .. 191 -- computes its last tile without the -inf mask, so the 61 clamped copies of key 258 count.  Only a row that gives that
+    key some weight moves at all, and only a little: the global metric stays at 1.4e-3 of its 4e-3 while one row leaves its bound.
+    (With the fault in every block no steered case stays under the global limit: the smallest figure is 2e-2, hot_gauss.)"""
+    q, k, v, scale, ref3 = score_problem("win", "hot_gauss")
+    out, bad = emulate("win", "hot_gauss"), emulate("win", "hot_gauss", "nomask")
+    le.check("attention hot_gauss", out, *ref3)
+    out[160:192] = bad[160:192]
+    assert rel_err(out.float(), ref3[0]) < TOL_ATTN
+    msg = must_fail(lambda: le.check("attention hot_gauss, one block unmasked", out, *ref3))
+    assert "in 1 rows" in msg
