@@ -449,3 +449,118 @@ def unpatchify_euler_reference(pred, x_t, out_shape, out_dtype=torch.bfloat16):
     p = values(pred[:, :4 * C]).reshape(T, H // 2, W // 2, 2, 2, C).permute(0, 1, 3, 2, 4, 5).reshape(T, H, W, C)
     want = values(x_t) - p if x_t is not None else p
     return want, store_bound(want, U32 * want.abs(), out_dtype)
+
+
+# ------------------------------------------------------------------------------------------------ glue kernels of the engines
+def ada_combine_reference(emb, params, slots):
+    """out[v, i] = emb[6 i + slots[v]] + params[v, i] into fp32: ONE fp32 add of two bf16 values, and the fp32 store keeps the
+    sum as it is -- bound u32 |want|.  -> (want, bound) [n_vec, dim]."""
+    dim = params.shape[1]
+    want = values(emb).reshape(dim, 6)[:, slots.long()].t() + values(params)
+    return want, U32 * want.abs()
+
+
+def check_ada_combine(got, emb, params, slots, *, name="ada_combine"):
+    want, bound = ada_combine_reference(emb, params, slots)
+    return check(name, got, want, bound)
+
+
+def check_bits(name, got, want):
+    """Pure data movement (patchify, im2col_causal): ``got`` must hold the BITS of ``want`` (the tests/ops_reference.py result,
+    pad columns zero) -- a bound of zero on the bit patterns, so -0.0 is not 0.0 and a NaN payload is compared too.
+    -> 0.0; a failure names the first differing element."""
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{name}: {tuple(got.shape)} {got.dtype} against {tuple(want.shape)} {want.dtype}"
+    raw = {1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[got.element_size()]
+    diff = got.contiguous().view(raw) != want.contiguous().view(raw)
+    n_bad = int(diff.sum())
+    _record(name, float("inf") if n_bad else 0.0)
+    if n_bad:
+        flat = int(diff.reshape(-1).to(torch.uint8).argmax())
+        cols = want.shape[-1]
+        r, c = divmod(flat, cols)
+        raise AssertionError(f"{name}: {n_bad} of {diff.numel()} elements do not hold the reference's bits; first at row {_mods(r)}, "
+                             f"column {_mods(c)}: got {float(got.reshape(-1)[flat]):.9g}, want {float(want.reshape(-1)[flat]):.9g}")
+    return 0.0
+
+
+def patchify_reference(vid, out):
+    """The 2 x 2 patch rows of ``vid`` [T, H, W, C] in the leading 4 C columns, zeros in the pad columns: the tests/ops_reference.py
+    result in the storage dtype (compare with check_bits)."""
+    from ops_reference import TorchOps
+    return TorchOps(vid.device, vid.dtype).patchify(vid, torch.empty_like(out))
+
+
+def im2col_causal_reference(x, out, conv):
+    """The tap-major im2col rows of a causal conv (carried halo or replicated first frame in front, zero borders, zero pad
+    columns): the tests/ops_reference.py result in the storage dtype (compare with check_bits)."""
+    from ops_reference import TorchOps
+    return TorchOps(x.device, x.dtype).im2col_causal(x, torch.empty_like(out), conv)
+
+
+def blend_accumulate_reference(tile, acc_before, cnt_before, wy, wx, y0, x0):
+    """acc[:, y0:y0+h, x0:x0+w] += tile (wy wx) in fp32, cnt[y0:y0+h, x0:x0+w] += wy wx (the kernel: by its t == 0 threads only --
+    once per pixel, whatever T is).  Three fp32 roundings per element -- w = wy wx, tile w, the add -- so
+
+        |acc err| <= 2 u32 |tile w| + u32 |want|        |cnt err| <= 2 u32 |w| + u32 |want|     (the second rounding is absent for cnt)
+
+    mask = the tile's rectangle; everything outside keeps its bits.  -> ((want, bound, mask) of acc, (want, bound, mask) of cnt)."""
+    T, h, w, C = tile.shape
+    wgt = wy.to(F64)[:, None] * wx.to(F64)[None, :]
+    res = []
+    for before, add in ((acc_before, values(tile) * wgt[None, :, :, None]), (cnt_before, wgt)):
+        want = torch.full(before.shape, float("nan"), dtype=F64, device=before.device)
+        bound = torch.zeros(before.shape, dtype=F64, device=before.device)
+        mask = torch.zeros(before.shape, dtype=torch.bool, device=before.device)
+        rect = (Ellipsis, slice(y0, y0 + h), slice(x0, x0 + w)) if before.dim() == 2 else (slice(None), slice(y0, y0 + h), slice(x0, x0 + w))
+        want[rect] = before.to(F64)[rect] + add
+        bound[rect] = 2.0 * U32 * add.abs() + U32 * want[rect].abs()
+        mask[rect] = True
+        res.append((want, bound, mask))
+    return res[0], res[1]
+
+
+def check_blend_accumulate(acc, cnt, tile, acc_before, cnt_before, wy, wx, y0, x0, *, name="blend_accumulate"):
+    (wa, ba, ma), (wc, bc, mc) = blend_accumulate_reference(tile, acc_before, cnt_before, wy, wx, y0, x0)
+    return max(check(name + " acc", acc, wa, ba, ma, acc_before), check(name + " cnt", cnt.reshape(wc.shape), wc, bc, mc, cnt_before.reshape(wc.shape)))
+
+
+def _f32(v):
+    """a Python scalar as the C ABI receives it (a ``float`` argument)"""
+    return float(torch.tensor(v, dtype=torch.float32))
+
+
+def blend_finalize_reference(acc, cnt, c_take, scale=1.0, shift=0.0, out_dtype=torch.bfloat16):
+    """want = (acc[..., :c_take] / max(cnt, 1e-6) - shift) scale.  q = acc / cnt may be formed with a reciprocal (APPROX |q|: v_rcp_f32
+    and the multiply behind it); then the quotient, the subtraction and the product are rounded to fp32 -- three roundings, each
+    at most u32 of the magnitudes that met, which (|q| + |shift|) |scale| covers in either order of evaluation (and under
+    cancellation in q - shift):
+
+        |err| <= u_out (|want| + b) + b,      b = (APPROX + 3 u32) (|q| + |shift|) |scale|
+
+    -> (want, bound) [T, H, W, c_take]."""
+    scale, shift = _f32(scale), _f32(shift)
+    q = acc[..., :c_take].to(F64) / cnt.to(F64).clamp_min(_f32(1e-6)).reshape(1, acc.shape[1], acc.shape[2], 1)
+    want = (q - shift) * scale
+    return want, store_bound(want, (APPROX + 3.0 * U32) * (q.abs() + abs(shift)) * abs(scale), out_dtype)
+
+
+def check_blend_finalize(got, acc, cnt, scale=1.0, shift=0.0, *, name="blend_finalize"):
+    want, bound = blend_finalize_reference(acc, cnt, got.shape[-1], scale, shift, got.dtype)
+    return check(name, got.reshape(want.shape), want, bound)
+
+
+def affine_slice_reference(inp, c_out, scale=1.0, shift=0.0, out_dtype=torch.bfloat16):
+    """want = (inp[..., :c_out] - shift) scale: two fp32 roundings (the subtraction, the product), then the store:
+
+        |err| <= u_out (|want| + b) + b,      b = 2 u32 (|x| + |shift|) |scale|
+
+    -> (want, bound) [..., c_out]."""
+    scale, shift = _f32(scale), _f32(shift)
+    x = values(inp[..., :c_out])
+    want = (x - shift) * scale
+    return want, store_bound(want, 2.0 * U32 * (x.abs() + abs(shift)) * abs(scale), out_dtype)
+
+
+def check_affine_slice(got, inp, scale=1.0, shift=0.0, *, name="affine_slice"):
+    want, bound = affine_slice_reference(inp, got.shape[-1], scale, shift, got.dtype)
+    return check(name, got.reshape(want.shape), want, bound)

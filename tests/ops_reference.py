@@ -48,6 +48,22 @@ def conv_padded_input(A, conv, dtype=torch.float32):
     return F.pad(xin, (pw, pw_hi, ph, ph_hi))
 
 
+def conv_by_taps(xin, Wf, g, N):
+    """The conv of the padded input ``xin`` [1, Cin, T', H', W'] (conv_padded_input) as one matmul per tap, [M, N] in xin's dtype.
+    gemm_acc takes this route for the fp64 reference on a device: device libraries have fp64 GEMMs, not all have fp64 convs, and
+    a host conv of an engine-sized launch takes seconds.  The order of the additions is the only difference to F.conv3d."""
+    kt, kh, kw = g.k
+    st, sh, sw = g.stride
+    x5 = xin[0].permute(1, 2, 3, 0)                                        # [T', H', W', Cin]
+    w4 = Wf[:, :kt * kh * kw * g.Cin].reshape(N, kt * kh * kw, g.Cin)
+    acc = torch.zeros(g.To * g.Ho * g.Wo, N, dtype=xin.dtype, device=xin.device)
+    for tap in range(kt * kh * kw):
+        dt, dy, dx = tap // (kh * kw), tap // kw % kh, tap % kw
+        sl = x5[dt: dt + (g.To - 1) * st + 1: st, dy: dy + (g.Ho - 1) * sh + 1: sh, dx: dx + (g.Wo - 1) * sw + 1: sw]
+        acc += sl.reshape(-1, g.Cin) @ w4[:, tap].t()
+    return acc
+
+
 def gemm_acc(A, W, *, N, K, M=None, conv=None, dtype=torch.float32):
     """A[M, K] @ W[:N, :K]^T (or the implicit-GEMM conv) before any epilogue, [M, N] in ``dtype``."""
     Wf = W[:N, :K].to(dtype)
@@ -58,6 +74,8 @@ def gemm_acc(A, W, *, N, K, M=None, conv=None, dtype=torch.float32):
     g = conv
     kt, kh, kw = g.k
     xin = conv_padded_input(A, g, dtype)
+    if dtype == torch.float64 and xin.device.type != "cpu":
+        return conv_by_taps(xin, Wf, g, N)
     w5 = Wf[:, :kt * kh * kw * g.Cin].reshape(N, kt, kh, kw, g.Cin).permute(0, 4, 1, 2, 3)   # (thin: K zero-padded)
     try:
         y = F.conv3d(xin, w5, stride=tuple(g.stride))[0]                   # [N, To', Ho', Wo']

@@ -5,6 +5,9 @@
     scaled to CPU size and at the small GEMM / conv / attention cases of tests/test_gpu_kernels.py.
   * Fault injection: a local fault put into a correct result fails the checker while the global metric the kernel tests used alone so
     far (||got - want|| / ||want|| < 2.5e-3, 4e-3 for attention) still passes -- the gap this checker closes.
+  * The engines' glue kernels (ada_combine, patchify, im2col_causal, blend_accumulate, blend_finalize, affine_slice): the restatement
+    is inside each bound (bit equality for pure data movement), a single-element or single-chunk fault is outside it, and the global
+    metric lets that fault pass.
   * Attention on steered score ranges (conditioning_cases.attn_score_cases): the flash ALGORITHM of both kernels
     (tests/attn_emulation.py: key tiles, clamped and masked tail, one rescale vote per query block, deferral) is inside the bound on
     every case, and with the mask missing, O stale or l stale it is rejected on every case that can see the fault."""
@@ -570,3 +573,138 @@ def test_fault_attention_ragged_tile_unmasked_in_one_query_block():
     assert rel_err(out.float(), ref3[0]) < TOL_ATTN
     msg = must_fail(lambda: le.check("attention hot_gauss, one block unmasked", out, *ref3))
     assert "in 1 rows" in msg
+
+
+# ------------------------------------------------------------------------------------------------ the engines' glue kernels
+def next_bf16(t):
+    """the neighbouring bf16 value (one unit in the last place away)"""
+    return (t.view(torch.int16) + 1).view(BF16)
+
+
+def test_ada_combine_is_inside_its_bounds_and_one_element_is_not():
+    dim, n_vec = 2560, 14
+    emb, params = rnd(dim * 6, scale=2.0), rnd(n_vec, dim, seed=1)
+    slots = torch.tensor([v % 6 for v in range(n_vec)], dtype=torch.int32)
+    out = ref.ada_combine(emb, params, slots, torch.empty(n_vec, dim))
+    assert le.check_ada_combine(out, emb, params, slots) <= 1.0
+    clean = out.clone()
+    out[9, 1303] *= 1.0 + 2.0 ** -18                                               # 64 fp32 ulps on one element
+    assert rel_err(out, clean) < TOL_BF16
+    msg = must_fail(lambda: le.check_ada_combine(out, emb, params, slots))
+    assert "1 of" in msg and "row 9 " in msg
+    out = clean.clone()
+    out[5] = clean[4]                                                              # a vector read through its neighbour's slot
+    assert "in 1 rows" in must_fail(lambda: le.check_ada_combine(out, emb, params, slots))
+
+
+def test_data_movement_is_checked_bit_for_bit():
+    """patchify and im2col_causal: no arithmetic, so the bound is zero -- on the bit patterns.  One element one bf16 step off, or a
+    pad column holding -0.0, passes the global metric (the second is invisible to ANY comparison of values)."""
+    ops = sub("ops")
+    vid = rnd(3, 8, 12, 33)
+    out = ref.patchify(vid, torch.empty(3 * 4 * 6, 192, dtype=BF16))
+    want = le.patchify_reference(vid, out)
+    assert le.check_bits("patchify", out, want) == 0.0 and bool((want[:, 132:] == 0).all())
+    one_off = out.clone()
+    one_off[40, 77:78] = next_bf16(out[40, 77:78])
+    assert rel_err(one_off.float(), want.float()) < TOL_BF16
+    with pytest.raises(AssertionError, match="1 of .* row 40 .* column 77 "):
+        le.check_bits("patchify", one_off, want)
+    pad = out.clone()
+    pad[71, 191] = -0.0
+    assert rel_err(pad.float(), want.float()) == 0.0 and torch.equal(pad, want)    # (value comparisons: all blind)
+    with pytest.raises(AssertionError, match="row 71 .* column 191 "):
+        le.check_bits("patchify", pad, want)
+    for T, hf, stride in ((3, 0, (1, 1, 1)), (1, 2, (1, 1, 1)), (4, 1, (2, 2, 2))):
+        H, W, Cin, k = 6, 10, 16, (3, 3, 3)
+        x, halo = rnd(T, H, W, Cin), (rnd(hf, H, W, Cin, seed=9) if hf else None)
+        pt = hf if hf else 2
+        plo, phi = (1, 1) if stride == (1, 1, 1) else (0, 1)
+        To, Ho, Wo = (T + pt - 3) // stride[0] + 1, (H + plo + phi - 3) // stride[1] + 1, (W + plo + phi - 3) // stride[2] + 1
+        geom = ops.Conv3dGeom(T, H, W, Cin, To, Ho, Wo, k, stride, (pt, plo, plo), halo)
+        cols = ref.im2col_causal(x, torch.empty(To * Ho * Wo, 448, dtype=BF16), geom)
+        want = le.im2col_causal_reference(x, cols, geom)
+        assert le.check_bits("im2col_causal", cols, want) == 0.0 and bool((want[:, 432:] == 0).all())
+        # the rows ARE the conv's operand: a GEMM over them is the conv (the index map is the one gemm_reference uses)
+        w5, Wp = conv_weight(64, Cin, k)
+        Wpad = torch.cat([Wp, torch.zeros(64, 16, dtype=BF16)], 1)
+        assert rel_err(cols.double() @ Wpad.double().t(), le.gemm_reference(x, Wp, torch.empty(To, Ho, Wo, 64, dtype=F32), N=64, K=432,
+                                                                             conv=geom)[0].reshape(-1, 64)) < 1e-12
+        tap = cols.clone()
+        tap[To * Ho * Wo - 1, 16:32] = cols[To * Ho * Wo - 2, 16:32]               # one tap's 32 bytes from the voxel before
+        with pytest.raises(AssertionError, match=f"row {To * Ho * Wo - 1} "):
+            le.check_bits("im2col_causal", tap, want)
+
+
+@pytest.mark.parametrize("case", CONVS)
+def test_conv_by_taps_is_the_fp64_conv(case):
+    """The tap-by-tap matmul form gemm_acc takes for the fp64 reference on a device == F.conv3d in fp64."""
+    from ops_reference import conv_by_taps, conv_padded_input, gemm_acc
+    x, w5, Wp, kw, shape = conv_problem(case)
+    g = kw["conv"]
+    got = conv_by_taps(conv_padded_input(x, g, torch.float64), Wp[:kw["N"]].double(), g, kw["N"])
+    assert rel_err(got, gemm_acc(x, Wp, N=kw["N"], K=kw["K"], conv=g, dtype=torch.float64)) < 1e-13
+
+
+def blend_problem(T=3, C=16, H=64, W=96, h=9, w=12, y0=7, x0=16):
+    vae = sub("vae")
+    tile = rnd(T, h, w, C, scale=0.5)
+    acc, cnt = rnd(T, H, W, C, dtype=F32, seed=1), rnd(H, W, dtype=F32, seed=2).abs() + 0.5
+    wy = vae._edge_weights(h, 4, True, False, vae._cos_ramp(4))
+    wx = vae._edge_weights(w, 4, True, True, vae._cos_ramp(4))
+    return tile, acc, cnt, wy, wx, y0, x0
+
+
+def test_blend_accumulate_is_inside_its_bounds_and_local_faults_are_not():
+    tile, acc0, cnt0, wy, wx, y0, x0 = blend_problem()
+    acc, cnt = acc0.clone(), cnt0.clone()
+    ref.blend_accumulate(tile, acc, cnt, wy, wx, y0, x0)
+    args = (tile, acc0, cnt0, wy, wx, y0, x0)
+    assert le.check_blend_accumulate(acc, cnt, *args) <= 1.0
+    (wa, ba, ma), (wc, bc, mc) = le.blend_accumulate_reference(*args)
+    assert int(ma.sum()) == tile.numel() and int(mc.sum()) == 9 * 12
+    # one element of one voxel never received its tile: 1 of 294 912 elements
+    bad = acc.clone()
+    bad[1, y0 + 3, x0 + 5, 6] = acc0[1, y0 + 3, x0 + 5, 6]
+    assert rel_err(bad, wa.where(ma, acc0.double())) < TOL_BF16
+    msg = must_fail(lambda: le.check_blend_accumulate(bad, cnt, *args))
+    assert "1 of" in msg and "in 1 rows" in msg
+    # the weight counted once per FRAME instead of once per pixel
+    cnt_T = cnt0.clone()
+    cnt_T[y0:y0 + 9, x0:x0 + 12] += 3 * (wy[:, None] * wx[None, :])
+    must_fail(lambda: le.check_blend_accumulate(acc, cnt_T, *args))
+    # a tile one column too wide: the extra column is not the launch's own
+    wide = acc.clone()
+    wide[:, y0:y0 + 9, x0 - 1] += 1.0
+    with pytest.raises(AssertionError, match="not its own"):
+        le.check_blend_accumulate(wide, cnt, *args)
+
+
+def test_blend_finalize_and_affine_slice_are_inside_their_bounds_and_local_faults_are_not():
+    T, H, W, C, c_take = 3, 20, 28, 32, 16
+    acc = rnd(T, H, W, C, dtype=F32, scale=3.0)
+    cnt = rnd(H, W, dtype=F32, seed=2).abs() + 0.25
+    cnt[3, 4] = 0.0                                                                # (never covered: the 1e-6 floor)
+    for scale, shift in ((0.9152, 0.0), (1.0, 0.0), (1.0 / 0.9152, 0.3)):
+        out = ref.blend_finalize(acc, cnt, torch.empty(T, H, W, c_take, dtype=BF16), scale, shift)
+        assert le.check_blend_finalize(out, acc, cnt, scale, shift) <= 1.0
+        want = le.blend_finalize_reference(acc, cnt, c_take, scale, shift)[0]
+        bad = out.clone()
+        bad[2, 11, 13, 8:16] = (out[2, 11, 13, 8:16].float() * 1.02).to(BF16)      # one 16-byte store 2 % off (its neighbour's weight sum)
+        assert rel_err(bad.float(), want) < TOL_BF16
+        msg = must_fail(lambda: le.check_blend_finalize(bad, acc, cnt, scale, shift))
+        assert "in 1 rows" in msg
+    inp = rnd(T, H, W, C, scale=2.0)
+    for scale, shift in ((0.9152, 0.0), (1.0 / 0.9152, -0.0), (1.7, 0.3)):
+        out = ref.affine_slice(inp, torch.empty(T, H, W, c_take, dtype=BF16), scale, shift)
+        assert le.check_affine_slice(out, inp, scale, shift) <= 1.0
+        want = le.affine_slice_reference(inp, c_take, scale, shift)[0]
+        bad = out.clone()
+        bad[1, 7, 9, :8] = (out[1, 7, 9, :8].float() * 1.02).to(BF16)              # one 16-byte store 2 % off (a stale scale)
+        assert rel_err(bad.float(), want) < TOL_BF16
+        assert "in 1 rows" in must_fail(lambda: le.check_affine_slice(bad, inp, scale, shift))
+    # a scale applied in bf16 instead of fp32 (0.9152 -> 0.9141): every element 1.2e-3 off, under the 2.5e-3 of the global metric
+    scale = 0.9152
+    out = ref.affine_slice(inp, torch.empty(T, H, W, c_take, dtype=BF16), float(torch.tensor(scale).to(BF16)), 0.0)
+    assert rel_err(out.float(), le.affine_slice_reference(inp, c_take, scale, 0.0)[0]) < TOL_BF16
+    must_fail(lambda: le.check_affine_slice(out, inp, scale, 0.0))
