@@ -17,7 +17,9 @@ upscaled frames.  Restated from src/utils/color_fix.py (results identical on the
 All tensors are [B, C, H, W] in [-1, 1]; the work is HBM / sort bound (no MFMA).  The functions below are torch and run on
 whatever device their inputs live on: they are the specification.  ``correct`` (at the end) is what the pipeline calls: on a
 HIP backend it hands the wavelet pyramid, the CIELAB conversions and AdaIN to csrc/svr_colorfix.hip (HipOps.wavelet_reconstruct /
-lab_planes / lab_merge / adain); the rank matching (torch's sort and scatter) and the HSV mode stay here.
+lab_planes / lab_merge / adain) and the rank matching of ``lab`` to csrc/svr_rank.hip (HipOps.rank_match: a stable radix sort, so
+the matched planes are ``rank_match_spec``'s bit for bit; ``RANK_MATCH = False`` puts torch's sort and scatter back); the HSV mode
+and its per-hue-bin matching of unequal sizes stay here.
 """
 import torch
 import torch.nn.functional as F
@@ -126,6 +128,37 @@ def histogram_match(source: torch.Tensor, reference: torch.Tensor) -> torch.Tens
     out = torch.empty_like(ref_sorted)
     out[src_sorted_idx] = ref_sorted          # == matched_sorted[argsort(source_indices)]
     return out.reshape(shape)
+
+
+def sort_key(x: torch.Tensor) -> torch.Tensor:
+    """fp32 -> the uint32 key (held in an int64 tensor) whose unsigned order is the order of ``torch.sort(stable=True)`` on the
+    CPU: a NaN of either sign becomes the quiet NaN 0x7FC00000 and both zeros +0.0; then a word with the sign bit set is
+    complemented and any other gets its sign bit set.  The value a key stands for is its canonical value (``key_value``)."""
+    bits = x.detach().float().contiguous().view(torch.int32).to(torch.int64) & 0xFFFFFFFF
+    mag = bits & 0x7FFFFFFF
+    bits = torch.where(mag > 0x7F800000, torch.full_like(bits, 0x7FC00000), bits)
+    bits = torch.where(mag == 0, torch.zeros_like(bits), bits)
+    return torch.where(bits >= 0x80000000, bits ^ 0xFFFFFFFF, bits | 0x80000000)
+
+
+def key_value(key: torch.Tensor) -> torch.Tensor:
+    """The canonical fp32 value of a ``sort_key``: -0.0 reads back as +0.0 and any NaN as the quiet NaN."""
+    bits = torch.where(key >= 0x80000000, key ^ 0x80000000, key ^ 0xFFFFFFFF)
+    return torch.where(bits >= 0x80000000, bits - (1 << 32), bits).to(torch.int32).view(torch.float32)
+
+
+def rank_match_spec(source: torch.Tensor, reference: torch.Tensor) -> torch.Tensor:
+    """``histogram_match`` for equal sizes with both sorts made stable and canonical values out -- the specification of
+    csrc/svr_rank.hip (HipOps.rank_match), bit for bit: ``out.flatten()[i] = sorted_reference[r(i)]``, r(i) = the number of j with
+    key(source_j) < key(source_i) plus the number of j < i with an equal key, so ties go to the lower flat index."""
+    if source.dtype != torch.float32 or reference.dtype != torch.float32 or source.numel() != reference.numel():
+        raise ValueError(f"rank_match_spec: two fp32 tensors of one size, got {source.dtype} {tuple(source.shape)} and "
+                         f"{reference.dtype} {tuple(reference.shape)}")
+    order = torch.sort(sort_key(source.flatten()), stable=True).indices
+    ref_sorted = key_value(torch.sort(sort_key(reference.flatten())).values)
+    out = torch.empty_like(ref_sorted)
+    out[order] = ref_sorted
+    return out.reshape(source.shape)
 
 
 def lab_color_transfer(content: torch.Tensor, style: torch.Tensor, luminance_weight: float = 0.8) -> torch.Tensor:
@@ -243,14 +276,26 @@ def routes_to_device(content: torch.Tensor, style: torch.Tensor, method: str, op
             and content.dim() == 4 and content.shape[1] == 3 and content.numel() > 0 and content.shape == style.shape)
 
 
+# Rank matching of the lab route on ops.rank_match (csrc/svr_rank.hip: stable, so the result is rank_match_spec's bit for bit)
+# where the ops offer it; False: histogram_match, torch's sorts.  The default follows the measurement in DESIGN.md 7.3e.
+RANK_MATCH = True
+RANK_MATCH_MAX = 1 << 30        # elements per plane svr_rank_match serves (uint32 offsets); a larger plane stays on histogram_match
+
+
 def _lab_on_device(content, style, ops, luminance_weight: float = 0.8):
     """lab_color_transfer with the wavelet base and both colour-space conversions as kernels; the rank matching between them is
-    histogram_match (torch's sort and scatter) on the planes."""
+    ops.rank_match (the radix sort of csrc/svr_rank.hip) under RANK_MATCH where the ops have it and a plane holds at most
+    RANK_MATCH_MAX values, else histogram_match (torch's sort and scatter, which has no size limit) on the planes."""
     t, _, h, w = content.shape
     c_lab, s_lab = ops.lab_planes(ops.wavelet_reconstruct(content, style), style)
-    a = histogram_match(c_lab[1], s_lab[1])
-    b = histogram_match(c_lab[2], s_lab[2])
-    m_l = histogram_match(c_lab[0], s_lab[0]) if luminance_weight < 1.0 else None
+    if RANK_MATCH and hasattr(ops, "rank_match") and t * h * w <= RANK_MATCH_MAX:
+        m_l = ops.rank_match(c_lab[0], s_lab[0]) if luminance_weight < 1.0 else None      # (c_L itself is still read by the merge)
+        a = ops.rank_match(c_lab[1], s_lab[1], out=c_lab[1])                              # the a and b planes are dead after matching
+        b = ops.rank_match(c_lab[2], s_lab[2], out=c_lab[2])
+    else:
+        a = histogram_match(c_lab[1], s_lab[1])
+        b = histogram_match(c_lab[2], s_lab[2])
+        m_l = histogram_match(c_lab[0], s_lab[0]) if luminance_weight < 1.0 else None
     return ops.lab_merge(c_lab[0], m_l, a, b, luminance_weight, (t, h, w))
 
 

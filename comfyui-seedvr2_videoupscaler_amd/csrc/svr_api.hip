@@ -21,6 +21,7 @@
 #include "svr_frame_unpack.hip"
 #include "svr_png.hip"
 #include "svr_colorfix.hip"
+#include "svr_rank.hip"
 #include "svr_gguf.hip"
 
 using namespace svr;
@@ -77,6 +78,7 @@ int svr_set_option(const char* key, int32_t value) {
     if (!strcmp(key, "attn_impl")) { g_attn_impl = value; return 0; }
     if (!strcmp(key, "attn_variant")) { g_attn_variant = value; return 0; }
     if (!strcmp(key, "png_passes")) { if (value < 1 || value > 3) return fail("svr_set_option: png_passes is 1, 2 or 3"); g_png_passes = value; return 0; }
+    if (!strcmp(key, "rank_launches")) { if (value < 1 || value > 3) return fail("svr_set_option: rank_launches is 1, 2 or 3"); g_rank_launches = value; return 0; }
     return fail("svr_set_option: unknown key");
 }
 
@@ -734,6 +736,130 @@ int svr_adain_apply(const void* content, const int64_t* content_strides, const v
                        (const float*)content, cs, (const float*)stats, eps, (float*)out, os, H, W, chunks);
     return check(hipGetLastError(), "svr_adain_apply");
 }
+
+// ---- rank matching (svr_rank.hip): a stable radix sort of fp32 keys and the scatter that hands out the sorted reference.
+// Workspace (bytes; n4 = 4 * n rounded up to 256): [sorted reference values n4][keys A n4][indices A n4][keys B n4][indices B n4]
+// [table 256 * tiles_p * 4][totals 1024], tiles_p = ceil(n / 4096) rounded up to 16.
+struct RankPlan {
+    uint32_t n, tiles_p, groups;
+    char *ref, *keys[2], *idx[2];
+    uint32_t *table, *totals;
+    int64_t bytes;
+};
+static RankPlan rank_plan(int64_t n, void* workspace) {
+    RankPlan p;
+    const int64_t tiles = (n + RANK_TILE - 1) / RANK_TILE, n4 = (4 * n + 255) / 256 * 256;
+    p.n = (uint32_t)n;
+    p.groups = (uint32_t)((tiles + RANK_GROUP - 1) / RANK_GROUP);
+    p.tiles_p = p.groups * RANK_GROUP;
+    char* w = (char*)workspace;
+    p.ref = w;
+    p.keys[0] = w + n4; p.idx[0] = w + 2 * n4; p.keys[1] = w + 3 * n4; p.idx[1] = w + 4 * n4;
+    p.table = (uint32_t*)(w + 5 * n4);
+    p.totals = p.table + (int64_t)RANK_RADIX * p.tiles_p;
+    p.bytes = 5 * n4 + (int64_t)RANK_RADIX * p.tiles_p * 4 + RANK_RADIX * 4;
+    return p;
+}
+// The four passes of one sort: in -> A -> B -> A -> (out_keys, out_idx).  pairs: indices travel with the keys (the first pass
+// makes them: a key's place in ``in``).  out_mode: what the last pass stores (svr_rank.hip, rank_scatter_kernel).
+static void rank_sort_launch(const RankPlan& p, const void* in, bool pairs, int out_mode, void* out_keys, void* out_idx, hipStream_t s) {
+    const void* src_k = in;
+    const void* src_i = nullptr;
+    for (int pass = 0; pass < 32 / RANK_BITS; ++pass) {
+        const bool last = pass == 32 / RANK_BITS - 1;
+        const int shift = pass * RANK_BITS, first = pass == 0, mode = last ? out_mode : 0;
+        void* dst_k = last ? out_keys : p.keys[pass & 1];
+        void* dst_i = last ? out_idx : p.idx[pass & 1];
+        hipLaunchKernelGGL(rank_hist_kernel, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)src_k, p.n, shift, first, p.table, p.tiles_p);
+        // (g_rank_launches < 3, tools/colorfix_timing.py only: every pass's launches up to that one, to time them by difference; the
+        // passes then read what an earlier whole sort left in the workspace and the outputs are not written)
+        if (g_rank_launches >= 2) hipLaunchKernelGGL(rank_scan_kernel, dim3(RANK_RADIX), dim3(RANK_THREADS), 0, s, p.table, p.tiles_p, p.totals);
+        if (g_rank_launches < 3) { src_k = p.keys[pass & 1]; src_i = p.idx[pass & 1]; continue; }
+        if (pairs)
+            hipLaunchKernelGGL(rank_scatter_kernel<true>, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)src_k, (const uint32_t*)src_i,
+                               p.n, shift, first, mode, (const uint32_t*)p.table, p.tiles_p, (const uint32_t*)p.totals, (uint32_t*)dst_k, (uint32_t*)dst_i);
+        else
+            hipLaunchKernelGGL(rank_scatter_kernel<false>, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)src_k, (const uint32_t*)nullptr,
+                               p.n, shift, first, mode, (const uint32_t*)p.table, p.tiles_p, (const uint32_t*)p.totals, (uint32_t*)dst_k, (uint32_t*)nullptr);
+        src_k = dst_k; src_i = dst_i;
+    }
+}
+static bool rank_overlap(const void* a, int64_t a_bytes, const void* b, int64_t b_bytes) {
+    const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+    return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
+}
+#define SVR_RANK_N_AND_WORKSPACE(name) do { \
+        if (n < 1 || n > RANK_MAX_N) SVR_COLORFIX_REFUSE(name, "n", "must be in [1, 2^30]"); \
+        if ((uintptr_t)workspace % 16) SVR_COLORFIX_REFUSE(name, "workspace", "is not aligned to 16 bytes"); \
+        if (workspace_bytes < svr_rank_workspace_bytes(n)) SVR_COLORFIX_REFUSE(name, "workspace_bytes", "is below svr_rank_workspace_bytes(n)"); \
+    } while (0)
+#define SVR_RANK_ALIGNED(name, p) do { if ((uintptr_t)(p) % 4) SVR_COLORFIX_REFUSE(name, #p, "is not aligned to 4 bytes"); } while (0)
+#define SVR_RANK_APART(name, a, b) do { if (rank_overlap(a, 4 * n, b, 4 * n)) SVR_COLORFIX_REFUSE(name, #a, "overlaps " #b); } while (0)
+#define SVR_RANK_OFF_WORKSPACE(name, a) do { if (rank_overlap(a, 4 * n, workspace, svr_rank_workspace_bytes(n))) SVR_COLORFIX_REFUSE(name, #a, "overlaps workspace"); } while (0)
+
+int64_t svr_rank_workspace_bytes(int64_t n) {
+    if (n < 1 || n > RANK_MAX_N) return 0;
+    return rank_plan(n, nullptr).bytes;
+}
+
+int svr_rank_geometry(int32_t* out2) {
+    SVR_COLORFIX_PTR("svr_rank_geometry", out2);
+    out2[0] = RANK_TILE;
+    out2[1] = 0;                                     // rank_scan_kernel walks a row of any length with a carry
+    return 0;
+}
+
+int svr_sort_f32(const void* keys, int64_t n, void* sorted, void* index, void* workspace, int64_t workspace_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    SVR_COLORFIX_PTR("svr_sort_f32", keys);
+    SVR_COLORFIX_PTR("svr_sort_f32", sorted);
+    SVR_COLORFIX_PTR("svr_sort_f32", workspace);
+    SVR_RANK_N_AND_WORKSPACE("svr_sort_f32");
+    SVR_RANK_ALIGNED("svr_sort_f32", keys);
+    SVR_RANK_ALIGNED("svr_sort_f32", sorted);
+    SVR_RANK_ALIGNED("svr_sort_f32", index);
+    SVR_RANK_APART("svr_sort_f32", sorted, keys);
+    if (index) {
+        SVR_RANK_APART("svr_sort_f32", index, keys);
+        SVR_RANK_APART("svr_sort_f32", index, sorted);
+        SVR_RANK_OFF_WORKSPACE("svr_sort_f32", index);
+    }
+    SVR_RANK_OFF_WORKSPACE("svr_sort_f32", keys);
+    SVR_RANK_OFF_WORKSPACE("svr_sort_f32", sorted);
+    const RankPlan p = rank_plan(n, workspace);
+    rank_sort_launch(p, keys, index != nullptr, 1, sorted, index, (hipStream_t)stream);
+    return check(hipGetLastError(), "svr_sort_f32");
+}
+
+int svr_rank_match(const void* source, const void* reference, int64_t n, void* out, void* workspace, int64_t workspace_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    SVR_COLORFIX_PTR("svr_rank_match", source);
+    SVR_COLORFIX_PTR("svr_rank_match", reference);
+    SVR_COLORFIX_PTR("svr_rank_match", out);
+    SVR_COLORFIX_PTR("svr_rank_match", workspace);
+    if (g_rank_launches != 3) SVR_COLORFIX_REFUSE("svr_rank_match", "", "svr_set_option(\"rank_launches\") below 3 serves svr_sort_f32 only");
+    SVR_RANK_N_AND_WORKSPACE("svr_rank_match");
+    SVR_RANK_ALIGNED("svr_rank_match", source);
+    SVR_RANK_ALIGNED("svr_rank_match", reference);
+    SVR_RANK_ALIGNED("svr_rank_match", out);
+    SVR_RANK_APART("svr_rank_match", out, reference);
+    if (out != source) SVR_RANK_APART("svr_rank_match", out, source);          // out == source: the plane is matched in place
+    SVR_RANK_APART("svr_rank_match", source, reference);
+    SVR_RANK_OFF_WORKSPACE("svr_rank_match", source);
+    SVR_RANK_OFF_WORKSPACE("svr_rank_match", reference);
+    SVR_RANK_OFF_WORKSPACE("svr_rank_match", out);
+    const RankPlan p = rank_plan(n, workspace);
+    const hipStream_t s = (hipStream_t)stream;
+    rank_sort_launch(p, reference, false, 1, p.ref, nullptr, s);               // the reference's sorted values stay in the workspace
+    rank_sort_launch(p, source, true, 2, nullptr, p.idx[1], s);                // source: only where each rank came from is kept
+    hipLaunchKernelGGL(rank_apply_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, s, (const uint32_t*)p.idx[1], (const uint32_t*)p.ref,
+                       p.n, (uint32_t*)out);
+    return check(hipGetLastError(), "svr_rank_match");
+}
+#undef SVR_RANK_OFF_WORKSPACE
+#undef SVR_RANK_APART
+#undef SVR_RANK_ALIGNED
+#undef SVR_RANK_N_AND_WORKSPACE
 #undef SVR_COLORFIX_GEOMETRY
 #undef SVR_COLORFIX_STRIDES
 #undef SVR_COLORFIX_PTR

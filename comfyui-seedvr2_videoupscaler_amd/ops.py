@@ -733,6 +733,55 @@ class HipOps:
                       "svr_adain_apply")
         return out
 
+    # (colorfix.sort_key / rank_match_spec are the specification, bit for bit; csrc/svr_rank.hip.)
+    def _rank_workspace(self, n, what):
+        nbytes = int(self.lib.svr_rank_workspace_bytes(n))
+        if nbytes <= 0:
+            raise ValueError(f"{what}: between 1 and 2^30 elements per call, got {n}")
+        return torch.empty(nbytes, dtype=torch.uint8, device=self.device), nbytes
+
+    def sort_f32(self, keys, index=True, sorted_out=None, index_out=None):
+        """Stable ascending sort of an fp32 tensor (flattened), the order of ``torch.sort(stable=True)`` on the CPU with NaN last
+        -> (sorted fp32 [n] of canonical values, uint32-valued int32 [n] source indices or None for ``index=False``: keys only)."""
+        self._chk(keys, torch.float32, "sort_f32: keys")
+        if hip_lib.OPTIONS.get("rank_launches", 3) != 3:
+            raise hip_lib.HipLibraryError("sort_f32: set_option('rank_launches') is below 3 (a measurement setting under which "
+                                          "svr_sort_f32 stores nothing); set it back to 3")
+        n = keys.numel()
+        ws, nbytes = self._rank_workspace(n, "sort_f32")
+
+        def out(t, dtype, name):
+            if t is None:
+                t = torch.empty(n, dtype=dtype, device=self.device)
+            self._chk(t, dtype, name)
+            if t.numel() != n:
+                raise ValueError(f"{name} must hold {n} elements, got {tuple(t.shape)}")
+            return t
+
+        sorted_out = out(sorted_out, torch.float32, "sort_f32: sorted_out")
+        idx = out(index_out, torch.int32, "sort_f32: index_out") if index else None      # keys only: no index is allocated
+        hip_lib.check(self.lib.svr_sort_f32(_ptr(keys), n, _ptr(sorted_out), _ptr(idx), _ptr(ws), nbytes, self._stream()), "svr_sort_f32")
+        return sorted_out, idx
+
+    def rank_match(self, source, reference, out=None):
+        """colorfix.rank_match_spec: the k-th smallest source value becomes the k-th smallest reference value, ties to the lower
+        flat index.  Two fp32 tensors of one size; ``out`` may be ``source`` itself (matched in place)."""
+        self._chk(source, torch.float32, "rank_match: source")
+        self._chk(reference, torch.float32, "rank_match: reference")
+        n = source.numel()
+        if reference.numel() != n:
+            raise ValueError(f"rank_match: source and reference must hold the same number of elements, got {tuple(source.shape)} and "
+                             f"{tuple(reference.shape)} (unequal sizes: colorfix.histogram_match)")
+        if out is None:
+            out = torch.empty_like(source)
+        self._chk(out, torch.float32, "rank_match: out")
+        if tuple(out.shape) != tuple(source.shape):
+            raise ValueError(f"rank_match: out must be fp32 {tuple(source.shape)}, got {tuple(out.shape)}")
+        ws, nbytes = self._rank_workspace(n, "rank_match")
+        hip_lib.check(self.lib.svr_rank_match(_ptr(source), _ptr(reference), n, _ptr(out), _ptr(ws), nbytes, self._stream()),
+                      "svr_rank_match")
+        return out
+
     # ------------------------------------------------------------------ packed input frames
     def unpack_frames(self, packed, fmt, T, H, W, C, matrix="bt709", range_="tv", out=None):
         """Input frames widened on the device (frameio_in.py is the specification; csrc/svr_frame_unpack.hip): ``packed`` a dense

@@ -58,6 +58,7 @@
  *   svr_png_encode                             frames element alignment, scratch 16, sizes 8, out any (byte stores)
  *   svr_wavelet_reconstruct, svr_lab_*,        element accesses only: pixel operands by four element strides (input >= 0, output
  *     svr_chan_stats, svr_adain_apply          >= 1), planes and stats dense fp32; svr_chan_stats' workspace 8
+ *   svr_sort_f32, svr_rank_match               operands 4 (dense [n]), workspace 16
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -85,6 +86,8 @@ extern "C" {
  * device).  New symbols only.
  * v9, additive: + svr_wavelet_reconstruct() / svr_lab_planes() / svr_lab_merge() / svr_chan_stats() / svr_adain_apply() and
  * svr_colorfix_workspace_bytes() (colour correction after the decode: wavelet, LAB and AdaIN on the device).  New symbols only.
+ * v9, additive: + svr_sort_f32() / svr_rank_match() / svr_rank_workspace_bytes() / svr_rank_geometry() (a stable radix sort of fp32
+ * keys and the rank matching of the LAB colour transfer on top of it).  New symbols only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -454,6 +457,30 @@ int svr_chan_stats(const void* content, const int64_t* content_strides, const vo
 int svr_adain_apply(const void* content, const int64_t* content_strides, const void* stats, float eps, void* out,
                     const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream);
 
+/* Rank matching (colorfix.sort_key / colorfix.rank_match_spec are the specification, BIT FOR BIT; csrc/svr_rank.hip): a stable
+ * least-significant-digit radix sort of fp32 keys, 8-bit digits, four passes of three launches (per-tile digit counts, a scan of the
+ * digit x tile table, a stable scatter).  No workgroup waits on another, no atomic decides a position: the same bits on every run.
+ * All operands are dense fp32 / uint32 [n], 4-byte aligned, 1 <= n <= 2^30; inputs are not modified.  The order is that of
+ * torch.sort(stable=True) on the CPU: -inf ... -0.0 = +0.0 ... +inf, NaN last, equal keys in the order of their indices; a sorted
+ * value is canonical (-0.0 reads back as +0.0, any NaN as the quiet NaN 0x7FC00000).
+ * svr_rank_workspace_bytes(n): bytes of device memory either call needs, 16-byte aligned: 5 * roundup(4 n, 256) + 1024 *
+ *   roundup(ceil(n / 4096), 16) + 1024, which is at most 20.25 n + 20 KiB (below 24 n + 65536); <= 0: n is refused.
+ * svr_rank_geometry(out2): out2[0] = 4096, the keys of one tile (one column of the table; a workgroup walks 16 consecutive tiles, so
+ *   n = 65536 is a boundary as well); out2[1] = 0: one launch of the table scan covers any number of tiles.
+ * svr_sort_f32(): sorted[k] = the k-th smallest key's canonical value; index (may be NULL: keys only, 4 bytes per element and pass
+ *   less) [k] = where that key stood in `keys`.  12 launches.
+ * svr_rank_match(): out[i] = sorted_reference[r(i)], r(i) = the number of j with key(source_j) < key(source_i), plus the number of
+ *   j < i with an equal key.  The reference is sorted first (keys only) and its 4 n bytes kept, then the source's key + index pairs
+ *   are sorted and out[index[k]] = sorted_reference[k] is stored.  25 launches.
+ * No two of the operands, outputs and the workspace may overlap, with one exception: out may be `source` itself (the same pointer).
+ * Every argument is checked before the first launch (a null pointer, n, alignment, a workspace below svr_rank_workspace_bytes(n),
+ * overlap) and svr_last_error() names it; nothing is allocated, all launches go to `stream`, none synchronises with the host. */
+int64_t svr_rank_workspace_bytes(int64_t n);
+int svr_rank_geometry(int32_t* out2);
+int svr_sort_f32(const void* keys, int64_t n, void* sorted, void* index, void* workspace, int64_t workspace_bytes, void* stream);
+int svr_rank_match(const void* source, const void* reference, int64_t n, void* out, void* workspace, int64_t workspace_bytes,
+                   void* stream);
+
 /* ---- packed input frames -------------------------------------------------------------------- */
 /* frameio_in.py (the specification, bit for bit), the inverse of svr_pack_frames: packed samples as a decoder emits them -> out
  * fp32 [T, H, W, C] dense, nominally in [0, 1].  Every value is an integer code q over a full scale D, computed in exact integers,
@@ -517,6 +544,8 @@ int svr_dequant_gguf(const void* blocks, int32_t ggml_type, int64_t n_blocks, vo
  * "attn_impl" 0 auto (second-generation window kernel for head_dim 128 / windows <= 2048 rows) | 1 first kernel everywhere,
  * "attn_variant" build variant of the second-generation window kernel (0 default = 8 waves x 32 queries; 1 / 3 / 4: 4-wave and
  * s_setprio builds -- see svr_attn_win.hip),
+ * "rank_launches" 3 (default) | 1 | 2: measurement only -- svr_sort_f32 issues only the histogram, or the histogram and the table scan,
+ * of every pass (nothing is stored to its outputs; svr_rank_match refuses), so that the launches can be timed by difference,
  * "pipe_abl" measurement-only ablations in -DSVR_ABLATIONS builds (non-zero values give garbage). */
 int svr_set_option(const char* key, int32_t value);
 /* Calibration aid, NOT on the data path (ABI v9; the reference has no counterpart -- its timing report is src/utils/debug.py): launches

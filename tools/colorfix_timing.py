@@ -8,10 +8,13 @@ the matched values of near-tied pixels).  No threshold is attached to any figure
 Byte model, printed next to the times: one pass over a span is T * H * W * 3 * 4 bytes (1.69 GB at 17 x 2160 x 3840).  The wavelet
 launch ideally reads content and style and writes the result once: 3 passes.  The torch route makes on the order of sixty (two
 operands x five levels x about six elementwise / index kernels, each reading and writing a span).  lab_planes reads 2 and writes 2
-passes, lab_merge reads 4/3 and writes 1, AdaIN reads content twice and style once and writes once; the sorts of the rank matching
-are torch's on both routes.
+passes, lab_merge reads 4/3 and writes 1, AdaIN reads content twice and style once and writes once.
 
-python tools/colorfix_timing.py [--frames 17] [--height 2160] [--width 3840] [--reps 5] > profiles/colorfix.txt"""
+Rank matching (csrc/svr_rank.hip, the last section): per plane HipOps.rank_match against colorfix.histogram_match (torch's sorts) on
+the same device planes; a sort's three launches per pass by difference; the whole lab route with colorfix.RANK_MATCH on and off
+(mean, min and max of the repetitions) and both routes' peak memory.  The per-method table above runs with RANK_MATCH as it stands.
+
+python tools/colorfix_timing.py [--frames 17] [--height 2160] [--width 3840] [--reps 5] >> profiles/colorfix.txt"""
 import argparse
 import importlib
 import os
@@ -38,6 +41,102 @@ def timed(fn, warmup, reps):
     return s.elapsed_time(e) / reps
 
 
+def timed_each(fn, warmup, reps):
+    """-> the ``reps`` single-call times in ms (an event pair per call), after the warm-up"""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    pairs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for s, e in pairs:
+        s.record()
+        fn()
+        e.record()
+    torch.cuda.synchronize()
+    return [s.elapsed_time(e) for s, e in pairs]
+
+
+def spread(ms):
+    return f"{sum(ms) / len(ms):8.2f} ms (min {min(ms):.2f}, max {max(ms):.2f})"
+
+
+def rank_section(ops, cf, content, style, args):
+    """Rank matching (csrc/svr_rank.hip) against colorfix.histogram_match (torch's sorts) on the same device planes, in this
+    process: per plane, the launches' shares of a pass, the whole lab route with colorfix.RANK_MATCH on and off, peak memory."""
+    T, H, W = args.frames, args.height, args.width
+    n = T * H * W
+    c_lab, s_lab = ops.lab_planes(ops.wavelet_reconstruct(content, style), style)
+    print(f"# ---- rank matching: {n} values per plane; byte model per element: source pairs 4 x (4 + 8 + 8) = 80 B (the last pass stores no "
+          f"keys: 76 B), reference keys 4 x (4 + 4 + 4) = 48 B, final scatter 8 B read + 4 B stored at random = {n * 136 / 1e9:.1f} GB per plane "
+          f"(+ the digit x tile table: 4 KiB per 4096-key tile and pass, {8 * 4096 * -(-n // 4096) / 1e9:.2f} GB)")
+    for i, name in enumerate(("L", "a", "b")):
+        src, ref = c_lab[i], s_lab[i]
+        out = torch.empty_like(src)
+        t_k = timed_each(lambda: ops.rank_match(src, ref, out=out), args.warmup, args.reps)
+        t_t = timed_each(lambda: cf.histogram_match(src, ref), args.warmup, args.reps)
+        mean_k = sum(t_k) / len(t_k)
+        print(f"# plane {name}: ops.rank_match {spread(t_k)}  -> {n * 136 / mean_k / 1e9:6.2f} TB/s of the model's bytes;  "
+              f"colorfix.histogram_match {spread(t_t)};  ratio {sum(t_t) / sum(t_k):.2f}")
+        del out
+    # one plane taken apart: the two sorts, the final scatter by difference, and the launches of a pass by difference
+    # (svr_set_option("rank_launches", 1 | 2 | 3): the histogram, + the table scan, + the scatter of every pass)
+    src, ref = c_lab[1], s_lab[1]
+    out = torch.empty_like(src)
+    sorted_, index = torch.empty_like(src), torch.empty(n, dtype=torch.int32, device=src.device)
+    t_match = timed(lambda: ops.rank_match(src, ref, out=out), args.warmup, args.reps)
+    t_keys = timed(lambda: ops.sort_f32(ref, index=False, sorted_out=sorted_), args.warmup, args.reps)
+    t_pairs = timed(lambda: ops.sort_f32(src, index=True, sorted_out=sorted_, index_out=index), args.warmup, args.reps)
+    print(f"# plane a: sort of the reference keys {t_keys:8.2f} ms ({n * 48 / t_keys / 1e9:5.2f} TB/s of 48 B),  sort of the source pairs "
+          f"{t_pairs:8.2f} ms ({n * 80 / t_pairs / 1e9:5.2f} TB/s of 80 B),  rank_match {t_match:8.2f} ms,  final scatter by difference "
+          f"{t_match - t_keys - t_pairs:8.2f} ms ({n * 12 / max(t_match - t_keys - t_pairs, 1e-3) / 1e9:5.2f} TB/s of 12 B; the pair sort "
+          f"timed alone also stores 4 B of keys in its last pass)")
+    # (one workspace for all of it, filled by a whole sort first: a pass cut short reads what that sort left there)
+    need = int(ops.lib.svr_rank_workspace_bytes(n))
+    ws = torch.empty(need, dtype=torch.uint8, device=src.device)
+
+    def sort_with(with_index):
+        rc = ops.lib.svr_sort_f32(src.data_ptr(), n, sorted_.data_ptr(), index.data_ptr() if with_index else None, ws.data_ptr(), need,
+                                  ops._stream())
+        assert rc == 0, ops.lib.svr_last_error()
+
+    for label, with_index, bytes_ in (("keys", False, (4, 0, 8)), ("pairs", True, (4, 0, 16))):
+        t = {}
+        try:
+            for stages in (3, 1, 2):
+                ops.set_option("rank_launches", stages)
+                t[stages] = timed(lambda: sort_with(with_index), args.warmup, args.reps)
+        finally:
+            ops.set_option("rank_launches", 3)                     # whatever happens: below 3 a sort stores nothing
+        h, sc, st = t[1], t[2] - t[1], t[3] - t[2]
+        print(f"# a pass of the {label:5s} sort (four passes, by difference): histogram {h / 4:6.2f} ms ({100 * h / t[3]:4.1f} %, "
+              f"{n * bytes_[0] * 4 / h / 1e9:5.2f} TB/s),  table scan {sc / 4:6.2f} ms ({100 * sc / t[3]:4.1f} %),  scatter {st / 4:6.2f} ms "
+              f"({100 * st / t[3]:4.1f} %, {n * bytes_[2] * 4 / max(st, 1e-3) / 1e9:5.2f} TB/s)")
+    del out, sorted_, index, c_lab, s_lab
+    # the whole lab route, both ways
+    fn = lambda: cf.correct(content, style, "lab", ops=ops)
+    shipped = cf.RANK_MATCH
+    res = {True: ([], 0), False: ([], 0)}
+    for flag in (True, False):
+        cf.RANK_MATCH = flag
+        res[flag] = ([], peak_above(fn))                           # (also the warm-up of that route)
+    for _ in range(args.reps):                                     # the two routes in turn: a drift of the box meets both alike
+        for flag in (True, False):
+            cf.RANK_MATCH = flag
+            res[flag][0].extend(timed_each(fn, 0, 1))
+    cf.RANK_MATCH = True
+    a, b = cf.correct(content, style, "lab", ops=ops), None
+    same = torch.equal(a, cf.correct(content, style, "lab", ops=ops))
+    cf.RANK_MATCH = False
+    b = cf.correct(content, style, "lab", ops=ops)
+    cf.RANK_MATCH = shipped
+    d = (a - b).abs_()
+    print(f"# lab route, colorfix.RANK_MATCH = True : {spread(res[True][0])}   peak above the operands {res[True][1] / 1e9:6.2f} GB   (two runs bit-equal: {same})")
+    print(f"# lab route, colorfix.RANK_MATCH = False: {spread(res[False][0])}   peak above the operands {res[False][1] / 1e9:6.2f} GB")
+    print(f"# the two routes apart: max {float(d.max()):.3e}, share > 2e-5 {float((d > 2e-5).float().mean()):.3e} (tied pixels exchange matched values)")
+    slower = sum(res[True][0]) > sum(res[False][0])
+    print(f"# -> RANK_MATCH default by the rule of DESIGN.md 7.3e: {'False (the radix route is slower)' if slower else 'True (not slower)'}"
+          f"; as shipped: {shipped}")
+
+
 def peak_above(fn):
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
@@ -57,7 +156,8 @@ def main():
     ap.add_argument("--width", type=int, default=3840)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reps", type=int, default=5)
-    ap.add_argument("--methods", default=",".join(METHODS))
+    ap.add_argument("--methods", default=",".join(METHODS), help="comma-separated; empty: none of the per-method lines")
+    ap.add_argument("--no-rank", action="store_true", help="leave the rank-matching section out")
     args = ap.parse_args()
     ops_mod, cf = (importlib.import_module(f"{PKG}.{m}") for m in ("ops", "colorfix"))
     ops = ops_mod.HipOps("cuda:0")
@@ -77,7 +177,7 @@ def main():
     print(f"# byte model: wavelet launch 3 passes = {3 * span / 1e9:.2f} GB (ideal); torch wavelet about 60 passes = {60 * span / 1e9:.0f} GB")
     print(f"{'method':18s} {'kernels ms':>11s} {'torch ms':>10s} {'ratio':>7s} {'kernels peak GB':>16s} {'torch peak GB':>14s}"
           f" {'max |k - t|':>12s} {'share > 2e-5':>13s}")
-    for m in args.methods.split(","):
+    for m in filter(None, args.methods.split(",")):
         assert cf.routes_to_device(content, style, m, ops), m
         dev = lambda: cf.correct(content, style, m, ops=ops)
         ref = lambda: cf.correct(content, style, m, ops=ops, impl="torch")
@@ -99,6 +199,9 @@ def main():
     for name, ms, passes in (("svr_wavelet_reconstruct", t_w, 3), ("svr_lab_planes", t_p, 4), ("svr_lab_merge", t_m, 4 / 3 + 1),
                              ("svr_chan_stats", t_s, 2), ("svr_chan_stats + svr_adain_apply", t_a, 4)):
         print(f"# {name:34s} {ms:8.2f} ms  model {passes * span / 1e9:5.2f} GB -> {passes * span / ms / 1e9:7.2f} TB/s of the model's bytes")
+    del base, planes, c_lab
+    if not args.no_rank and hasattr(ops, "rank_match"):
+        rank_section(ops, cf, content, style, args)
 
 
 if __name__ == "__main__":
