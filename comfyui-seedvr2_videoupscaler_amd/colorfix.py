@@ -18,8 +18,10 @@ All tensors are [B, C, H, W] in [-1, 1]; the work is HBM / sort bound (no MFMA).
 whatever device their inputs live on: they are the specification.  ``correct`` (at the end) is what the pipeline calls: on a
 HIP backend it hands the wavelet pyramid, the CIELAB conversions and AdaIN to csrc/svr_colorfix.hip (HipOps.wavelet_reconstruct /
 lab_planes / lab_merge / adain) and the rank matching of ``lab`` to csrc/svr_rank.hip (HipOps.rank_match: a stable radix sort, so
-the matched planes are ``rank_match_spec``'s bit for bit; ``RANK_MATCH = False`` puts torch's sort and scatter back); the HSV mode
-and its per-hue-bin matching of unequal sizes stay here.
+the matched planes are ``rank_match_spec``'s bit for bit; ``RANK_MATCH = False`` puts torch's sort and scatter back), and the HSV
+mode with the HSV half and blend of ``wavelet_adaptive`` to csrc/svr_hsv.hip (HipOps.hsv_planes / hue_match / hsv_merge /
+adaptive_blend: ``hsv_spec`` bit for bit, ``wavelet_adaptive_spec`` up to the sigmoid's exp; ``HSV_MATCH = False`` puts the torch
+chain back).
 """
 import torch
 import torch.nn.functional as F
@@ -254,6 +256,96 @@ def wavelet_adaptive_color_correction(content: torch.Tensor, style: torch.Tensor
     return (base * (1.0 - w) + hsv * w).to(dt)
 
 
+# ---- the specification of the HSV kernels (csrc/svr_hsv.hip): the functions above with two deliberate departures from torch,
+# both where torch's own result differs between its CPU and device kernels: ties are stable, and the nearest rank is exact.
+def _f32(x: float) -> float:
+    return torch.tensor(x, dtype=torch.float32).item()
+
+
+def hue_edges(bins: int = 12):
+    """The fp32 values a hue is compared with in ``hue_conditional_saturation_match``: torch casts the Python scalars k * (1 / bins)
+    (products in double) to fp32 before comparing an fp32 tensor with them.  -> (bins + 1 edges, the wrap edge 1 - 1 / bins)."""
+    width = 1.0 / bins
+    return tuple(_f32(k * width) for k in range(bins + 1)), _f32(1.0 - width)
+
+
+# e_0 .. e_12 and the wrap edge.  e_12 == 1.0 and the wrap edge == e_11, so bin 0 is [0, e_1) U [e_11, inf): all of bin 11 =
+# [e_11, 1.0) and every h >= 1.0 (tests/test_hsv_match.py checks both, and the fp32 neighbours of every edge).
+HUE_EDGES, HUE_WRAP_EDGE = hue_edges(12)
+
+
+def hue_bin_mask(h: torch.Tensor, k: int, bins: int = 12) -> torch.Tensor:
+    """Membership of fp32 hues in bin k, in fp32 comparisons against ``hue_edges``; a NaN hue is in no bin."""
+    edges, wrap = hue_edges(bins)
+    e = lambda v: torch.tensor(v, dtype=torch.float32)
+    if k == 0:
+        return ((h >= e(0.0)) & (h < e(edges[1]))) | (h >= e(wrap))
+    return (h >= e(edges[k])) & (h < e(edges[k + 1]))
+
+
+def nearest_rank_index(n_s: int, n_r: int) -> torch.Tensor:
+    """k -> (k * (n_r - 1)) // (n_s - 1), int64, k = 0 .. n_s - 1 (n_s >= 2): the exact quotient that ``histogram_match``'s
+    ``(torch.linspace(0, 1, n_s) * (n_r - 1)).long()`` approximates differently on every backend.  The identity for n_s == n_r."""
+    if n_s < 2 or n_r < 1:
+        raise ValueError(f"nearest_rank_index: n_s >= 2 and n_r >= 1, got {n_s} and {n_r}")
+    return (torch.arange(n_s, dtype=torch.int64) * (n_r - 1)) // (n_s - 1)
+
+
+def hue_match_spec(c_h, c_s, s_h, s_s, bins: int = 12, min_pixels: int = 100) -> torch.Tensor:
+    """``hue_conditional_saturation_match`` with each bin's ``histogram_match`` made exact -- the specification of
+    HipOps.hue_match, bit for bit.  Per bin (``hue_bin_mask``) with more than ``min_pixels`` pixels on both sides: the content
+    saturations in a stable sort of ``sort_key`` (ties to the lower flat index of the whole plane) receive the canonical sorted style
+    saturations at ``nearest_rank_index``.  Bins are applied in the order 0 .. bins - 1 and all read the original ``c_s``, so a pixel
+    of [e_11, 1) takes bin 11's value if bin 11 qualifies, else bin 0's if that qualifies, else keeps its own; so does a pixel of no
+    bin (a NaN hue)."""
+    for t in (c_h, c_s, s_h, s_s):
+        if t.dtype != torch.float32:
+            raise ValueError(f"hue_match_spec: fp32 planes, got {t.dtype}")
+    if c_h.numel() != c_s.numel() or s_h.numel() != s_s.numel():
+        raise ValueError("hue_match_spec: a hue and a saturation plane of one size per side")
+    ch, cs, sh, ss = c_h.flatten(), c_s.flatten(), s_h.flatten(), s_s.flatten()
+    out = cs.clone()
+    for k in range(bins):
+        where = hue_bin_mask(ch, k, bins).nonzero().flatten()                 # ascending flat indices
+        ref = ss[hue_bin_mask(sh, k, bins)]
+        n_s, n_r = where.numel(), ref.numel()
+        if n_s > min_pixels and n_r > min_pixels:
+            order = torch.sort(sort_key(cs[where]), stable=True).indices
+            ref_sorted = key_value(torch.sort(sort_key(ref)).values)
+            out[where[order]] = ref_sorted[nearest_rank_index(n_s, n_r)]
+    return out.reshape(c_s.shape)
+
+
+def hsv_spec(content: torch.Tensor, style: torch.Tensor) -> torch.Tensor:
+    """``hsv_saturation_histogram_match`` with ``hue_match_spec`` inside, otherwise operation for operation."""
+    style = _resize_like(style, content)
+    dt = content.dtype
+    c = rgb_to_hsv(((content.float() + 1.0) * 0.5).clamp(0.0, 1.0))
+    s = rgb_to_hsv(((style.float() + 1.0) * 0.5).clamp(0.0, 1.0))
+    sat = hue_match_spec(c[:, 0], c[:, 1], s[:, 0], s[:, 1])
+    rgb = hsv_to_rgb(torch.stack([c[:, 0], sat, c[:, 2]], dim=1)).clamp(0.0, 1.0)
+    return (rgb * 2.0 - 1.0).to(dt)
+
+
+def adaptive_weight(base, content, style, threshold: float = 0.15, sharpness: float = 5.0):
+    """The blend weight of ``wavelet_adaptive_color_correction`` and the mask inside it -> (w, mask)."""
+    s_sat = saturation_map(style)
+    w = torch.sigmoid(sharpness * (saturation_map(content) - s_sat - threshold))
+    mask = (saturation_map(base) - s_sat) > threshold * 0.5
+    return (w * mask.float()).clamp(0.0, 1.0), mask
+
+
+def wavelet_adaptive_spec(content: torch.Tensor, style: torch.Tensor, threshold: float = 0.15, sharpness: float = 5.0) -> torch.Tensor:
+    """``wavelet_adaptive_color_correction`` with ``hsv_spec`` inside, otherwise operation for operation."""
+    style = _resize_like(style, content)
+    dt = content.dtype
+    content, style = content.float(), style.float()
+    base = wavelet_reconstruction(content, style)
+    hsv = hsv_spec(content, style)
+    w, _ = adaptive_weight(base, content, style, threshold, sharpness)
+    return (base * (1.0 - w) + hsv * w).to(dt)
+
+
 METHODS = {
     "lab": lambda c, s: lab_color_transfer(c, s, luminance_weight=0.8),
     "wavelet_adaptive": wavelet_adaptive_color_correction,
@@ -270,10 +362,13 @@ _DEVICE_OPS = ("wavelet_reconstruct", "lab_planes", "lab_merge", "adain")
 def routes_to_device(content: torch.Tensor, style: torch.Tensor, method: str, ops=None) -> bool:
     """True where ``correct`` hands the method to ``ops``' kernels: a method they serve, ops that offer them, and two cuda fp32
     [T, 3, H, W] tensors of equal shape (bf16 frames of ``output_dtype=None``, CPU tensors, the torch double of the ops and a style
-    that still needs resizing all stay on METHODS)."""
-    return (method in DEVICE_METHODS and ops is not None and all(hasattr(ops, n) for n in _DEVICE_OPS)
-            and content.is_cuda and style.is_cuda and content.dtype == torch.float32 and style.dtype == torch.float32
-            and content.dim() == 4 and content.shape[1] == 3 and content.numel() > 0 and content.shape == style.shape)
+    that still needs resizing all stay on METHODS).  ``hsv`` is served by the HSV kernels alone (``_hsv_on_kernels``)."""
+    if not (ops is not None and content.is_cuda and style.is_cuda and content.dtype == torch.float32 and style.dtype == torch.float32
+            and content.dim() == 4 and content.shape[1] == 3 and content.numel() > 0 and content.shape == style.shape):
+        return False
+    if method == "hsv":                      # served by the HSV kernels alone: ops that offer all four of them, under HSV_MATCH
+        return _hsv_on_kernels(content, ops)
+    return method in DEVICE_METHODS and all(hasattr(ops, n) for n in _DEVICE_OPS)
 
 
 # Rank matching of the lab route on ops.rank_match (csrc/svr_rank.hip: stable, so the result is rank_match_spec's bit for bit)
@@ -299,9 +394,40 @@ def _lab_on_device(content, style, ops, luminance_weight: float = 0.8):
     return ops.lab_merge(c_lab[0], m_l, a, b, luminance_weight, (t, h, w))
 
 
+# The hsv method, and the HSV half and blend of wavelet_adaptive, on csrc/svr_hsv.hip where the ops offer all four calls and a plane
+# holds at most HSV_MATCH_MAX values (svr_hue_match's uint32 offsets); False: the torch chain.  The default follows the measurement
+# in DESIGN.md 7.3e.
+HSV_MATCH = True
+HSV_MATCH_MAX = 1 << 30
+_HSV_OPS = ("hsv_planes", "hue_match", "hsv_merge", "adaptive_blend")
+
+
+def _hsv_on_kernels(content, ops) -> bool:
+    t, _, h, w = content.shape
+    return HSV_MATCH and all(hasattr(ops, n) for n in _HSV_OPS) and t * h * w <= HSV_MATCH_MAX
+
+
+def _hsv_matched_planes(content, style, ops):
+    """-> (h, matched saturation, v) of the content, dense planes: hsv_spec up to its last conversion."""
+    c_hsv, s_hs = ops.hsv_planes(content, style)
+    sat = ops.hue_match(c_hsv[0], c_hsv[1], s_hs[0], s_hs[1], out=c_hsv[1])      # the saturation plane is dead after matching
+    return c_hsv[0], sat, c_hsv[2]
+
+
+def _hsv_on_device(content, style, ops):
+    """hsv_spec on the kernels, bit for bit."""
+    t, _, h, w = content.shape
+    hue, sat, v = _hsv_matched_planes(content, style, ops)
+    return ops.hsv_merge(hue, sat, v, (t, h, w))
+
+
 def _wavelet_adaptive_on_device(content, style, ops, threshold: float = 0.15, sharpness: float = 5.0):
-    """wavelet_adaptive_color_correction with its wavelet base from the kernel; the HSV half and the blend stay torch."""
+    """wavelet_adaptive_color_correction with its wavelet base from the kernel; the HSV half and the blend on the HSV kernels
+    (wavelet_adaptive_spec up to the sigmoid's exp) where ``_hsv_on_kernels`` says so, else in torch as they stand."""
     base = ops.wavelet_reconstruct(content, style)
+    if _hsv_on_kernels(content, ops):
+        hue, sat, v = _hsv_matched_planes(content, style, ops)
+        return ops.adaptive_blend(base, content, style, hue, sat, v, threshold, sharpness)
     hsv = hsv_saturation_histogram_match(content, style)
     s_sat = saturation_map(style)
     w = torch.sigmoid(sharpness * (saturation_map(content) - s_sat - threshold))
@@ -322,4 +448,6 @@ def correct(content: torch.Tensor, style: torch.Tensor, method: str, ops=None, i
         return ops.adain(content, style, 1e-5)
     if method == "lab":
         return _lab_on_device(content, style, ops)
+    if method == "hsv":
+        return _hsv_on_device(content, style, ops)
     return _wavelet_adaptive_on_device(content, style, ops)

@@ -22,6 +22,7 @@
 #include "svr_png.hip"
 #include "svr_colorfix.hip"
 #include "svr_rank.hip"
+#include "svr_hsv.hip"
 #include "svr_gguf.hip"
 
 using namespace svr;
@@ -761,26 +762,29 @@ static RankPlan rank_plan(int64_t n, void* workspace) {
     return p;
 }
 // The four passes of one sort: in -> A -> B -> A -> (out_keys, out_idx).  pairs: indices travel with the keys (the first pass
-// makes them: a key's place in ``in``).  out_mode: what the last pass stores (svr_rank.hip, rank_scatter_kernel).
-static void rank_sort_launch(const RankPlan& p, const void* in, bool pairs, int out_mode, void* out_keys, void* out_idx, hipStream_t s) {
+// makes them: a key's place in ``in``).  out_mode: what the last pass stores (svr_rank.hip, rank_scatter_kernel).  keyed: ``in``
+// holds keys already, not fp32 values, and (pairs) ``in_idx`` their indices: a run of a partition (svr_hue_match); no pass is a
+// first pass then.
+static void rank_sort_launch(const RankPlan& p, const void* in, bool pairs, int out_mode, void* out_keys, void* out_idx, hipStream_t s,
+                             bool keyed = false, const void* in_idx = nullptr) {
     const void* src_k = in;
-    const void* src_i = nullptr;
+    const void* src_i = keyed ? in_idx : nullptr;
     for (int pass = 0; pass < 32 / RANK_BITS; ++pass) {
         const bool last = pass == 32 / RANK_BITS - 1;
-        const int shift = pass * RANK_BITS, first = pass == 0, mode = last ? out_mode : 0;
+        const int shift = pass * RANK_BITS, first = pass == 0 && !keyed, mode = last ? out_mode : 0;
         void* dst_k = last ? out_keys : p.keys[pass & 1];
         void* dst_i = last ? out_idx : p.idx[pass & 1];
-        hipLaunchKernelGGL(rank_hist_kernel, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)src_k, p.n, shift, first, p.table, p.tiles_p);
+        hipLaunchKernelGGL(rank_hist_kernel<0>, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)src_k, (const float*)nullptr, p.n, shift, first, p.table, p.tiles_p);
         // (g_rank_launches < 3, tools/colorfix_timing.py only: every pass's launches up to that one, to time them by difference; the
         // passes then read what an earlier whole sort left in the workspace and the outputs are not written)
         if (g_rank_launches >= 2) hipLaunchKernelGGL(rank_scan_kernel, dim3(RANK_RADIX), dim3(RANK_THREADS), 0, s, p.table, p.tiles_p, p.totals);
         if (g_rank_launches < 3) { src_k = p.keys[pass & 1]; src_i = p.idx[pass & 1]; continue; }
         if (pairs)
-            hipLaunchKernelGGL(rank_scatter_kernel<true>, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)src_k, (const uint32_t*)src_i,
-                               p.n, shift, first, mode, (const uint32_t*)p.table, p.tiles_p, (const uint32_t*)p.totals, (uint32_t*)dst_k, (uint32_t*)dst_i);
+            hipLaunchKernelGGL((rank_scatter_kernel<true, 0>), dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)src_k, (const uint32_t*)src_i,
+                               (const float*)nullptr, p.n, shift, first, mode, (const uint32_t*)p.table, p.tiles_p, (const uint32_t*)p.totals, (uint32_t*)dst_k, (uint32_t*)dst_i);
         else
-            hipLaunchKernelGGL(rank_scatter_kernel<false>, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)src_k, (const uint32_t*)nullptr,
-                               p.n, shift, first, mode, (const uint32_t*)p.table, p.tiles_p, (const uint32_t*)p.totals, (uint32_t*)dst_k, (uint32_t*)nullptr);
+            hipLaunchKernelGGL((rank_scatter_kernel<false, 0>), dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)src_k, (const uint32_t*)nullptr,
+                               (const float*)nullptr, p.n, shift, first, mode, (const uint32_t*)p.table, p.tiles_p, (const uint32_t*)p.totals, (uint32_t*)dst_k, (uint32_t*)nullptr);
         src_k = dst_k; src_i = dst_i;
     }
 }
@@ -855,6 +859,189 @@ int svr_rank_match(const void* source, const void* reference, int64_t n, void* o
     hipLaunchKernelGGL(rank_apply_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, s, (const uint32_t*)p.idx[1], (const uint32_t*)p.ref,
                        p.n, (uint32_t*)out);
     return check(hipGetLastError(), "svr_rank_match");
+}
+
+// ---- the HSV half (svr_hsv.hip)
+int svr_hsv_planes(const void* content, const int64_t* content_strides, const void* style, const int64_t* style_strides, void* c_hsv,
+                   void* s_hs, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    PixStrides cs, ss;
+    SVR_COLORFIX_PTR("svr_hsv_planes", content);
+    SVR_COLORFIX_PTR("svr_hsv_planes", style);
+    SVR_COLORFIX_PTR("svr_hsv_planes", c_hsv);
+    SVR_COLORFIX_PTR("svr_hsv_planes", s_hs);
+    SVR_COLORFIX_STRIDES("svr_hsv_planes", content_strides, false, cs);
+    SVR_COLORFIX_STRIDES("svr_hsv_planes", style_strides, false, ss);
+    SVR_COLORFIX_GEOMETRY("svr_hsv_planes");
+    const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
+    const dim3 grid((unsigned)((int64_t)T * H * chunks), 2);
+    hipLaunchKernelGGL(hsv_planes_kernel, grid, dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream, (const float*)content, cs,
+                       (const float*)style, ss, (float*)c_hsv, (float*)s_hs, H, W, chunks, (int64_t)T * H * W);
+    return check(hipGetLastError(), "svr_hsv_planes");
+}
+
+int svr_hsv_merge(const void* h, const void* sat, const void* v, void* out, const int64_t* out_strides, int32_t T, int32_t H, int32_t W,
+                  int32_t kind, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    PixStrides os;
+    SVR_COLORFIX_PTR("svr_hsv_merge", h);
+    SVR_COLORFIX_PTR("svr_hsv_merge", sat);
+    SVR_COLORFIX_PTR("svr_hsv_merge", v);
+    SVR_COLORFIX_PTR("svr_hsv_merge", out);
+    SVR_COLORFIX_STRIDES("svr_hsv_merge", out_strides, true, os);
+    SVR_COLORFIX_GEOMETRY("svr_hsv_merge");
+    const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
+    hipLaunchKernelGGL(hsv_merge_kernel, dim3((unsigned)((int64_t)T * H * chunks)), dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream,
+                       (const float*)h, (const float*)sat, (const float*)v, (float*)out, os, H, W, chunks);
+    return check(hipGetLastError(), "svr_hsv_merge");
+}
+
+int svr_adaptive_blend(const void* base, const int64_t* base_strides, const void* content, const int64_t* content_strides,
+                       const void* style, const int64_t* style_strides, const void* h, const void* sat, const void* v, double threshold,
+                       double sharpness, void* out, const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind,
+                       void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    PixStrides bs, cs, ss, os;
+    SVR_COLORFIX_PTR("svr_adaptive_blend", base);
+    SVR_COLORFIX_PTR("svr_adaptive_blend", content);
+    SVR_COLORFIX_PTR("svr_adaptive_blend", style);
+    SVR_COLORFIX_PTR("svr_adaptive_blend", h);
+    SVR_COLORFIX_PTR("svr_adaptive_blend", sat);
+    SVR_COLORFIX_PTR("svr_adaptive_blend", v);
+    SVR_COLORFIX_PTR("svr_adaptive_blend", out);
+    SVR_COLORFIX_STRIDES("svr_adaptive_blend", base_strides, false, bs);
+    SVR_COLORFIX_STRIDES("svr_adaptive_blend", content_strides, false, cs);
+    SVR_COLORFIX_STRIDES("svr_adaptive_blend", style_strides, false, ss);
+    SVR_COLORFIX_STRIDES("svr_adaptive_blend", out_strides, true, os);
+    if (!(threshold == threshold)) SVR_COLORFIX_REFUSE("svr_adaptive_blend", "threshold", "is not a number");
+    if (!(sharpness == sharpness)) SVR_COLORFIX_REFUSE("svr_adaptive_blend", "sharpness", "is not a number");
+    SVR_COLORFIX_GEOMETRY("svr_adaptive_blend");
+    const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
+    hipLaunchKernelGGL(adaptive_blend_kernel, dim3((unsigned)((int64_t)T * H * chunks)), dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream,
+                       (const float*)base, bs, (const float*)content, cs, (const float*)style, ss, (const float*)h, (const float*)sat,
+                       (const float*)v, (float)threshold, (float)(threshold * 0.5), (float)sharpness, (float*)out, os, H, W, chunks);
+    return check(hipGetLastError(), "svr_adaptive_blend");
+}
+
+// Hue-conditional rank matching.  Workspace (bytes; n4 = 4 * n rounded up to 256): [source keys by class n4][source indices by class
+// n4][source keys, bin 0 first n4][source indices, bin 0 first n4][reference keys by class n4][class counts: source 1024, reference
+// 1024, bin-0 partition 1024][the workspace of one sort of n keys: svr_rank_workspace_bytes(n)].
+constexpr int HUE_MIN_PIXELS = 100;                 // a bin is matched when both sides hold MORE pixels than this
+struct HuePlan {
+    RankPlan sort;                                  // buffers, table and geometry of a sort of all n keys
+    char *cls_k, *cls_i, *bin0_k, *bin0_i, *ref_k;
+    uint32_t *tot_src, *tot_ref, *tot_bin0;
+    int64_t bytes;
+};
+static HuePlan hue_plan(int64_t n, void* workspace) {
+    HuePlan p;
+    const int64_t n4 = (4 * n + 255) / 256 * 256;
+    char* w = (char*)workspace;
+    p.cls_k = w; p.cls_i = w + n4; p.bin0_k = w + 2 * n4; p.bin0_i = w + 3 * n4; p.ref_k = w + 4 * n4;
+    p.tot_src = (uint32_t*)(w + 5 * n4);
+    p.tot_ref = p.tot_src + RANK_RADIX;
+    p.tot_bin0 = p.tot_ref + RANK_RADIX;
+    p.sort = rank_plan(n, w + 5 * n4 + 3 * RANK_RADIX * 4);
+    p.bytes = 5 * n4 + 3 * RANK_RADIX * 4 + p.sort.bytes;
+    return p;
+}
+// the sort of a run of m <= n keys in the buffers of the sort of n: the same addresses whatever m is (a run's sorted reference stays
+// where the next sort does not write), its own tile counts
+static RankPlan hue_run_plan(const RankPlan& whole, uint32_t m) {
+    RankPlan p = whole;
+    p.n = m;
+    p.groups = (uint32_t)(((int64_t)m + (int64_t)RANK_GROUP * RANK_TILE - 1) / ((int64_t)RANK_GROUP * RANK_TILE));
+    p.tiles_p = p.groups * RANK_GROUP;
+    return p;
+}
+// one pass whose digit is the hue's (svr_rank.hip, DIGIT 1: the class, or 2: outside bin 0): keys (and flat indices) of ``sat`` in the
+// stable order of the digit
+#define SVR_HUE_SCATTER(PAIRS, DIGIT, OUT_IDX) \
+    hipLaunchKernelGGL((rank_scatter_kernel<PAIRS, DIGIT>), dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)sat, \
+                       (const uint32_t*)nullptr, (const float*)hue, p.n, 0, 1, 0, (const uint32_t*)p.table, p.tiles_p, \
+                       (const uint32_t*)totals, (uint32_t*)out_keys, (uint32_t*)(OUT_IDX))
+static void hue_partition_launch(const RankPlan& p, bool by_class, const void* sat, const void* hue, bool pairs, uint32_t* totals,
+                                 void* out_keys, void* out_idx, hipStream_t s) {
+    if (by_class)
+        hipLaunchKernelGGL(rank_hist_kernel<1>, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)sat, (const float*)hue, p.n, 0, 1,
+                           p.table, p.tiles_p);
+    else
+        hipLaunchKernelGGL(rank_hist_kernel<2>, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)sat, (const float*)hue, p.n, 0, 1,
+                           p.table, p.tiles_p);
+    hipLaunchKernelGGL(rank_scan_kernel, dim3(RANK_RADIX), dim3(RANK_THREADS), 0, s, p.table, p.tiles_p, totals);
+    if (!by_class) SVR_HUE_SCATTER(true, 2, out_idx);             // (the partition of bin 0 serves the source side only)
+    else if (pairs) SVR_HUE_SCATTER(true, 1, out_idx);
+    else SVR_HUE_SCATTER(false, 1, nullptr);
+}
+#undef SVR_HUE_SCATTER
+
+int64_t svr_hue_match_workspace_bytes(int64_t n) {
+    if (n < 1 || n > RANK_MAX_N) return 0;
+    return hue_plan(n, nullptr).bytes;
+}
+
+int svr_hue_match(const void* c_h, const void* c_s, const void* s_h, const void* s_s, int64_t n, void* out, void* workspace,
+                  int64_t workspace_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    SVR_COLORFIX_PTR("svr_hue_match", c_h);
+    SVR_COLORFIX_PTR("svr_hue_match", c_s);
+    SVR_COLORFIX_PTR("svr_hue_match", s_h);
+    SVR_COLORFIX_PTR("svr_hue_match", s_s);
+    SVR_COLORFIX_PTR("svr_hue_match", out);
+    SVR_COLORFIX_PTR("svr_hue_match", workspace);
+    if (g_rank_launches != 3) SVR_COLORFIX_REFUSE("svr_hue_match", "", "svr_set_option(\"rank_launches\") below 3 serves svr_sort_f32 only");
+    if (n < 1 || n > RANK_MAX_N) SVR_COLORFIX_REFUSE("svr_hue_match", "n", "must be in [1, 2^30]");
+    if ((uintptr_t)workspace % 16) SVR_COLORFIX_REFUSE("svr_hue_match", "workspace", "is not aligned to 16 bytes");
+    const int64_t need = svr_hue_match_workspace_bytes(n);
+    if (workspace_bytes < need) SVR_COLORFIX_REFUSE("svr_hue_match", "workspace_bytes", "is below svr_hue_match_workspace_bytes(n)");
+#define SVR_HUE_OFF_WORKSPACE(a) do { if (rank_overlap(a, 4 * n, workspace, need)) SVR_COLORFIX_REFUSE("svr_hue_match", #a, "overlaps workspace"); } while (0)
+    SVR_RANK_ALIGNED("svr_hue_match", c_h);
+    SVR_RANK_ALIGNED("svr_hue_match", c_s);
+    SVR_RANK_ALIGNED("svr_hue_match", s_h);
+    SVR_RANK_ALIGNED("svr_hue_match", s_s);
+    SVR_RANK_ALIGNED("svr_hue_match", out);
+    SVR_RANK_APART("svr_hue_match", out, c_h);
+    if (out != c_s) SVR_RANK_APART("svr_hue_match", out, c_s);                 // out == c_s: the saturation plane is matched in place
+    SVR_RANK_APART("svr_hue_match", out, s_h);
+    SVR_RANK_APART("svr_hue_match", out, s_s);
+    SVR_HUE_OFF_WORKSPACE(c_h);
+    SVR_HUE_OFF_WORKSPACE(c_s);
+    SVR_HUE_OFF_WORKSPACE(s_h);
+    SVR_HUE_OFF_WORKSPACE(s_s);
+    SVR_HUE_OFF_WORKSPACE(out);
+#undef SVR_HUE_OFF_WORKSPACE
+    const HuePlan p = hue_plan(n, workspace);
+    const hipStream_t s = (hipStream_t)stream;
+    hue_partition_launch(p.sort, true, c_s, c_h, true, p.tot_src, p.cls_k, p.cls_i, s);
+    hue_partition_launch(p.sort, true, s_s, s_h, false, p.tot_ref, p.ref_k, nullptr, s);
+    if (int rc = check(hipGetLastError(), "svr_hue_match")) return rc;
+    // the one read of the call: 2 x 256 class counts (source, reference), which decide the bins that are sorted and their runs
+    uint32_t counts[2 * RANK_RADIX];
+    if (int rc = check(hipMemcpyAsync(counts, p.tot_src, sizeof(counts), hipMemcpyDeviceToHost, s), "svr_hue_match: class counts")) return rc;
+    if (int rc = check(hipStreamSynchronize(s), "svr_hue_match: class counts")) return rc;
+    const uint32_t *n_src = counts, *n_ref = counts + RANK_RADIX;
+    uint32_t at_src[HUE_CLASSES + 1] = {0}, at_ref[HUE_CLASSES + 1] = {0};
+    for (int d = 0; d < HUE_CLASSES; ++d) { at_src[d + 1] = at_src[d] + n_src[d]; at_ref[d + 1] = at_ref[d] + n_ref[d]; }
+    if (at_src[HUE_CLASSES] != (uint32_t)n || at_ref[HUE_CLASSES] != (uint32_t)n)
+        SVR_COLORFIX_REFUSE("svr_hue_match", "", "the class counts read back do not add up to n");
+    if (out != c_s)
+        if (int rc = check(hipMemcpyAsync(out, c_s, (size_t)(4 * n), hipMemcpyDeviceToDevice, s), "svr_hue_match: out = c_s")) return rc;
+    for (int bin = 0; bin < HUE_BINS; ++bin) {
+        // digits of the bin's classes (svr_rank.hip, rank_hue_class): bin 0 = digits 0..2, bin 11 = digit 2, bin k = digit k + 2
+        const int d0 = bin == 0 ? 0 : (bin == HUE_BINS - 1 ? 2 : bin + 2), d1 = bin == 0 ? 3 : d0 + 1;
+        const uint32_t m_src = at_src[d1] - at_src[d0], m_ref = at_ref[d1] - at_ref[d0];
+        if (m_src <= (uint32_t)HUE_MIN_PIXELS || m_ref <= (uint32_t)HUE_MIN_PIXELS) continue;
+        const char *run_k = p.cls_k + 4 * (int64_t)at_src[d0], *run_i = p.cls_i + 4 * (int64_t)at_src[d0];
+        if (bin == 0) {                            // its three classes in the order of the plane: the head of a partition of its own
+            hue_partition_launch(p.sort, false, c_s, c_h, true, p.tot_bin0, p.bin0_k, p.bin0_i, s);
+            run_k = p.bin0_k; run_i = p.bin0_i;
+        }
+        rank_sort_launch(hue_run_plan(p.sort, m_ref), p.ref_k + 4 * (int64_t)at_ref[d0], false, 1, p.sort.ref, nullptr, s, true);
+        rank_sort_launch(hue_run_plan(p.sort, m_src), run_k, true, 2, nullptr, p.sort.idx[1], s, true, run_i);
+        hipLaunchKernelGGL(hue_apply_kernel, dim3(blocks_for(m_src, 256)), dim3(256), 0, s, (const uint32_t*)p.sort.idx[1],
+                           (const uint32_t*)p.sort.ref, m_src, m_ref, (uint32_t*)out);
+    }
+    return check(hipGetLastError(), "svr_hue_match");
 }
 #undef SVR_RANK_OFF_WORKSPACE
 #undef SVR_RANK_APART

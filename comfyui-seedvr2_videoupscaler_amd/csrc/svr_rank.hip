@@ -20,6 +20,11 @@
 //            A lane past the end of the data stays in every ballot and barrier, flagged empty; only whole tiles past the end are
 //            left (a workgroup-uniform test before the tile's first barrier).
 //   rank_apply_kernel      out[index[k]] = value[k], four consecutive k per lane.
+//   DIGIT    where a pass takes its digit from.  0: bits [shift, shift + 8) of the key (the sort).  1 and 2: the hue of the pixel the
+//            key belongs to (rank_hue_digit: the hue class, or "outside bin 0"), read from a plane beside the keys: the one-pass
+//            stable partitions of the hue-conditional matching (svr_hsv.hip).  Such a pass is a first pass (it makes the key and the
+//            index from the element's place), counts and ranks exactly as a sort's pass does, and keeps each key's digit in LDS
+//            beside it, since the digit cannot be read back from the key.
 // Offsets are uint32: n <= 2^30 (svr_api.hip refuses more), so positions, byte offsets of 4-byte elements and the table's
 // 256 * ceil16(tiles) entries all stay below 2^32.
 #include "svr_common.h"
@@ -48,6 +53,27 @@ SVR_DEVICE uint32_t rank_key_bits(uint32_t b) {
 }
 SVR_DEVICE uint32_t rank_value_bits(uint32_t k) { return (k & 0x80000000u) ? (k ^ 0x80000000u) : ~k; }
 
+// Hue bins of colorfix.hue_match_spec (HUE_EDGES): e_k = float32(k * (1.0 / 12)), the product taken in double as Python takes it; bin k
+// = [e_k, e_k+1) in fp32 comparisons, bin 11 ends at 1.0, and bin 0 also holds every h >= e_11 (float32(1 - 1/12) == e_11).  A hue is
+// in one CLASS: digit 0: h >= 1.0 (bin 0 only), 1: [0, e_1) (bin 0 only; -0.0 is in it), 2: [e_11, 1.0) (bins 0 and 11), 2 + k: bin k
+// of 1..10, 13: no bin (NaN, h < 0).  So the classes of bin 0 are digits 0..2 and stand together after a partition by class.
+constexpr int HUE_BINS = 12;
+constexpr int HUE_CLASSES = 14;
+SVR_DEVICE uint32_t rank_hue_class(float h) {
+    if (!(h >= 0.0f)) return 13u;
+    if (h >= 1.0f) return 0u;
+    uint32_t k = 0;
+#pragma unroll
+    for (int e = 1; e < HUE_BINS; ++e) k += h >= (float)(e * (1.0 / 12)) ? 1u : 0u;
+    return k == 0u ? 1u : (k == 11u ? 2u : k + 2u);
+}
+// DIGIT 1: the class; DIGIT 2: 0 inside bin 0, 1 outside (a stable partition that leaves bin 0 in the order of the plane)
+template <int DIGIT>
+SVR_DEVICE uint32_t rank_hue_digit(float h) {
+    const uint32_t c = rank_hue_class(h);
+    return DIGIT == 1 ? c : (c <= 2u ? 0u : 1u);
+}
+
 // exclusive prefix of ``v`` over the workgroup's 256 threads (and the sum of all); wave_tot: RANK_WAVES words of LDS
 SVR_DEVICE uint32_t rank_block_scan(uint32_t v, uint32_t* wave_tot, uint32_t& total) {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -72,7 +98,9 @@ SVR_DEVICE uint32_t rank_block_scan(uint32_t v, uint32_t* wave_tot, uint32_t& to
 }
 
 // grid: ceil(tiles / 16).  table: [256][tiles_p] with tiles_p = tiles rounded up to 16 (the columns past the last tile get zeros).
-__global__ __launch_bounds__(RANK_THREADS) void rank_hist_kernel(const uint32_t* __restrict__ in, uint32_t n, int shift, int first,
+template <int DIGIT>
+__global__ __launch_bounds__(RANK_THREADS) void rank_hist_kernel(const uint32_t* __restrict__ in, const float* __restrict__ hue,
+                                                                 uint32_t n, int shift, int first,
                                                                  uint32_t* __restrict__ table, uint32_t tiles_p) {
     __shared__ uint32_t hist[RANK_GROUP * RANK_RADIX];
     const uint32_t tid = threadIdx.x;
@@ -88,9 +116,15 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_hist_kernel(const uint32_t*
         for (int j = 0; j < RANK_KPT; ++j) {
             const uint32_t g = base + (uint32_t)j * RANK_THREADS + tid;
             if (g < n) {
-                uint32_t k = in[g];
-                if (first) k = rank_key_bits(k);
-                atomicAdd(&hist[tt * RANK_RADIX + ((k >> shift) & (RANK_RADIX - 1))], 1u);
+                uint32_t d;
+                if constexpr (DIGIT == 0) {
+                    uint32_t k = in[g];
+                    if (first) k = rank_key_bits(k);
+                    d = (k >> shift) & (RANK_RADIX - 1);
+                } else {
+                    d = rank_hue_digit<DIGIT>(hue[g]);
+                }
+                atomicAdd(&hist[tt * RANK_RADIX + d], 1u);
             }
         }
     }
@@ -130,14 +164,16 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_scan_kernel(uint32_t* __res
 
 // out_mode 0: keys (and indices) as they are, for the next pass; 1: the keys' canonical values (and indices): the last pass of a
 // sort; 2: indices only: the last pass over the source plane of a rank matching, whose sorted keys nobody reads
-template <bool PAIRS>
+template <bool PAIRS, int DIGIT>
 __global__ __launch_bounds__(RANK_THREADS) void rank_scatter_kernel(const uint32_t* __restrict__ in_keys, const uint32_t* __restrict__ in_idx,
+                                                                    const float* __restrict__ hue,
                                                                     uint32_t n, int shift, int first, int out_mode,
                                                                     const uint32_t* __restrict__ table, uint32_t tiles_p,
                                                                     const uint32_t* __restrict__ totals,
                                                                     uint32_t* __restrict__ out_keys, uint32_t* __restrict__ out_idx) {
     __shared__ uint32_t skey[RANK_TILE];
     __shared__ uint32_t sidx[PAIRS ? RANK_TILE : 1];
+    __shared__ unsigned char sdig[DIGIT ? RANK_TILE : 1];         // DIGIT != 0: the digit of the key at each place of the tile
     __shared__ uint32_t cnt[RANK_WAVES * RANK_RADIX];             // per wave and digit: counts, then the wave's first place in the tile
     __shared__ uint32_t gdelta[RANK_RADIX];                       // per digit: global place - place in the tile
     __shared__ uint32_t wave_tot[RANK_WAVES];
@@ -154,22 +190,25 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_scatter_kernel(const uint32
         const uint32_t toff = table[tid * tiles_p + tile];        // keys of digit tid in the tiles before this one
 #pragma unroll
         for (int i = 0; i < RANK_WAVES; ++i) cnt[i * RANK_RADIX + tid] = 0;
-        uint32_t key[RANK_KPT], idx[PAIRS ? RANK_KPT : 1], r[RANK_KPT];
+        uint32_t key[RANK_KPT], idx[PAIRS ? RANK_KPT : 1], r[RANK_KPT], dig[DIGIT ? RANK_KPT : 1];
 #pragma unroll
         for (int j = 0; j < RANK_KPT; ++j) {
             const uint32_t p = w * RANK_WAVE_KEYS + j * 64 + lane;
             key[j] = 0xFFFFFFFFu;
             if constexpr (PAIRS) idx[j] = 0;
+            if constexpr (DIGIT != 0) dig[j] = RANK_RADIX - 1;
             if (p < nvalid) {
                 const uint32_t k = in_keys[tbase + p];
                 key[j] = first ? rank_key_bits(k) : k;
                 if constexpr (PAIRS) idx[j] = first ? tbase + p : in_idx[tbase + p];
+                if constexpr (DIGIT != 0) dig[j] = rank_hue_digit<DIGIT>(hue[tbase + p]);
             }
         }
         __syncthreads();                                          // the counters are zero
 #pragma unroll
         for (int j = 0; j < RANK_KPT; ++j) {
-            const uint32_t d = (key[j] >> shift) & (RANK_RADIX - 1);
+            uint32_t d = (key[j] >> shift) & (RANK_RADIX - 1);
+            if constexpr (DIGIT != 0) d = dig[j];
             const bool valid = w * RANK_WAVE_KEYS + j * 64 + lane < nvalid;
             uint64_t m = __ballot(valid);                         // an empty lane votes in every ballot and is in no mask
 #pragma unroll
@@ -200,9 +239,12 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_scatter_kernel(const uint32
 #pragma unroll
         for (int j = 0; j < RANK_KPT; ++j) {
             if (w * RANK_WAVE_KEYS + j * 64 + lane < nvalid) {
-                const uint32_t at = wcnt[(key[j] >> shift) & (RANK_RADIX - 1)] + r[j];
+                uint32_t d = (key[j] >> shift) & (RANK_RADIX - 1);
+                if constexpr (DIGIT != 0) d = dig[j];
+                const uint32_t at = wcnt[d] + r[j];
                 skey[at] = key[j];
                 if constexpr (PAIRS) sidx[at] = idx[j];
+                if constexpr (DIGIT != 0) sdig[at] = (unsigned char)d;
             }
         }
         __syncthreads();
@@ -211,7 +253,9 @@ __global__ __launch_bounds__(RANK_THREADS) void rank_scatter_kernel(const uint32
             const uint32_t q = (uint32_t)j * RANK_THREADS + tid;
             if (q < nvalid) {
                 const uint32_t k = skey[q];
-                const uint32_t dst = gdelta[(k >> shift) & (RANK_RADIX - 1)] + q;
+                uint32_t d = (k >> shift) & (RANK_RADIX - 1);
+                if constexpr (DIGIT != 0) d = sdig[q];
+                const uint32_t dst = gdelta[d] + q;
                 if (out_mode != 2) out_keys[dst] = out_mode ? rank_value_bits(k) : k;
                 if constexpr (PAIRS) out_idx[dst] = sidx[q];
             }

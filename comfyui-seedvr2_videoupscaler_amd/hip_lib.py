@@ -114,6 +114,12 @@ SYMBOLS = {
     "svr_rank_geometry": (C.c_int, [C.POINTER(C.c_int32)]),
     "svr_sort_f32": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _vp]),
     "svr_rank_match": (C.c_int, [_vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "svr_hsv_planes": (C.c_int, [_vp, _strides, _vp, _strides, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "svr_hue_match_workspace_bytes": (C.c_int64, [_i64]),
+    "svr_hue_match": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
+    "svr_hsv_merge": (C.c_int, [_vp, _vp, _vp, _vp, _strides, _i32, _i32, _i32, _i32, _vp]),
+    "svr_adaptive_blend": (C.c_int, [_vp, _strides, _vp, _strides, _vp, _strides, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _strides,
+                                     _i32, _i32, _i32, _i32, _vp]),
     "svr_unpack_frames": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_dequant_gguf": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp]),
     "svr_set_option": (C.c_int, [C.c_char_p, _i32]),

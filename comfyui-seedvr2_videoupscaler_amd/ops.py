@@ -782,6 +782,78 @@ class HipOps:
                       "svr_rank_match")
         return out
 
+    # (colorfix.hsv_spec / wavelet_adaptive_spec / hue_match_spec are the specification; csrc/svr_hsv.hip.)
+    def _plane(self, t, n, name):
+        self._chk(t, torch.float32, name)
+        if t.numel() != n:
+            raise ValueError(f"{name} must hold {n} values, got {tuple(t.shape)}")
+        return t
+
+    def hsv_planes(self, content, style, c_hsv=None, s_hs=None):
+        """[-1, 1] frames -> colorfix.rgb_to_hsv of ((x + 1) * 0.5).clamp(0, 1), bit for bit: dense fp32 planes, content
+        [3, T*H*W] (h, s, v) and style [2, T*H*W] (h, s)."""
+        cs = self._pixels(content, "hsv_planes: content")
+        ss = self._pixels(style, "hsv_planes: style", content.shape)
+        T, _, H, W = content.shape
+        planes = []
+        for t, k, name in ((c_hsv, 3, "hsv_planes: c_hsv"), (s_hs, 2, "hsv_planes: s_hs")):
+            if t is None:
+                t = torch.empty((k, T * H * W), dtype=torch.float32, device=self.device)
+            self._chk(t, torch.float32, name)
+            if tuple(t.shape) != (k, T * H * W):
+                raise ValueError(f"{name} must be fp32 {(k, T * H * W)}, got {tuple(t.shape)}")
+            planes.append(t)
+        hip_lib.check(self.lib.svr_hsv_planes(_ptr(content), cs, _ptr(style), ss, _ptr(planes[0]), _ptr(planes[1]), T, H, W, 1,
+                                              self._stream()), "svr_hsv_planes")
+        return planes[0], planes[1]
+
+    def hue_match(self, c_h, c_s, s_h, s_s, out=None):
+        """colorfix.hue_match_spec (12 bins, more than 100 pixels on both sides), bit for bit: four fp32 planes, content and style
+        each of one size; ``out`` may be ``c_s`` itself.  Reads the class counts on the host: one synchronisation of the stream."""
+        n = c_s.numel()
+        for t, name in ((c_h, "c_h"), (c_s, "c_s"), (s_h, "s_h"), (s_s, "s_s")):
+            self._plane(t, n, f"hue_match: {name}")
+        if hip_lib.OPTIONS.get("rank_launches", 3) != 3:
+            raise hip_lib.HipLibraryError("hue_match: set_option('rank_launches') is below 3 (a measurement setting); set it back to 3")
+        if out is None:
+            out = torch.empty_like(c_s)
+        self._chk(out, torch.float32, "hue_match: out")
+        if tuple(out.shape) != tuple(c_s.shape):
+            raise ValueError(f"hue_match: out must be fp32 {tuple(c_s.shape)}, got {tuple(out.shape)}")
+        nbytes = int(self.lib.svr_hue_match_workspace_bytes(n))
+        if nbytes <= 0:
+            raise ValueError(f"hue_match: between 1 and 2^30 elements per plane, got {n}")
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        hip_lib.check(self.lib.svr_hue_match(_ptr(c_h), _ptr(c_s), _ptr(s_h), _ptr(s_s), n, _ptr(out), _ptr(ws), nbytes, self._stream()),
+                      "svr_hue_match")
+        return out
+
+    def hsv_merge(self, h, sat, v, shape, out=None):
+        """colorfix.hsv_to_rgb(h, sat, v) clamped to [0, 1], * 2 - 1, bit for bit.  Dense fp32 planes [T*H*W]; ``shape`` = (T, H, W);
+        -> [T, 3, H, W]."""
+        T, H, W = (int(x) for x in shape)
+        for t, name in ((h, "h"), (sat, "sat"), (v, "v")):
+            self._plane(t, T * H * W, f"hsv_merge: {name}")
+        like = torch.empty((T, 3, H, W), dtype=torch.float32, device="meta")
+        out, os_ = self._pixels_out(out, like, "hsv_merge: out")
+        hip_lib.check(self.lib.svr_hsv_merge(_ptr(h), _ptr(sat), _ptr(v), _ptr(out), os_, T, H, W, 1, self._stream()), "svr_hsv_merge")
+        return out
+
+    def adaptive_blend(self, base, content, style, h, sat, v, threshold=0.15, sharpness=5.0, out=None):
+        """The blend of colorfix.wavelet_adaptive_color_correction: ``base`` (the wavelet result) and the HSV pixel of (h, sat, v)
+        mixed by w = sigmoid(sharpness * (sat(content) - sat(style) - threshold)), gated by sat(base) - sat(style) > threshold / 2."""
+        bs = self._pixels(base, "adaptive_blend: base")
+        cs = self._pixels(content, "adaptive_blend: content", base.shape)
+        ss = self._pixels(style, "adaptive_blend: style", base.shape)
+        T, _, H, W = base.shape
+        for t, name in ((h, "h"), (sat, "sat"), (v, "v")):
+            self._plane(t, T * H * W, f"adaptive_blend: {name}")
+        out, os_ = self._pixels_out(out, base, "adaptive_blend: out", base, content, style)
+        hip_lib.check(self.lib.svr_adaptive_blend(_ptr(base), bs, _ptr(content), cs, _ptr(style), ss, _ptr(h), _ptr(sat), _ptr(v),
+                                                  float(threshold), float(sharpness), _ptr(out), os_, T, H, W, 1, self._stream()),
+                      "svr_adaptive_blend")
+        return out
+
     # ------------------------------------------------------------------ packed input frames
     def unpack_frames(self, packed, fmt, T, H, W, C, matrix="bt709", range_="tv", out=None):
         """Input frames widened on the device (frameio_in.py is the specification; csrc/svr_frame_unpack.hip): ``packed`` a dense

@@ -59,6 +59,9 @@
  *   svr_wavelet_reconstruct, svr_lab_*,        element accesses only: pixel operands by four element strides (input >= 0, output
  *     svr_chan_stats, svr_adain_apply          >= 1), planes and stats dense fp32; svr_chan_stats' workspace 8
  *   svr_sort_f32, svr_rank_match               operands 4 (dense [n]), workspace 16
+ *   svr_hsv_planes, svr_hsv_merge,             as svr_lab_*: pixel operands by four element strides, planes dense fp32, element
+ *     svr_adaptive_blend                       accesses only
+ *   svr_hue_match                              planes 4 (dense [n]), workspace 16
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -88,6 +91,8 @@ extern "C" {
  * svr_colorfix_workspace_bytes() (colour correction after the decode: wavelet, LAB and AdaIN on the device).  New symbols only.
  * v9, additive: + svr_sort_f32() / svr_rank_match() / svr_rank_workspace_bytes() / svr_rank_geometry() (a stable radix sort of fp32
  * keys and the rank matching of the LAB colour transfer on top of it).  New symbols only.
+ * v9, additive: + svr_hsv_planes() / svr_hue_match() / svr_hue_match_workspace_bytes() / svr_hsv_merge() / svr_adaptive_blend() (the
+ * HSV half of the colour correction: the `hsv` method and the HSV half and blend of `wavelet_adaptive`).  New symbols only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -480,6 +485,40 @@ int svr_rank_geometry(int32_t* out2);
 int svr_sort_f32(const void* keys, int64_t n, void* sorted, void* index, void* workspace, int64_t workspace_bytes, void* stream);
 int svr_rank_match(const void* source, const void* reference, int64_t n, void* out, void* workspace, int64_t workspace_bytes,
                    void* stream);
+
+/* The HSV half (colorfix.hsv_spec / wavelet_adaptive_spec / hue_match_spec are the specification; csrc/svr_hsv.hip).  Pixel operands,
+ * T, H, W, kind and their checks are those of the colour-correction calls above; planes are dense fp32 [T*H*W].
+ * svr_hsv_planes(): content, style in [-1, 1] -> ((x + 1) * 0.5) clamped to [0, 1] -> colorfix.rgb_to_hsv in its operation order
+ *   (IEEE divisions, no contraction) -> c_hsv: dense planar fp32 [3, T*H*W] (h, s, v), s_hs: [2, T*H*W] (h, s).  BIT FOR BIT the
+ *   CPU run for finite and infinite inputs (a NaN input is not pinned).  One launch.
+ * svr_hue_match(): colorfix.hue_match_spec BIT FOR BIT with bins = 12, min_pixels = 100: for every hue bin k (fp32 comparisons
+ *   against colorfix.HUE_EDGES; bin 0 also holds every h >= e_11) with more than 100 pixels in c_h and in s_h, the content
+ *   saturations of the bin are rank-matched to the style saturations of the bin: the j-th smallest (stable: ties to the lower flat
+ *   index of the whole plane) of n_s receives the sorted reference value of rank (j * (n_r - 1)) / (n_s - 1), an exact integer
+ *   quotient.  Bins are applied in the order 0..11 and all read the original c_s; a pixel of no qualifying bin keeps its value.
+ *   out may be c_s itself (the same pointer); otherwise no two of out, the inputs and the workspace may overlap.  1 <= n <= 2^30.
+ *   Launches: two partitions by hue class (one radix pass each: 3 launches), then per qualifying bin two four-pass sorts and one
+ *   scatter (25 launches; bin 0 three more for a partition of its own): at most 6 + 3 + 12 * 25 launches and one device-to-device
+ *   copy.  The class counts that decide which bins qualify are READ BY THE HOST: one 2 KiB device-to-host copy and one
+ *   synchronisation of `stream` per call, so the call cannot be captured into a graph.
+ * svr_hue_match_workspace_bytes(n): 5 * roundup(4 n, 256) + 3072 + svr_rank_workspace_bytes(n) (below 48 n + 131072); <= 0: n is
+ *   refused.  16-byte aligned.
+ * svr_hsv_merge(): colorfix.hsv_to_rgb(h, sat, v) in its operation order, clamped to [0, 1], * 2 - 1 -> out.  BIT FOR BIT.  One launch.
+ * svr_adaptive_blend(): the blend of colorfix.wavelet_adaptive_color_correction: with hsv = svr_hsv_merge's pixel, s = the
+ *   saturation map of ((x + 1) * 0.5) clamped, w = sigmoid(sharpness * (s(content) - s(style) - threshold)) where s(base) - s(style) >
+ *   threshold * 0.5 and 0 elsewhere, out = base * (1 - w) + hsv * w.  threshold, threshold * 0.5 and sharpness are rounded to fp32
+ *   from fp64 once.  The saturation maps and the mask are exact; the sigmoid is 1 / (1 + expf(-x)).  One launch. */
+int svr_hsv_planes(const void* content, const int64_t* content_strides, const void* style, const int64_t* style_strides, void* c_hsv,
+                   void* s_hs, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream);
+int64_t svr_hue_match_workspace_bytes(int64_t n);
+int svr_hue_match(const void* c_h, const void* c_s, const void* s_h, const void* s_s, int64_t n, void* out, void* workspace,
+                  int64_t workspace_bytes, void* stream);
+int svr_hsv_merge(const void* h, const void* sat, const void* v, void* out, const int64_t* out_strides, int32_t T, int32_t H, int32_t W,
+                  int32_t kind, void* stream);
+int svr_adaptive_blend(const void* base, const int64_t* base_strides, const void* content, const int64_t* content_strides,
+                       const void* style, const int64_t* style_strides, const void* h, const void* sat, const void* v, double threshold,
+                       double sharpness, void* out, const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind,
+                       void* stream);
 
 /* ---- packed input frames -------------------------------------------------------------------- */
 /* frameio_in.py (the specification, bit for bit), the inverse of svr_pack_frames: packed samples as a decoder emits them -> out

@@ -14,6 +14,10 @@ Rank matching (csrc/svr_rank.hip, the last section): per plane HipOps.rank_match
 the same device planes; a sort's three launches per pass by difference; the whole lab route with colorfix.RANK_MATCH on and off
 (mean, min and max of the repetitions) and both routes' peak memory.  The per-method table above runs with RANK_MATCH as it stands.
 
+The HSV half (csrc/svr_hsv.hip, the section after it): the four calls on their own, svr_hue_match taken apart by the bins that
+qualify, and the hsv and wavelet_adaptive routes with colorfix.HSV_MATCH on and off in turn (mean, min and max), with both routes' peak
+memory.  HSV_MATCH = False is the torch chain of before.
+
 python tools/colorfix_timing.py [--frames 17] [--height 2160] [--width 3840] [--reps 5] >> profiles/colorfix.txt"""
 import argparse
 import importlib
@@ -25,7 +29,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 PKG = "comfyui-seedvr2_videoupscaler_amd"
-METHODS = ("wavelet", "adain", "lab", "wavelet_adaptive")
+METHODS = ("wavelet", "adain", "lab", "wavelet_adaptive", "hsv")
 
 
 def timed(fn, warmup, reps):
@@ -137,6 +141,71 @@ def rank_section(ops, cf, content, style, args):
           f"; as shipped: {shipped}")
 
 
+def hsv_section(ops, cf, content, style, args):
+    """The HSV kernels (csrc/svr_hsv.hip) on their own, and the hsv and wavelet_adaptive routes with colorfix.HSV_MATCH on and off in
+    turn in this process (off: the torch chain of before), with both routes' peak memory."""
+    T, H, W = args.frames, args.height, args.width
+    n = T * H * W
+    span = n * 3 * 4
+    c_hsv, s_hs = ops.hsv_planes(content, style)
+    counts = lambda h: [int(cf.hue_bin_mask(h, k).sum()) for k in range(12)]
+    n_c, n_s = counts(c_hsv[0]), counts(s_hs[0])
+    bins = [k for k in range(12) if n_c[k] > 100 and n_s[k] > 100]
+    sorted_src, sorted_ref = sum(n_c[k] for k in bins), sum(n_s[k] for k in bins)
+    # bytes: two class partitions (source 4 + 8 + 8, reference 4 + 8 + 4 per pixel), bin 0's own partition (20), out = c_s when not
+    # in place (8); per sorted source element 76 + 8 (apply: index and value read) + 4 stored at random, per reference element 48
+    model = n * (20 + 16 + 8 + (20 if 0 in bins else 0)) + sorted_src * 88 + sorted_ref * 48
+    print(f"# ---- the HSV half: {n} pixels; bins that qualify {bins}; {sorted_src} source and {sorted_ref} reference elements sorted; "
+          f"svr_hue_match byte model {model / 1e9:.1f} GB, workspace {int(ops.lib.svr_hue_match_workspace_bytes(n)) / 1e9:.2f} GB")
+    t_p = timed(lambda: ops.hsv_planes(content, style, c_hsv=c_hsv, s_hs=s_hs), args.warmup, args.reps)
+    sat = torch.empty_like(c_hsv[1])
+    t_h = timed_each(lambda: ops.hue_match(c_hsv[0], c_hsv[1], s_hs[0], s_hs[1], out=sat), args.warmup, args.reps)
+    same = torch.equal(sat, ops.hue_match(c_hsv[0], c_hsv[1], s_hs[0], s_hs[1]))
+    # a style without hues qualifies no bin: the two class partitions, the host's read of the counts and out = c_s alone
+    no_hue = torch.full_like(s_hs[0], float("nan"))
+    t_0 = timed_each(lambda: ops.hue_match(c_hsv[0], c_hsv[1], no_hue, s_hs[1], out=sat), args.warmup, args.reps)
+    del no_hue
+    ops.hue_match(c_hsv[0], c_hsv[1], s_hs[0], s_hs[1], out=sat)
+    base = ops.wavelet_reconstruct(content, style)
+    out = torch.empty_like(base)
+    t_m = timed(lambda: ops.hsv_merge(c_hsv[0], sat, c_hsv[2], (T, H, W), out=out), args.warmup, args.reps)
+    t_b = timed(lambda: ops.adaptive_blend(base, content, style, c_hsv[0], sat, c_hsv[2], out=out), args.warmup, args.reps)
+    mean_h = sum(t_h) / len(t_h)
+    for name, ms, nbytes in (("svr_hsv_planes", t_p, 2 * span + 5 * n * 4), ("svr_hsv_merge", t_m, 3 * n * 4 + span),
+                             ("svr_adaptive_blend", t_b, 3 * n * 4 + 4 * span)):
+        print(f"# {name:34s} {ms:8.2f} ms  model {nbytes / 1e9:5.2f} GB -> {nbytes / ms / 1e9:7.2f} TB/s of the model's bytes")
+    print(f"# {'svr_hue_match':34s} {spread(t_h)}  model {model / 1e9:5.2f} GB -> {model / mean_h / 1e9:7.2f} TB/s of the model's bytes "
+          f"(one host read of the class counts inside; two runs bit-equal: {same})")
+    print(f"# {'  of it, no bin qualifying':34s} {spread(t_0)}  the two class partitions ({n * 36 / 1e9:.2f} GB), the read of the counts and "
+          f"out = c_s ({n * 8 / 1e9:.2f} GB); the sorts and scatters of the bins by difference {mean_h - sum(t_0) / len(t_0):.2f} ms")
+    del sat, base, out, c_hsv, s_hs
+    shipped = cf.HSV_MATCH
+    verdict = {}
+    for m in ("hsv", "wavelet_adaptive"):
+        fn = lambda: cf.correct(content, style, m, ops=ops)
+        res = {}
+        for flag in (True, False):
+            cf.HSV_MATCH = flag
+            res[flag] = ([], peak_above(fn))                       # (also the warm-up of that route)
+        for _ in range(args.reps):                                 # the two routes in turn: a drift of the box meets both alike
+            for flag in (True, False):
+                cf.HSV_MATCH = flag
+                res[flag][0].extend(timed_each(fn, 0, 1))
+        cf.HSV_MATCH = True
+        a = cf.correct(content, style, m, ops=ops)
+        cf.HSV_MATCH = False
+        d = (a - cf.correct(content, style, m, ops=ops)).abs_()
+        cf.HSV_MATCH = shipped
+        print(f"# {m:16s} route, colorfix.HSV_MATCH = True : {spread(res[True][0])}   peak above the operands {res[True][1] / 1e9:6.2f} GB")
+        print(f"# {m:16s} route, colorfix.HSV_MATCH = False: {spread(res[False][0])}   peak above the operands {res[False][1] / 1e9:6.2f} GB"
+              f"   ratio {sum(res[False][0]) / sum(res[True][0]):.2f}")
+        print(f"# {m:16s} the two routes apart: max {float(d.max()):.3e}, share > 2e-5 {float((d > 2e-5).float().mean()):.3e}")
+        verdict[m] = sum(res[True][0]) <= sum(res[False][0])
+        del a, d
+    print(f"# -> HSV_MATCH default by the rule of DESIGN.md 7.3e: {'True (not slower on both methods)' if all(verdict.values()) else 'False (slower on ' + ', '.join(k for k, v in verdict.items() if not v) + ')'}"
+          f"; as shipped: {shipped}")
+
+
 def peak_above(fn):
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
@@ -158,6 +227,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--methods", default=",".join(METHODS), help="comma-separated; empty: none of the per-method lines")
     ap.add_argument("--no-rank", action="store_true", help="leave the rank-matching section out")
+    ap.add_argument("--no-hsv", action="store_true", help="leave the section of the HSV half out")
+    ap.add_argument("--random-colours", action="store_true", help="uniformly random pixels instead of noise over a gradient: every "
+                    "hue bin holds a twelfth of both operands, so the HSV matching sorts every pixel")
     args = ap.parse_args()
     ops_mod, cf = (importlib.import_module(f"{PKG}.{m}") for m in ("ops", "colorfix"))
     ops = ops_mod.HipOps("cuda:0")
@@ -169,6 +241,9 @@ def main():
     frames = (smooth + tint + torch.randn(T, H, W, 3, generator=g, device="cuda") * 0.05).clamp_(-1, 1).contiguous()
     big = torch.empty(3, T, H + 8, W + 8, device="cuda")
     big[:, :, :H, :W] = (smooth * 0.8 - tint + torch.randn(T, H, W, 3, generator=g, device="cuda") * 0.02).clamp_(-1, 1).permute(3, 0, 1, 2)
+    if args.random_colours:
+        frames.copy_(torch.rand(T, H, W, 3, generator=g, device="cuda") * 1.8 - 0.9)
+        big[:, :, :H, :W] = (torch.rand(T, H, W, 3, generator=g, device="cuda") * 1.2 - 0.5).permute(3, 0, 1, 2)
     content, style = frames.permute(0, 3, 1, 2), big.permute(1, 0, 2, 3)[:, :, :H, :W]
     del smooth, yy, xx
     span = T * H * W * 3 * 4
@@ -202,6 +277,8 @@ def main():
     del base, planes, c_lab
     if not args.no_rank and hasattr(ops, "rank_match"):
         rank_section(ops, cf, content, style, args)
+    if not args.no_hsv and all(hasattr(ops, k) for k in cf._HSV_OPS):
+        hsv_section(ops, cf, content, style, args)
 
 
 if __name__ == "__main__":
