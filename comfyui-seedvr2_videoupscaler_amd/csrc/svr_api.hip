@@ -455,99 +455,93 @@ int svr_alpha_refine(const void* rgb, const float* base, float* out, uint8_t* ed
 }
 #undef SVR_ALPHA_REFUSE
 
-// ---- packed output frames (svr_frame_pack.hip)
-int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t fmt, void* out,
-                    int64_t out_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+// ---- packed output frames (svr_frame_pack.hip: rgb8 / bgr8; svr_frame_pack_colour.hip: yuv420p10, whichever entry point asks)
+// The refusals svr_pack_frames and svr_pack_yuv420p10 share, in the order both report them -> the message, left in g_err behind
+// ``fn``, or nullptr.  ``own``: the caller's refusal of its own format / colour codes (nullptr: none), which ranks between the
+// geometry and the alignment.  ``C8``: bytes per pixel of an 8-bit format, 0 for yuv420p10 planes.  ``needs``: the caller's words.
+static const char* pack_refusal(const char* fn, const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C8,
+                                const char* own, const void* out, int64_t out_bytes, const char* needs) {
     const char* why = nullptr;
     if (!frames) why = "frames is a null pointer";
     else if (!out) why = "out is a null pointer";
     else if (x_kind != SVR_STORE_BF16 && x_kind != SVR_STORE_FP32) why = "x_kind must be SVR_STORE_BF16 or SVR_STORE_FP32";
     else if (T < 1 || H < 1 || W < 1) why = "need T >= 1, H >= 1, W >= 1";
     else if ((int64_t)H * W > ((int64_t)1 << 40) / T) why = "T * H * W must not exceed 2^40 pixels";
-    else if (fmt != SVR_PACK_RGB8 && fmt != SVR_PACK_BGR8 && fmt != SVR_PACK_YUV420P10) why = "fmt must be SVR_PACK_RGB8, SVR_PACK_BGR8 or SVR_PACK_YUV420P10";
-    else if (fmt == SVR_PACK_YUV420P10 ? C != 3 : (C != 3 && C != 4)) why = fmt == SVR_PACK_YUV420P10 ? "C must be 3 for SVR_PACK_YUV420P10" : "C must be 3 or 4";
+    else if (own) why = own;
     else if ((uintptr_t)frames % (x_kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
-    else if (fmt == SVR_PACK_YUV420P10 && (uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
-    if (why) { snprintf(g_err, sizeof(g_err), "svr_pack_frames: %s", why); return -1; }
-    const int64_t px = (int64_t)T * H * W, h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
-    const int64_t need = fmt == SVR_PACK_YUV420P10 ? 2 * (int64_t)T * ((int64_t)H * W + 2 * h2 * w2) : px * C;
-    if (out_bytes != need) {
-        snprintf(g_err, sizeof(g_err), "svr_pack_frames: out_bytes is %lld, the format needs exactly %lld", (long long)out_bytes, (long long)need);
-        return -1;
-    }
-    const bool aligned = (uintptr_t)frames % 16 == 0 && (uintptr_t)out % 16 == 0;
-    // capped in 64 bits: under the 2^40-pixel limit the block count of the element-wise routes does not fit 32
-    const int64_t cap = (int64_t)device_cu_count() * 8;
-    auto capped = [cap](int64_t work) { return (unsigned)std::min<int64_t>((work + 255) / 256, cap); };
+    else if (!C8 && (uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
+    if (why) { snprintf(g_err, sizeof(g_err), "%s: %s", fn, why); return g_err; }
+    const int64_t h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
+    const int64_t need = C8 ? (int64_t)T * H * W * C8 : 2 * (int64_t)T * ((int64_t)H * W + 2 * h2 * w2);
+    if (out_bytes == need) return nullptr;
+    snprintf(g_err, sizeof(g_err), "%s: out_bytes is %lld, the %s exactly %lld", fn, (long long)out_bytes, needs, (long long)need);
+    return g_err;
+}
+
+// capped in 64 bits: under the 2^40-pixel limit the block count of the element-wise routes does not fit 32
+static unsigned pack_grid(int64_t work) { return (unsigned)std::min<int64_t>((work + 255) / 256, (int64_t)device_cu_count() * 8); }
+
+// Kr, Kb exact decimals, every weight rounded at 2^16, luma deficit to green (frameio.yuv_matrix): wr, wg, wb | cb_r, cb_g | cr_g, cr_b
+static PackCoef pack_coef(int32_t matrix, int32_t range) {
+    PackCoef k = matrix == SVR_COLOUR_MATRIX_BT709 ? PackCoef{0, 0, 0, 13933, 46871, 4732, -7509, -25259, -29763, -3005}
+               : matrix == SVR_COLOUR_MATRIX_BT601 ? PackCoef{0, 0, 0, 19595, 38470, 7471, -11058, -21710, -27439, -5329}
+                                                   : PackCoef{0, 0, 0, 17216, 44434, 3886, -9151, -23617, -30133, -2635};
+    if (range == SVR_COLOUR_RANGE_TV) { k.y0 = 64; k.ys = 876; k.cs = 896; } else { k.y0 = 0; k.ys = 1023; k.cs = 1023; }
+    return k;
+}
+
+// the one yuv420p10 launch: 16 x 2 pixels per lane where every row, plane and frame starts on 16 bytes, else one chroma sample
+static void launch_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, const PackCoef& k, bool left,
+                                  unsigned short* o, hipStream_t s) {
+    const bool vec = (uintptr_t)frames % 16 == 0 && (uintptr_t)o % 16 == 0 && W % 16 == 0;
+    const int64_t h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
+    const unsigned grid = pack_grid((int64_t)T * h2 * (vec ? W / 16 : w2));
+#define SVR_PACK_COLOUR(KIND, LEFT) \
+    if (vec) hipLaunchKernelGGL((pack_colour_vec_kernel<KIND, LEFT>), dim3(grid), dim3(256), 0, s, frames, o, T, H, W, k); \
+    else hipLaunchKernelGGL((pack_colour_kernel<KIND, LEFT>), dim3(grid), dim3(256), 0, s, frames, o, T, H, W, k)
+    if (x_kind == SVR_STORE_FP32) { if (left) { SVR_PACK_COLOUR(SVR_STORE_FP32, true); } else { SVR_PACK_COLOUR(SVR_STORE_FP32, false); } }
+    else { if (left) { SVR_PACK_COLOUR(SVR_STORE_BF16, true); } else { SVR_PACK_COLOUR(SVR_STORE_BF16, false); } }
+#undef SVR_PACK_COLOUR
+}
+
+int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t fmt, void* out,
+                    int64_t out_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const bool yuv = fmt == SVR_PACK_YUV420P10;
+    const char* own = nullptr;
+    if (fmt != SVR_PACK_RGB8 && fmt != SVR_PACK_BGR8 && !yuv) own = "fmt must be SVR_PACK_RGB8, SVR_PACK_BGR8 or SVR_PACK_YUV420P10";
+    else if (yuv ? C != 3 : (C != 3 && C != 4)) own = yuv ? "C must be 3 for SVR_PACK_YUV420P10" : "C must be 3 or 4";
+    if (pack_refusal("svr_pack_frames", frames, x_kind, T, H, W, yuv ? 0 : C, own, out, out_bytes, "format needs")) return -1;
     const hipStream_t s = (hipStream_t)stream;
-    const bool f32 = x_kind == SVR_STORE_FP32;
-    if (fmt == SVR_PACK_YUV420P10) {
-        unsigned short* o = (unsigned short*)out;
-        if (aligned && W % 16 == 0) {
-            const unsigned grid = capped((int64_t)T * h2 * (W / 16));
-            if (f32) hipLaunchKernelGGL(pack_yuv_vec_kernel<SVR_STORE_FP32>, dim3(grid), dim3(256), 0, s, frames, o, T, H, W);
-            else hipLaunchKernelGGL(pack_yuv_vec_kernel<SVR_STORE_BF16>, dim3(grid), dim3(256), 0, s, frames, o, T, H, W);
-        } else {
-            const unsigned grid = capped((int64_t)T * h2 * w2);
-            if (f32) hipLaunchKernelGGL(pack_yuv_kernel<SVR_STORE_FP32>, dim3(grid), dim3(256), 0, s, frames, o, T, H, W);
-            else hipLaunchKernelGGL(pack_yuv_kernel<SVR_STORE_BF16>, dim3(grid), dim3(256), 0, s, frames, o, T, H, W);
-        }
+    if (yuv) {                                                     // BT.709, limited range, centre-sited chroma
+        launch_pack_yuv420p10(frames, x_kind, T, H, W, pack_coef(SVR_COLOUR_MATRIX_BT709, SVR_COLOUR_RANGE_TV), false, (unsigned short*)out, s);
         return check(hipGetLastError(), "svr_pack_frames");
     }
-    const int64_t n = px * C;
+    const int64_t n = (int64_t)T * H * W * C;
     const int swap = fmt == SVR_PACK_BGR8 ? C : 0;                 // pack8_kernel's C: 0 = samples in place
     const int unit = swap == 3 ? 48 : 16;
-    const int64_t n_units = aligned ? n / unit : 0;
-    const unsigned grid = capped(std::max<int64_t>(n_units, n - n_units * unit));
+    const int64_t n_units = (uintptr_t)frames % 16 == 0 && (uintptr_t)out % 16 == 0 ? n / unit : 0;
+    const unsigned grid = pack_grid(std::max<int64_t>(n_units, n - n_units * unit));
     unsigned char* o = (unsigned char*)out;
 #define SVR_PACK8(KIND, CH) hipLaunchKernelGGL((pack8_kernel<KIND, CH>), dim3(grid), dim3(256), 0, s, frames, o, n_units, n)
-    if (f32) { if (swap == 0) SVR_PACK8(SVR_STORE_FP32, 0); else if (swap == 3) SVR_PACK8(SVR_STORE_FP32, 3); else SVR_PACK8(SVR_STORE_FP32, 4); }
+    if (x_kind == SVR_STORE_FP32) { if (swap == 0) SVR_PACK8(SVR_STORE_FP32, 0); else if (swap == 3) SVR_PACK8(SVR_STORE_FP32, 3); else SVR_PACK8(SVR_STORE_FP32, 4); }
     else { if (swap == 0) SVR_PACK8(SVR_STORE_BF16, 0); else if (swap == 3) SVR_PACK8(SVR_STORE_BF16, 3); else SVR_PACK8(SVR_STORE_BF16, 4); }
 #undef SVR_PACK8
     return check(hipGetLastError(), "svr_pack_frames");
 }
 
-// ---- yuv420p10 planes with a chosen matrix, range and chroma siting (svr_frame_pack_colour.hip)
+// ---- yuv420p10 planes with a chosen matrix, range and chroma siting
 int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t matrix, int32_t range,
                        int32_t siting, void* out, int64_t out_bytes, void* stream) {
     StreamDeviceGuard on_stream_device(stream);
-    const char* why = nullptr;
-    if (!frames) why = "frames is a null pointer";
-    else if (!out) why = "out is a null pointer";
-    else if (x_kind != SVR_STORE_BF16 && x_kind != SVR_STORE_FP32) why = "x_kind must be SVR_STORE_BF16 or SVR_STORE_FP32";
-    else if (T < 1 || H < 1 || W < 1) why = "need T >= 1, H >= 1, W >= 1";
-    else if ((int64_t)H * W > ((int64_t)1 << 40) / T) why = "T * H * W must not exceed 2^40 pixels";
-    else if (matrix != SVR_COLOUR_MATRIX_BT709 && matrix != SVR_COLOUR_MATRIX_BT601 && matrix != SVR_COLOUR_MATRIX_BT2020)
-        why = "matrix must be SVR_COLOUR_MATRIX_BT709, SVR_COLOUR_MATRIX_BT601 or SVR_COLOUR_MATRIX_BT2020";
-    else if (range != SVR_COLOUR_RANGE_TV && range != SVR_COLOUR_RANGE_PC) why = "range must be SVR_COLOUR_RANGE_TV or SVR_COLOUR_RANGE_PC";
-    else if (siting != SVR_COLOUR_SITING_CENTER && siting != SVR_COLOUR_SITING_LEFT) why = "siting must be SVR_COLOUR_SITING_CENTER or SVR_COLOUR_SITING_LEFT";
-    else if ((uintptr_t)frames % (x_kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
-    else if ((uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
-    if (why) { snprintf(g_err, sizeof(g_err), "svr_pack_yuv420p10: %s", why); return -1; }
-    const int64_t h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
-    const int64_t need = 2 * (int64_t)T * ((int64_t)H * W + 2 * h2 * w2);
-    if (out_bytes != need) {
-        snprintf(g_err, sizeof(g_err), "svr_pack_yuv420p10: out_bytes is %lld, the planes need exactly %lld", (long long)out_bytes, (long long)need);
-        return -1;
-    }
-    // Kr, Kb exact decimals, every weight rounded at 2^16, luma deficit to green (frameio.yuv_matrix): wr, wg, wb | cb_r, cb_g | cr_g, cr_b
-    PackCoef k = matrix == SVR_COLOUR_MATRIX_BT709 ? PackCoef{0, 0, 0, 13933, 46871, 4732, -7509, -25259, -29763, -3005}
-               : matrix == SVR_COLOUR_MATRIX_BT601 ? PackCoef{0, 0, 0, 19595, 38470, 7471, -11058, -21710, -27439, -5329}
-                                                   : PackCoef{0, 0, 0, 17216, 44434, 3886, -9151, -23617, -30133, -2635};
-    if (range == SVR_COLOUR_RANGE_TV) { k.y0 = 64; k.ys = 876; k.cs = 896; } else { k.y0 = 0; k.ys = 1023; k.cs = 1023; }
-    const bool vec = (uintptr_t)frames % 16 == 0 && (uintptr_t)out % 16 == 0 && W % 16 == 0;
-    const int64_t cap = (int64_t)device_cu_count() * 8;
-    const unsigned grid = (unsigned)std::min<int64_t>(((vec ? (int64_t)T * h2 * (W / 16) : (int64_t)T * h2 * w2) + 255) / 256, cap);
-    const hipStream_t s = (hipStream_t)stream;
-    unsigned short* o = (unsigned short*)out;
-#define SVR_PACK_COLOUR(KIND, LEFT) \
-    if (vec) hipLaunchKernelGGL((pack_colour_vec_kernel<KIND, LEFT>), dim3(grid), dim3(256), 0, s, frames, o, T, H, W, k); \
-    else hipLaunchKernelGGL((pack_colour_kernel<KIND, LEFT>), dim3(grid), dim3(256), 0, s, frames, o, T, H, W, k)
-    const bool left = siting == SVR_COLOUR_SITING_LEFT;
-    if (x_kind == SVR_STORE_FP32) { if (left) { SVR_PACK_COLOUR(SVR_STORE_FP32, true); } else { SVR_PACK_COLOUR(SVR_STORE_FP32, false); } }
-    else { if (left) { SVR_PACK_COLOUR(SVR_STORE_BF16, true); } else { SVR_PACK_COLOUR(SVR_STORE_BF16, false); } }
-#undef SVR_PACK_COLOUR
+    const char* own = nullptr;
+    if (matrix != SVR_COLOUR_MATRIX_BT709 && matrix != SVR_COLOUR_MATRIX_BT601 && matrix != SVR_COLOUR_MATRIX_BT2020)
+        own = "matrix must be SVR_COLOUR_MATRIX_BT709, SVR_COLOUR_MATRIX_BT601 or SVR_COLOUR_MATRIX_BT2020";
+    else if (range != SVR_COLOUR_RANGE_TV && range != SVR_COLOUR_RANGE_PC) own = "range must be SVR_COLOUR_RANGE_TV or SVR_COLOUR_RANGE_PC";
+    else if (siting != SVR_COLOUR_SITING_CENTER && siting != SVR_COLOUR_SITING_LEFT) own = "siting must be SVR_COLOUR_SITING_CENTER or SVR_COLOUR_SITING_LEFT";
+    if (pack_refusal("svr_pack_yuv420p10", frames, x_kind, T, H, W, 0, own, out, out_bytes, "planes need")) return -1;
+    launch_pack_yuv420p10(frames, x_kind, T, H, W, pack_coef(matrix, range), siting == SVR_COLOUR_SITING_LEFT, (unsigned short*)out,
+                          (hipStream_t)stream);
     return check(hipGetLastError(), "svr_pack_yuv420p10");
 }
 

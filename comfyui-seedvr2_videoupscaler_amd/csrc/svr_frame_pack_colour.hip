@@ -1,11 +1,14 @@
-// yuv420p10 planes with a choice of matrix, range and chroma siting (frameio.pack_yuv420p10_torch is the specification, bit for
-// bit): what an HDR (BT.2020) source is written with.  The two shapes of svr_frame_pack.hip's yuv kernels, same streaming rules
-// (no LDS, no atomics, capped grids with a grid-stride loop, no cross-lane traffic):
+// The yuv420p10 writer, behind both entry points: svr_pack_yuv420p10 with a choice of matrix, range and chroma siting
+// (frameio.pack_yuv420p10_torch is the specification, bit for bit: what an HDR (BT.2020) source is written with), and
+// svr_pack_frames' SVR_PACK_YUV420P10 with BT.709, limited range, centre siting (frameio.pack_frames_torch, an independent
+// statement of the same integers).  Two shapes, svr_frame_pack.hip's streaming rules (no LDS, no atomics, capped grids with a
+// grid-stride loop, no cross-lane traffic) and its pack_load, pack_load_run, pack_code and YUV_D:
 //   pack_colour_vec_kernel  W % 16 == 0 and 16-byte aligned pointers: a lane owns 16 x 2 pixels = two Y runs of 32 bytes and 8 + 8
-//                           chroma samples, every access of its own run 16 bytes.
-//   pack_colour_kernel      any other geometry: a lane owns one chroma sample and its 2 x 2 pixels, element accesses.
+//                           chroma samples, every access of its own run 16 bytes (rows, planes and frames all start on 16 bytes then).
+//   pack_colour_kernel      any other geometry: a lane owns one chroma sample and its 2 x 2 pixels, element accesses (a Y row
+//                           starts 2 * W bytes after the previous one: off 16 bytes whenever W % 8 != 0).
 // Matrix and range arrive as integers in PackCoef (as the unpack's YuvCoef); the siting is a template parameter:
-//   LEFT = false  chroma from the 2 x 2 block, weights 1: S = 4 -- with the BT.709 tv coefficients the bytes of pack_yuv_*_kernel.
+//   LEFT = false  chroma from the 2 x 2 block, weights 1: S = 4.
 //   LEFT = true   columns 2k-1, 2k, 2k+1 with weights 1, 2, 1 over the two rows: S = 8.  Column 2k-1 of a lane's FIRST chroma sample
 //                 lies one pixel to the left of its run: the lane loads that pixel itself (three elements per row, 1/16 more loads,
 //                 from a line its left neighbour streams anyway), so nothing depends on which lane, wave or workgroup holds the

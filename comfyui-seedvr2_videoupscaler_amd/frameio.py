@@ -1,6 +1,7 @@
 """Output frames narrowed for the encoder: the packed formats, stated once, in plain torch.
 
-This module is the specification of the kernels in csrc/svr_frame_pack.hip (equal bit for bit: integer results, no tolerance) and
+This module is the specification of the kernels in csrc/svr_frame_pack.hip and, for "yuv420p10", of csrc/svr_frame_pack_colour.hip
+run with the BT.709 limited-range constants and centre-sited chroma (equal bit for bit: integer results, no tolerance) and
 the path taken when ``ops`` has no ``pack_frames`` (the fp32 torch double of the C ABI that drives the CPU tests).  Any device.
 
 ``frames`` [T, H, W, C], fp32 or bf16, nominally in [0, 1], C = 3 or 4.

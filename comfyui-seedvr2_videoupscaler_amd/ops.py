@@ -538,28 +538,36 @@ class HipOps:
         return out
 
     # ------------------------------------------------------------------ packed output frames
-    def pack_frames(self, frames, fmt, out=None):
-        """Output frames narrowed on the device (frameio.py is the specification; csrc/svr_frame_pack.hip): frames [T, H, W, 3 | 4]
-        fp32 / bf16, dense -> uint8 [T, H, W, C] ("rgb8", "bgr8") or uint16 [T, H*W + 2*h2*w2] ("yuv420p10", C = 3).  One launch on
-        the current stream, no host synchronisation.  ``out``: a dense tensor of exactly that shape and dtype."""
+    def _pack_args(self, name, frames, fmt, out, colour=None):
+        """What pack_frames and pack_yuv420p10 check before their launch -> (T, H, W, Cn, x_kind, out); ``out`` allocated where it
+        was None.  ``colour``: pack_yuv420p10's (matrix, range_, siting), refused with the format."""
         from . import frameio
         if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
-            raise ValueError(f"pack_frames: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
+            raise ValueError(f"{name}: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
         T, H, W, Cn = frames.shape
         try:
+            if colour is not None:
+                frameio.check_colour(*colour)
             shape = frameio.packed_shape(T, H, W, Cn, fmt)
         except ValueError as e:
-            raise ValueError(f"pack_frames: {e}") from None
+            raise ValueError(f"{name}: {e}") from None
         if T < 1 or H < 1 or W < 1:
-            raise ValueError(f"pack_frames: frames must hold at least one pixel, got {tuple(frames.shape)}")
-        self._chk(frames, None, "pack_frames: frames")
+            raise ValueError(f"{name}: frames must hold at least one pixel, got {tuple(frames.shape)}")
+        self._chk(frames, None, f"{name}: frames")
         dtype = frameio.packed_dtype(fmt)
         if out is None:
             out = torch.empty(shape, dtype=dtype, device=self.device)
-        self._chk(out, dtype, "pack_frames: out")
+        self._chk(out, dtype, f"{name}: out")
         if tuple(out.shape) != tuple(shape):
-            raise ValueError(f"pack_frames: out must be {tuple(shape)} for {fmt}, got {tuple(out.shape)}")
-        kind = 1 if frames.dtype == torch.float32 else 0                     # SVR_STORE_FP32 / SVR_STORE_BF16
+            raise ValueError(f"{name}: out must be {tuple(shape)}{'' if colour else f' for {fmt}'}, got {tuple(out.shape)}")
+        return T, H, W, Cn, 1 if frames.dtype == torch.float32 else 0, out     # SVR_STORE_FP32 / SVR_STORE_BF16
+
+    def pack_frames(self, frames, fmt, out=None):
+        """Output frames narrowed on the device (frameio.py is the specification; csrc/svr_frame_pack.hip, yuv420p10 through
+        csrc/svr_frame_pack_colour.hip): frames [T, H, W, 3 | 4] fp32 / bf16, dense -> uint8 [T, H, W, C] ("rgb8", "bgr8") or
+        uint16 [T, H*W + 2*h2*w2] ("yuv420p10", C = 3).  One launch on the current stream, no host synchronisation.  ``out``: a dense
+        tensor of exactly that shape and dtype."""
+        T, H, W, Cn, kind, out = self._pack_args("pack_frames", frames, fmt, out)
         hip_lib.check(self.lib.svr_pack_frames(_ptr(frames), kind, T, H, W, Cn, hip_lib.PACK_FORMATS[fmt], _ptr(out),
                                                out.numel() * out.element_size(), self._stream()), "svr_pack_frames")
         return out
@@ -569,24 +577,7 @@ class HipOps:
         "left") on the device (frameio.pack_yuv420p10_torch is the specification; csrc/svr_frame_pack_colour.hip): frames
         [T, H, W, 3] fp32 / bf16, dense -> uint16 [T, H*W + 2*h2*w2].  One launch on the current stream, no host synchronisation.
         ``out``: a dense tensor of exactly that shape and dtype."""
-        from . import frameio
-        if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
-            raise ValueError(f"pack_yuv420p10: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
-        T, H, W, Cn = frames.shape
-        try:
-            frameio.check_colour(matrix, range_, siting)
-            shape = frameio.packed_shape(T, H, W, Cn, "yuv420p10")
-        except ValueError as e:
-            raise ValueError(f"pack_yuv420p10: {e}") from None
-        if T < 1 or H < 1 or W < 1:
-            raise ValueError(f"pack_yuv420p10: frames must hold at least one pixel, got {tuple(frames.shape)}")
-        self._chk(frames, None, "pack_yuv420p10: frames")
-        if out is None:
-            out = torch.empty(shape, dtype=torch.uint16, device=self.device)
-        self._chk(out, torch.uint16, "pack_yuv420p10: out")
-        if tuple(out.shape) != tuple(shape):
-            raise ValueError(f"pack_yuv420p10: out must be {tuple(shape)}, got {tuple(out.shape)}")
-        kind = 1 if frames.dtype == torch.float32 else 0                     # SVR_STORE_FP32 / SVR_STORE_BF16
+        T, H, W, _, kind, out = self._pack_args("pack_yuv420p10", frames, "yuv420p10", out, colour=(matrix, range_, siting))
         hip_lib.check(self.lib.svr_pack_yuv420p10(_ptr(frames), kind, T, H, W, hip_lib.COLOUR_MATRICES[matrix],
                                                   hip_lib.COLOUR_RANGES[range_], hip_lib.COLOUR_SITINGS[siting], _ptr(out),
                                                   out.numel() * out.element_size(), self._stream()), "svr_pack_yuv420p10")

@@ -88,6 +88,27 @@ def test_non_finite_and_negative_zero(hip, dtype):
     assert run_kernel(hip, one, "yuv420p10").flatten().tolist() == [691, 167, 105]
 
 
+# (Y, Cb, Cr) of the flat frames black, blue, green, cyan, red, magenta, yellow, white: BT.709, limited range
+CORNER_CODES = [(64, 512, 512), (127, 960, 471), (691, 167, 105), (754, 615, 64), (250, 409, 960), (313, 857, 919), (877, 64, 553),
+                (940, 512, 512)]
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, BF16], ids=["fp32", "bf16"])
+def test_cube_corners_reach_the_chroma_extremes(hip, dtype):
+    """Every pixel one of the eight corners of the RGB cube: chroma reaches 64 and 960, where the shared kernel's clamp at 1023 and
+    its rounding constant S * 512 * D + S * D / 2 must give what the BT.709 statement's 2050 * D gives.  (1, 2, 16) and (2, 5, 32)
+    take the 16-byte route, (1, 3, 5) and (1, 1, 1) the element-wise one."""
+    frameio = sub("frameio")
+    corners = torch.tensor([[r, g, b] for r in (0., 1.) for g in (0., 1.) for b in (0., 1.)])
+    g = torch.Generator().manual_seed(31)
+    for shape in [(1, 2, 16), (2, 5, 32), (1, 3, 5), (1, 1, 1)]:
+        x = corners[torch.randint(0, 8, shape, generator=g)].to(dtype)
+        assert same(run_kernel(hip, x, "yuv420p10"), frameio.pack_frames_torch(x, "yuv420p10")), shape
+    flat = corners.view(8, 1, 1, 3).expand(8, 2, 2, 3).contiguous().to(dtype)
+    got = run_kernel(hip, flat, "yuv420p10")                                   # per frame: 4 Y, 1 Cb, 1 Cr
+    assert got.to(torch.int32).tolist() == [[y] * 4 + [cb, cr] for y, cb, cr in CORNER_CODES]
+
+
 def test_output_allocated_by_the_op_and_an_unaligned_view(hip):
     """Without ``out`` the op allocates; frames that start 4 bytes into an allocation (a dense view: frames[1:] of a one-pixel
     first frame would be 12 bytes in) take the element-wise route and give the same bytes."""

@@ -1,8 +1,12 @@
-"""Time the colour-out pack (HipOps.pack_yuv420p10, csrc/svr_frame_pack_colour.hip) against today's yuv420p10 pack
-(HipOps.pack_frames, csrc/svr_frame_pack.hip) in one process on one production batch: 17 frames of 3840 x 2160 fp32 RGB, the same
-input and output buffers for every variant.  5 warm-ups per variant, then 15 rounds that alternate the variants, each timed as 10
-launches between HIP events; the median over the rounds and the spread (min .. max) are printed, and each variant's ratio to
-today's kernel.  Every variant is first checked against its specification on one frame.
+"""Time the yuv420p10 pack (csrc/svr_frame_pack_colour.hip) through its two entry points and in its variants, in one process on
+one production batch: 17 frames of 3840 x 2160 fp32 RGB, the same input and output buffers for every variant.  The first row,
+"pack_frames yuv420p10 (today)", is HipOps.pack_frames' "yuv420p10": it reaches the same kernel through svr_pack_frames, with
+BT.709, limited range and centre siting.  (It had a kernel pair of its own, constants baked in, when the tool was written: the
+rows up to the removal in profiles/colour_out_pack.txt compare two kernels, the later ones one kernel through two entry points.)
+The second row, "pack_yuv420p10 bt709 tv center", is therefore the same launch through svr_pack_yuv420p10, and its ratio says what
+the measurement cannot tell apart.  5 warm-ups per variant, then 15 rounds that alternate the variants, each timed as 10 launches
+between HIP events; the median over the rounds and the spread (min .. max) are printed, and each variant's ratio to the first row
+(the column still headed "today's kernel").  Every variant is first checked against its specification on one frame.
 
 Byte model per pixel: 12 B read (fp32 RGB; 6 B for bf16), 3 B written (2 B of Y + 2 x 0.5 B of chroma); left siting reads one
 pixel more per 16 (12 B / 16 px), from a line the neighbouring lane streams anyway.

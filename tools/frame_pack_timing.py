@@ -1,4 +1,5 @@
-"""Time the frame-pack op (HipOps.pack_frames, csrc/svr_frame_pack.hip) on one production batch: 17 frames of 3840 x 2160 fp32 RGB.
+"""Time the frame-pack op (HipOps.pack_frames: csrc/svr_frame_pack.hip for rgb8 / bgr8, csrc/svr_frame_pack_colour.hip with the
+BT.709 limited-range constants for yuv420p10) on one production batch: 17 frames of 3840 x 2160 fp32 RGB.
 3 warm-ups, then the mean of 20 launches between HIP events, per format, next to the torch expression for the same conversion on
 the same device: for rgb8 the expression inference_cli.save_frames ran on the device before the formats had a kernel,
 ``(x.float().clamp(0, 1) * 255.0).round().to(torch.uint8)``; for bgr8 the same followed by the channel flip (done on the host
