@@ -556,17 +556,18 @@ static const char* png_geometry_refusal(int32_t T, int32_t H, int32_t W, int32_t
     return nullptr;
 }
 
-int svr_png_encode_bytes(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes, int64_t* capacity) {
+static int png_encode_bytes(const char* who, bool runs, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes,
+                            int64_t* capacity) {
     const char* why = png_geometry_refusal(T, H, W, C, depth);
-    if (why) { snprintf(g_err, sizeof(g_err), "svr_png_encode_bytes: %s", why); return -1; }
-    const PngLayout L = png_layout(T, H, W, C, depth);
+    if (why) { snprintf(g_err, sizeof(g_err), "%s: %s", who, why); return -1; }
+    const PngLayout L = png_layout(T, H, W, C, depth, runs);
     if (scratch_bytes) *scratch_bytes = L.scratch_bytes;
     if (capacity) *capacity = L.capacity;
     return 0;
 }
 
-int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, void* scratch,
-                   int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream) {
+static int png_encode(const char* who, bool runs, const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C,
+                      int32_t depth, void* scratch, int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream) {
     StreamDeviceGuard on_stream_device(stream);
     const char* why = nullptr;
     if (!frames) why = "frames is a null pointer";
@@ -578,14 +579,14 @@ int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int
     else if ((uintptr_t)frames % (x_kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
     else if ((uintptr_t)scratch % 16) why = "scratch is not aligned to 16 bytes";
     else if ((uintptr_t)sizes % 8) why = "sizes is not aligned to 8 bytes";
-    if (why) { snprintf(g_err, sizeof(g_err), "svr_png_encode: %s", why); return -1; }
-    const PngLayout L = png_layout(T, H, W, C, depth);
+    if (why) { snprintf(g_err, sizeof(g_err), "%s: %s", who, why); return -1; }
+    const PngLayout L = png_layout(T, H, W, C, depth, runs);
     if (scratch_bytes < L.scratch_bytes) {
-        snprintf(g_err, sizeof(g_err), "svr_png_encode: scratch_bytes is %lld, the geometry needs at least %lld", (long long)scratch_bytes, (long long)L.scratch_bytes);
+        snprintf(g_err, sizeof(g_err), "%s: scratch_bytes is %lld, the geometry needs at least %lld", who, (long long)scratch_bytes, (long long)L.scratch_bytes);
         return -1;
     }
     if (out_capacity < L.capacity) {
-        snprintf(g_err, sizeof(g_err), "svr_png_encode: out_capacity is %lld per frame, the geometry needs at least %lld", (long long)out_capacity, (long long)L.capacity);
+        snprintf(g_err, sizeof(g_err), "%s: out_capacity is %lld per frame, the geometry needs at least %lld", who, (long long)out_capacity, (long long)L.capacity);
         return -1;
     }
     const hipStream_t s = (hipStream_t)stream;
@@ -594,6 +595,7 @@ int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int
     uint32_t* table = (uint32_t*)(base + L.table_off);
     uint32_t* meta = (uint32_t*)(base + L.meta_off);
     int64_t* segoff = (int64_t*)(base + L.segoff_off);
+    uint32_t* table2 = (uint32_t*)(base + L.table2_off);         // (inside the scratch with runs only, and only then used)
     const dim3 grid((unsigned)((int64_t)T * L.nseg)), block(256);
 #define SVR_PNG_FILTER(KIND, DEPTH, CH) hipLaunchKernelGGL((png_filter_kernel<KIND, DEPTH, CH>), grid, block, 0, s, frames, filt, table, meta, H, W, L.R, L.nseg)
 #define SVR_PNG_FILTER_KIND(KIND) \
@@ -602,10 +604,33 @@ int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int
     if (x_kind == SVR_STORE_FP32) { SVR_PNG_FILTER_KIND(SVR_STORE_FP32) } else { SVR_PNG_FILTER_KIND(SVR_STORE_BF16) }
 #undef SVR_PNG_FILTER_KIND
 #undef SVR_PNG_FILTER
-    // (g_png_passes < 3, tools/png_encode_timing.py only: the launches up to that pass, to time them by difference)
+    // (g_png_passes < 3, tools/png_encode_timing.py only: the launches up to that pass, to time them by difference; with runs the
+    // token + second code pass counts with the scan, so that the first figure is the same work in both modes)
+    if (runs && g_png_passes >= 2) hipLaunchKernelGGL(png_runs_kernel, grid, block, 0, s, filt, table2, meta, H, L.stride, L.R, L.nseg);
     if (g_png_passes >= 2) hipLaunchKernelGGL(png_scan_kernel, dim3((unsigned)T), block, 0, s, meta, segoff, (unsigned char*)out, out_capacity, sizes, H, L.stride, L.R, L.nseg);
-    if (g_png_passes >= 3) hipLaunchKernelGGL(png_pack_kernel, grid, block, 0, s, filt, table, segoff, (unsigned char*)out, out_capacity, H, L.stride, L.R, L.nseg);
-    return check(hipGetLastError(), "svr_png_encode");
+    if (g_png_passes >= 3) {
+        if (runs) hipLaunchKernelGGL(png_pack_kernel<true>, grid, block, 0, s, filt, table, table2, meta, segoff, (unsigned char*)out, out_capacity, H, L.stride, L.R, L.nseg);
+        else hipLaunchKernelGGL(png_pack_kernel<false>, grid, block, 0, s, filt, table, table2, meta, segoff, (unsigned char*)out, out_capacity, H, L.stride, L.R, L.nseg);
+    }
+    return check(hipGetLastError(), who);
+}
+
+int svr_png_encode_bytes(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes, int64_t* capacity) {
+    return png_encode_bytes("svr_png_encode_bytes", false, T, H, W, C, depth, scratch_bytes, capacity);
+}
+
+int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, void* scratch,
+                   int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream) {
+    return png_encode("svr_png_encode", false, frames, x_kind, T, H, W, C, depth, scratch, scratch_bytes, out, out_capacity, sizes, stream);
+}
+
+int svr_png_encode_runs_bytes(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes, int64_t* capacity) {
+    return png_encode_bytes("svr_png_encode_runs_bytes", true, T, H, W, C, depth, scratch_bytes, capacity);
+}
+
+int svr_png_encode_runs(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, void* scratch,
+                        int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream) {
+    return png_encode("svr_png_encode_runs", true, frames, x_kind, T, H, W, C, depth, scratch, scratch_bytes, out, out_capacity, sizes, stream);
 }
 
 // ---- colour correction (svr_colorfix.hip).  Every argument is checked here, before any launch.

@@ -14,6 +14,14 @@
 //                       of the lanes' bit counts gives each its bit offset; a lane assembles 32-bit words in a register pair and ORs
 //                       them into a zeroed LDS image of the tile (integer OR: order-independent, so the bytes are deterministic);
 //                       the tile's whole bytes go to the output, its last partial byte is carried into the next tile.
+// svr_png_encode_runs (pngenc.py "Runs": run-length matches at distance 1) puts one launch behind the first and packs differently:
+//   png_runs_kernel     one workgroup per (frame, segment): the tokens tile by tile (png_tile_tokens: run starts by a running
+//                       maximum over the workgroup, carried from tile to tile; run ends by a look of 258 bytes ahead), their
+//                       histogram over 286 symbols in LDS, the second code by the same construction, both bit totals compared:
+//                       meta[3] = the choice, meta[0] and the second table for a chosen segment.
+//   png_pack_kernel<true>  a chosen segment: the 1222-bit header, the tokens found again tile by tile (nothing but the choice and
+//                       the table passes between the launches), a position giving 0 bits, a literal's code, or a match's code,
+//                       extra bits and distance bit; any other segment exactly as png_pack_kernel<false>, the literal packer.
 // Every indexed per-lane array is fully unrolled (registers) or lives in LDS: no kernel here has a private segment.  Every store to
 // ``out`` is guarded by the frame's capacity.  Bytes of ``out`` past sizes[t] are not written.
 #include "svr_common.h"
@@ -27,17 +35,28 @@ constexpr uint32_t PNG_ADLER = 65521u;
 constexpr int PNG_HEADER_BITS = 1106;
 constexpr int PNG_RUN = 16;                        // symbols per lane and tile in png_pack_kernel
 constexpr int PNG_TILE = 256 * PNG_RUN;
-constexpr int PNG_BUF_WORDS = PNG_TILE * 15 / 32 + 2;      // 7 carried bits + PNG_TILE symbols of at most 15 bits
+// The packer's tile image: 7 carried bits + PNG_TILE positions of at most 15 bits + 6 bits.  (A match head takes up to 15 + 5 + 1 =
+// 21 bits and the two or more positions it covers none: they make up for it, unless the head is the tile's last position.)
+constexpr int PNG_BUF_WORDS = (7 + PNG_TILE * 15 + 6 + 31) / 32 + 1;
+constexpr int PNG_RUN_SYMS = 286;                  // with run-length matches: the length symbols 257..285 as well
+constexpr int PNG_RUN_TABLE = 288;
+constexpr int PNG_RUN_HEADER_BITS = 1222;
+constexpr uint32_t PNG_MAX_MATCH = 258u;
+// groups of PNG_RUN positions behind a lane's own in which a run's end decides a token: whether 258 bytes are left at position i is
+// known from the positions up to i + 257
+constexpr int PNG_LOOK = (PNG_RUN - 1 + 257) / PNG_RUN;
+constexpr uint32_t PNG_NONE = 0xFFFFFFFFu;
 
 static int g_png_passes = 3;                       // svr_set_option("png_passes"): measurement only, 3 = the whole encoder
 
 struct PngLayout {
     int bpp, stride, R, nseg;
-    int64_t filt_off, table_off, meta_off, segoff_off, scratch_bytes, capacity;
+    int64_t filt_off, table_off, meta_off, segoff_off, table2_off, scratch_bytes, capacity;
 };
 
-// (pngenc.geometry / frame_bound; the scratch: filtered bytes | tables | {bytes, adler s1, s2, 0} per segment | segment offsets)
-static inline PngLayout png_layout(int64_t T, int64_t H, int64_t W, int C, int depth) {
+// (pngenc.geometry / frame_bound; the scratch: filtered bytes | tables | {bytes, adler s1, s2, literal data bits -> run block chosen}
+// per segment | segment offsets | with runs: the run blocks' tables)
+static inline PngLayout png_layout(int64_t T, int64_t H, int64_t W, int C, int depth, bool runs = false) {
     PngLayout L;
     L.bpp = C * depth / 8;
     L.stride = (int)(1 + W * L.bpp);
@@ -49,7 +68,8 @@ static inline PngLayout png_layout(int64_t T, int64_t H, int64_t W, int C, int d
     L.table_off = up16(T * H * L.stride);
     L.meta_off = L.table_off + segs * PNG_TABLE * 4;
     L.segoff_off = L.meta_off + segs * 16;
-    L.scratch_bytes = L.segoff_off + segs * 8;
+    L.table2_off = up16(L.segoff_off + segs * 8);
+    L.scratch_bytes = runs ? L.table2_off + segs * PNG_RUN_TABLE * 4 : L.segoff_off + segs * 8;
     const int64_t full = H / L.R, rest = H - full * L.R;
     auto bound = [](int64_t n) { return 139 + (15 * (n + 1) + 7) / 8 + 5; };
     L.capacity = 2 + full * bound((int64_t)L.R * L.stride) + (rest ? bound(rest * L.stride) : 0) + 6;
@@ -93,17 +113,105 @@ SVR_DEVICE uint32_t png_wave_sum(uint32_t v) {
     return v;
 }
 
+// The code of pngenc.code_lengths / canonical_codes over the NS counts ``hist`` (LDS; every thread of the workgroup calls this;
+// hist is complete and at least two counts are non-zero): two-queue Huffman over the used symbols, counts halved (rounding up)
+// while the tree is deeper than 15.  On return, for everyone: sw[s] = bit-reversed code | length << 16 (0 for an unused symbol);
+// for thread 0 the return value is the sum of hist[s] * length[s].  ``sw`` (LDS, 2 NS words) is also the weights' working space:
+// the sorted leaves, then the internal nodes.  The function's own arrays are one set per NS, distinct objects (the serial part is
+// LDS-latency bound, and the compiler keeps more of it in registers when it knows that the arrays do not overlap).
+template <int NS>
+SVR_DEVICE uint64_t png_build_code(const uint32_t* hist, uint32_t* sw, int tid) {
+    __shared__ uint32_t cnt[NS], len_s[NS];
+    __shared__ unsigned short ssym[NS], parent[2 * NS], depth_s[2 * NS];
+    __shared__ uint32_t blc[17], nxt[17];
+    __shared__ uint32_t ctl[2];
+    __syncthreads();
+    for (int s = tid; s < NS; s += 256) {
+        cnt[s] = hist[s];
+        len_s[s] = 0;
+    }
+    for (;;) {
+        __syncthreads();
+        for (int s = tid; s < NS; s += 256) {
+            const uint32_t c = cnt[s];
+            if (c) {
+                int rank = 0;
+                for (int j = 0; j < NS; ++j) {
+                    const uint32_t cj = cnt[j];
+                    rank += (cj != 0u && (cj < c || (cj == c && j < s))) ? 1 : 0;
+                }
+                sw[rank] = c;
+                ssym[rank] = (unsigned short)s;
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int n = 0;
+            for (int s = 0; s < NS; ++s) n += cnt[s] != 0u ? 1 : 0;
+            int leaf = 0, node = n;                               // (n >= 2: a type byte and the end-of-block symbol)
+            for (int q = n; q < 2 * n - 1; ++q) {
+                uint32_t w = 0;
+                for (int rep = 0; rep < 2; ++rep) {
+                    const bool take_leaf = leaf < n && (node >= q || sw[leaf] <= sw[node]);
+                    const int pick = take_leaf ? leaf++ : node++;
+                    w += sw[pick];
+                    parent[pick] = (unsigned short)q;
+                }
+                sw[q] = w;
+            }
+            depth_s[2 * n - 2] = 0;
+            uint32_t deepest = 0;
+            for (int x = 2 * n - 3; x >= 0; --x) {
+                const uint32_t d = depth_s[parent[x]] + 1u;
+                depth_s[x] = (unsigned short)d;
+                if (x < n) deepest = max(deepest, d);
+            }
+            ctl[0] = (uint32_t)n;
+            ctl[1] = deepest;
+        }
+        __syncthreads();
+        if (ctl[1] <= 15u) break;
+        for (int s = tid; s < NS; s += 256) {
+            const uint32_t c = cnt[s];
+            cnt[s] = c ? (c + 1u) >> 1 : 0u;
+        }
+    }
+    for (int i = tid; i < (int)ctl[0]; i += 256) len_s[ssym[i]] = depth_s[i];
+    __syncthreads();
+    uint64_t total = 0;
+    if (tid == 0) {                                               // canonical codes (RFC 1951, 3.2.2), stored bit-reversed
+        for (int b = 0; b <= 16; ++b) blc[b] = 0;
+        for (int s = 0; s < NS; ++s) blc[len_s[s]] += 1u;
+        blc[0] = 0;
+        uint32_t code = 0;
+        nxt[0] = 0;
+        for (int b = 1; b <= 15; ++b) { code = (code + blc[b - 1]) << 1; nxt[b] = code; }
+        uint64_t bits = 0;
+        for (int s = 0; s < NS; ++s) {
+            const uint32_t l = len_s[s];
+            uint32_t e = 0;
+            if (l) {
+                const uint32_t c = nxt[l];
+                nxt[l] = c + 1u;
+                e = (__brev(c) >> (32u - l)) | (l << 16);
+                bits += (uint64_t)hist[s] * l;
+            }
+            sw[s] = e;
+        }
+        total = bits;
+    }
+    __syncthreads();
+    return total;
+}
+
 template <int KIND, int DEPTH, int C>
 __global__ __launch_bounds__(256) void png_filter_kernel(const void* __restrict__ frames, unsigned char* __restrict__ filt,
                                                          uint32_t* __restrict__ table, uint32_t* __restrict__ meta, int H, int W, int R,
                                                          int nseg) {
     constexpr int BPP = C * DEPTH / 8;
     __shared__ uint32_t whist[4][256];
-    __shared__ uint32_t hist[PNG_SYMS], cnt[PNG_SYMS], len_s[PNG_SYMS];
-    __shared__ uint32_t sw[2 * PNG_SYMS];                         // weights: the sorted leaves, then the internal nodes
-    __shared__ unsigned short ssym[PNG_SYMS], parent[2 * PNG_SYMS], depth_s[2 * PNG_SYMS];
-    __shared__ uint32_t blc[17], nxt[17];
-    __shared__ uint32_t adler[2], ctl[2];
+    __shared__ uint32_t hist[PNG_SYMS], sw[2 * PNG_SYMS];
+    __shared__ uint32_t adler[2];
     const int seg = (int)(blockIdx.x % (unsigned)nseg);
     const int64_t t = blockIdx.x / (unsigned)nseg;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -168,89 +276,161 @@ __global__ __launch_bounds__(256) void png_filter_kernel(const void* __restrict_
         if (lane == 0) { atomicAdd(&adler[0], a % PNG_ADLER); atomicAdd(&adler[1], b % PNG_ADLER); }
     }
     __syncthreads();
-    for (int s = tid; s < PNG_SYMS; s += 256) {
-        const uint32_t c = s < 256 ? whist[0][s] + whist[1][s] + whist[2][s] + whist[3][s] : 1u;
-        hist[s] = cnt[s] = c;
-        len_s[s] = 0;
-    }
-
-    // the code: two-queue Huffman over the used symbols, counts halved (rounding up) while the tree is deeper than 15
-    for (;;) {
-        __syncthreads();
-        for (int s = tid; s < PNG_SYMS; s += 256) {
-            const uint32_t c = cnt[s];
-            if (c) {
-                int rank = 0;
-                for (int j = 0; j < PNG_SYMS; ++j) {
-                    const uint32_t cj = cnt[j];
-                    rank += (cj != 0u && (cj < c || (cj == c && j < s))) ? 1 : 0;
-                }
-                sw[rank] = c;
-                ssym[rank] = (unsigned short)s;
-            }
-        }
-        __syncthreads();
-        if (tid == 0) {
-            int n = 0;
-            for (int s = 0; s < PNG_SYMS; ++s) n += cnt[s] != 0u ? 1 : 0;
-            int leaf = 0, node = n;                               // (n >= 2: a type byte and the end-of-block symbol)
-            for (int k = n; k < 2 * n - 1; ++k) {
-                uint32_t w = 0;
-                for (int rep = 0; rep < 2; ++rep) {
-                    const bool take_leaf = leaf < n && (node >= k || sw[leaf] <= sw[node]);
-                    const int pick = take_leaf ? leaf++ : node++;
-                    w += sw[pick];
-                    parent[pick] = (unsigned short)k;
-                }
-                sw[k] = w;
-            }
-            depth_s[2 * n - 2] = 0;
-            uint32_t deepest = 0;
-            for (int x = 2 * n - 3; x >= 0; --x) {
-                const uint32_t d = depth_s[parent[x]] + 1u;
-                depth_s[x] = (unsigned short)d;
-                if (x < n) deepest = max(deepest, d);
-            }
-            ctl[0] = (uint32_t)n;
-            ctl[1] = deepest;
-        }
-        __syncthreads();
-        if (ctl[1] <= 15u) break;
-        for (int s = tid; s < PNG_SYMS; s += 256) {
-            const uint32_t c = cnt[s];
-            cnt[s] = c ? (c + 1u) >> 1 : 0u;
-        }
-    }
-    for (int i = tid; i < (int)ctl[0]; i += 256) len_s[ssym[i]] = depth_s[i];
-    __syncthreads();
-    uint32_t* tab = table + ((int64_t)blockIdx.x) * PNG_TABLE;
-    if (tid == 0) {                                               // canonical codes (RFC 1951, 3.2.2), stored bit-reversed
-        for (int b = 0; b <= 16; ++b) blc[b] = 0;
-        for (int s = 0; s < PNG_SYMS; ++s) blc[len_s[s]] += 1u;
-        blc[0] = 0;
-        uint32_t code = 0;
-        nxt[0] = 0;
-        for (int b = 1; b <= 15; ++b) { code = (code + blc[b - 1]) << 1; nxt[b] = code; }
-        uint64_t bits = 0;
-        for (int s = 0; s < PNG_SYMS; ++s) {
-            const uint32_t l = len_s[s];
-            uint32_t e = 0;
-            if (l) {
-                const uint32_t c = nxt[l];
-                nxt[l] = c + 1u;
-                e = (__brev(c) >> (32u - l)) | (l << 16);
-                bits += (uint64_t)hist[s] * l;
-            }
-            sw[s] = e;
-        }
+    for (int s = tid; s < PNG_SYMS; s += 256) hist[s] = s < 256 ? whist[0][s] + whist[1][s] + whist[2][s] + whist[3][s] : 1u;
+    const uint64_t bits = png_build_code<PNG_SYMS>(hist, sw, tid);
+    if (tid == 0) {
         uint32_t* m = meta + ((int64_t)blockIdx.x) * 4;
         m[0] = (uint32_t)((PNG_HEADER_BITS + bits + 3 + 7) / 8 + 4);
         m[1] = adler[0] % PNG_ADLER;
         m[2] = adler[1] % PNG_ADLER;
-        m[3] = 0;
+        m[3] = (uint32_t)bits;                                    // (the literal block's data bits: png_runs_kernel's; < 2^28)
+    }
+    uint32_t* tab = table + ((int64_t)blockIdx.x) * PNG_TABLE;
+    for (int s = tid; s < PNG_TABLE; s += 256) tab[s] = s < PNG_SYMS ? sw[s] : 0u;
+}
+
+// ---- run-length matches (pngenc.py "Runs"): the tokens of a tile, the second code, the choice
+struct PngTokLds {
+    uint32_t first[256 + PNG_LOOK];                               // per group of PNG_RUN positions: its first run start, or PNG_NONE
+    uint32_t wmax[4];
+};
+
+// the length symbol 257..285 of a match of c = 3..258 bytes, the number of its extra bits and their value (RFC 1951, 3.2.5)
+SVR_DEVICE void png_length_symbol(uint32_t c, uint32_t& sym, uint32_t& extra_n, uint32_t& extra_v) {
+    const uint32_t m = c - 3u;
+    extra_n = (m < 8u || c == PNG_MAX_MATCH) ? 0u : 29u - (uint32_t)__clz(m);      // floor(log2 m) - 2
+    extra_v = m & ((1u << extra_n) - 1u);
+    sym = c == PNG_MAX_MATCH ? 285u : 257u + 4u * extra_n + (m >> extra_n);
+}
+
+// The tokens of the positions [base, base + PNG_TILE) of a segment of n filtered bytes ``src``; every thread of the workgroup
+// calls this, tile after tile in ascending order; lane tid owns the positions base + PNG_RUN tid + j.  tok[j]: a literal's byte
+// 0..255; 256 + c for the head of a match of c bytes; PNG_NONE for a position that emits nothing (covered by a match, or at /
+// past the segment's end).  A position starts a run if it is position 0 or its byte differs from the one before; positions from n
+// on count as starts too, so a run ends with the segment whatever follows it in memory.
+//   forward   each lane's last start, a workgroup-wide running maximum: the start s of the run a lane's stretch begins in --
+//             ``run_start`` carries it from tile to tile, so a run may be as long as the segment;
+//   backward  a match covers at most 258 bytes, so min(rem, 258) is enough (rem: the bytes left in the run): a lane looks for the
+//             next start in the PNG_LOOK groups behind its own, PNG_LOOK of them lying past the tile (their first starts are
+//             found by the first PNG_LOOK lanes).
+// With o = i - s and q = (o - 1) % 258 the specification's c is min(258, rem + q).
+SVR_DEVICE void png_tile_tokens(const unsigned char* __restrict__ src, uint32_t n, uint32_t base, int tid, PngTokLds& L,
+                                uint32_t& run_start, uint32_t* tok) {
+    const int lane = tid & 63, wave = tid >> 6;
+    const uint32_t i0 = base + (uint32_t)tid * PNG_RUN;
+    uint32_t b[PNG_RUN + 1];
+    b[0] = (i0 > 0u && i0 <= n) ? src[i0 - 1u] : 0u;
+    uint32_t starts = 0;                                          // bit j: position i0 + j starts a run
+#pragma unroll
+    for (int j = 0; j < PNG_RUN; ++j) {
+        const uint32_t i = i0 + j;
+        b[j + 1] = i < n ? src[i] : 0u;
+        if (i == 0u || i >= n || b[j + 1] != b[j]) starts |= 1u << j;
+    }
+    __syncthreads();                                              // (the tile before is done with L)
+    L.first[tid] = starts ? i0 + (uint32_t)__ffs((int)starts) - 1u : PNG_NONE;
+    if (tid < PNG_LOOK) {
+        const uint32_t h0 = base + PNG_TILE + (uint32_t)tid * PNG_RUN;
+        uint32_t f = PNG_NONE;
+        for (int j = PNG_RUN - 1; j >= 0; --j) {                  // (descending: the first start is the last one assigned)
+            const uint32_t i = h0 + j;
+            if (i >= n || src[i] != src[i - 1u]) f = i;
+        }
+        L.first[256 + tid] = f;
+    }
+    uint32_t v = starts ? i0 + (32u - (uint32_t)__clz(starts)) : 0u;      // 1 + the lane's last start
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = (uint32_t)__shfl_up((int)v, d);
+        if (lane >= d) v = max(v, o);
+    }
+    if (lane == 63) L.wmax[wave] = v;
+    uint32_t enter = (uint32_t)__shfl_up((int)v, 1);
+    if (lane == 0) enter = 0u;
+    __syncthreads();
+    uint32_t last = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { const uint32_t x = L.wmax[w]; last = max(last, x); if (w < wave) enter = max(enter, x); }
+    uint32_t s = enter ? enter - 1u : run_start;
+    run_start = last ? last - 1u : run_start;
+    uint32_t next = i0 + PNG_RUN * (PNG_LOOK + 1);                // the next start behind the lane's stretch (>= 258 away if none)
+#pragma unroll
+    for (int g = PNG_LOOK; g >= 1; --g) { const uint32_t f = L.first[tid + g]; if (f != PNG_NONE) next = f; }
+    uint32_t rem[PNG_RUN];
+#pragma unroll
+    for (int j = PNG_RUN - 1; j >= 0; --j) {
+        rem[j] = next - (i0 + j);
+        if ((starts >> j) & 1u) next = i0 + j;
+    }
+#pragma unroll
+    for (int j = 0; j < PNG_RUN; ++j) {
+        const uint32_t i = i0 + j;
+        if ((starts >> j) & 1u) s = i;
+        const uint32_t o = i - s, q = o ? (o - 1u) % PNG_MAX_MATCH : 0u;
+        uint32_t t = PNG_NONE;
+        if (i < n) {
+            if (o == 0u || rem[j] + q < 3u) t = b[j + 1];
+            else if (q == 0u) t = 256u + min(rem[j], PNG_MAX_MATCH);
+        }
+        tok[j] = t;
+    }
+}
+
+// One workgroup per (frame, segment), behind png_filter_kernel: the histogram of the tokens over 286 symbols, the second code, the
+// choice.  In: meta[3] = the literal block's data bits.  Out: meta[3] = 1 if the segment is written as a run block -- then meta[0] is
+// that block's size and table2 its code --, else 0 and nothing else changes.
+__global__ __launch_bounds__(256) void png_runs_kernel(const unsigned char* __restrict__ filt, uint32_t* __restrict__ table2,
+                                                       uint32_t* __restrict__ meta, int H, int stride, int R, int nseg) {
+    __shared__ PngTokLds tl;
+    __shared__ uint32_t whist[4][PNG_RUN_SYMS];
+    __shared__ uint32_t hist[PNG_RUN_SYMS], sw[2 * PNG_RUN_SYMS], chosen_s;
+    const int seg = (int)(blockIdx.x % (unsigned)nseg);
+    const int64_t t = blockIdx.x / (unsigned)nseg;
+    const int tid = threadIdx.x, wave = tid >> 6;
+    const int r0 = seg * R, r1 = min(H, r0 + R);
+    const uint32_t n = (uint32_t)(r1 - r0) * (uint32_t)stride;
+    const unsigned char* src = filt + (t * H + r0) * (int64_t)stride;
+    for (int i = tid; i < 4 * PNG_RUN_SYMS; i += 256) (&whist[0][0])[i] = 0;
+    __syncthreads();
+    uint32_t run_start = 0;
+    for (uint32_t base = 0; base < n; base += PNG_TILE) {
+        uint32_t tok[PNG_RUN];
+        png_tile_tokens(src, n, base, tid, tl, run_start, tok);
+#pragma unroll
+        for (int j = 0; j < PNG_RUN; ++j) {
+            if (tok[j] == PNG_NONE) continue;
+            uint32_t sym = tok[j], en, ev;
+            if (sym >= 256u) png_length_symbol(sym - 256u, sym, en, ev);
+            atomicAdd(&whist[wave][sym], 1u);
+        }
     }
     __syncthreads();
-    for (int s = tid; s < PNG_TABLE; s += 256) tab[s] = s < PNG_SYMS ? sw[s] : 0u;
+    for (int s = tid; s < PNG_RUN_SYMS; s += 256) hist[s] = s == 256 ? 1u : whist[0][s] + whist[1][s] + whist[2][s] + whist[3][s];
+    __syncthreads();
+    uint32_t matches = 0, extra = 0;                              // (every thread sums the 29 counts: the branch below is uniform)
+    for (int s = 257; s < PNG_RUN_SYMS; ++s) {
+        const uint32_t c = hist[s];
+        matches += c;
+        extra += c * ((s < 265 || s == 285) ? 0u : (uint32_t)(s - 261) >> 2);
+    }
+    uint32_t* m = meta + ((int64_t)blockIdx.x) * 4;
+    if (matches == 0u) {
+        if (tid == 0) m[3] = 0;
+        return;
+    }
+    const uint64_t bits = png_build_code<PNG_RUN_SYMS>(hist, sw, tid);
+    if (tid == 0) {
+        const uint64_t bits_runs = PNG_RUN_HEADER_BITS + bits + extra + matches, bits_lit = (uint64_t)PNG_HEADER_BITS + m[3];
+        const bool chosen = bits_runs < bits_lit;
+        if (chosen) m[0] = (uint32_t)((bits_runs + 3 + 7) / 8 + 4);
+        m[3] = chosen ? 1u : 0u;
+        chosen_s = chosen ? 1u : 0u;
+    }
+    __syncthreads();
+    if (chosen_s) {
+        uint32_t* tab = table2 + ((int64_t)blockIdx.x) * PNG_RUN_TABLE;
+        for (int s = tid; s < PNG_RUN_TABLE; s += 256) tab[s] = s < PNG_RUN_SYMS ? sw[s] : 0u;
+    }
 }
 
 // one workgroup per frame: segment offsets, sizes[t], the Adler-32 and the stream's head and tail
@@ -304,12 +484,19 @@ __global__ __launch_bounds__(256) void png_scan_kernel(const uint32_t* __restric
     }
 }
 
+// RUNS: a segment whose meta[3] is set (png_runs_kernel) is written as a run block from table2; the others, and every segment
+// without RUNS, as the literal block from table.  An entry e[j] of the tile is value | bits << SH: 16 + 15 bits without RUNS, up
+// to 21 bits of value (code, extra bits, the distance bit 0) with them.
+template <bool RUNS>
 __global__ __launch_bounds__(256) void png_pack_kernel(const unsigned char* __restrict__ filt, const uint32_t* __restrict__ table,
+                                                       const uint32_t* __restrict__ table2, const uint32_t* __restrict__ meta,
                                                        const int64_t* __restrict__ segoff, unsigned char* __restrict__ out, int64_t cap,
                                                        int H, int stride, int R, int nseg) {
-    __shared__ uint32_t tab[PNG_TABLE];
+    constexpr uint32_t SH = RUNS ? 24u : 16u, MASK = (1u << SH) - 1u;
+    __shared__ uint32_t tab[RUNS ? PNG_RUN_TABLE : PNG_TABLE];
     __shared__ uint32_t buf[PNG_BUF_WORDS];
     __shared__ uint32_t wsum[4];
+    __shared__ PngTokLds tl;
     const int seg = (int)(blockIdx.x % (unsigned)nseg);
     const int64_t t = blockIdx.x / (unsigned)nseg;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -319,7 +506,9 @@ __global__ __launch_bounds__(256) void png_pack_kernel(const unsigned char* __re
     const int64_t off0 = segoff[blockIdx.x];
     unsigned char* dst = out + t * cap + off0;
     const int64_t room = cap - off0;                              // no store at or beyond dst[room]
-    for (int i = tid; i < PNG_TABLE; i += 256) tab[i] = table[(int64_t)blockIdx.x * PNG_TABLE + i];
+    const bool runs = RUNS && meta[(int64_t)blockIdx.x * 4 + 3] != 0u;       // (uniform over the workgroup)
+    if (runs) for (int i = tid; i < PNG_RUN_TABLE; i += 256) tab[i] = table2[(int64_t)blockIdx.x * PNG_RUN_TABLE + i];
+    else for (int i = tid; i < PNG_TABLE; i += 256) tab[i] = table[(int64_t)blockIdx.x * PNG_TABLE + i];
     for (int i = tid; i < PNG_BUF_WORDS; i += 256) buf[i] = 0;
     __syncthreads();
 
@@ -335,11 +524,13 @@ __global__ __launch_bounds__(256) void png_pack_kernel(const unsigned char* __re
     };
 
     // the block header: 17 bits, nineteen 3-bit lengths (4 for the code-length symbols 0..15: all but the first three in the
-    // transmitted order), 258 lengths as 4-bit codes (symbol v has code v: written bit-reversed)
-    if (tid == 19) atomicOr(&buf[0], (1u << 2) | (15u << 13));    // BTYPE = 10 (its high bit), HCLEN = 15
+    // transmitted order), 258 lengths as 4-bit codes (symbol v has code v: written bit-reversed) -- 287 in a run block: HLIT = 29,
+    // 286 lengths and the one distance code's length 1
+    const int nsyms = runs ? PNG_RUN_SYMS : PNG_SYMS, header_bits = runs ? PNG_RUN_HEADER_BITS : PNG_HEADER_BITS;
+    if (tid == 19) atomicOr(&buf[0], (1u << 2) | (runs ? 29u << 3 : 0u) | (15u << 13));      // BTYPE = 10 (its high bit), HLIT, HCLEN = 15
     if (tid >= 3 && tid < 19) { const uint32_t bit = 17u + 3u * tid + 2u; atomicOr(&buf[bit >> 5], 1u << (bit & 31u)); }
-    for (int i = tid; i < 258; i += 256) {
-        const uint32_t l = i < PNG_SYMS ? tab[i] >> 16 : 0u;
+    for (int i = tid; i < nsyms + 1; i += 256) {
+        const uint32_t l = i < nsyms ? tab[i] >> 16 : (runs ? 1u : 0u);
         const uint32_t v = __brev(l) >> 28, bit = 74u + 4u * i, sh = bit & 31u;
         if (v) {
             atomicOr(&buf[bit >> 5], v << sh);
@@ -347,17 +538,41 @@ __global__ __launch_bounds__(256) void png_pack_kernel(const unsigned char* __re
         }
     }
     __syncthreads();
-    flush(0, 0u, PNG_HEADER_BITS);
-    int64_t bitpos = PNG_HEADER_BITS;
+    flush(0, 0u, (uint32_t)header_bits);
+    int64_t bitpos = header_bits;
+    uint32_t run_start = 0;
 
     for (int64_t base = 0; base <= n; base += PNG_TILE) {
         const int64_t i0 = base + (int64_t)tid * PNG_RUN;
         uint32_t e[PNG_RUN], nb = 0;
+        if (runs) {
+            uint32_t tok[PNG_RUN];
+            png_tile_tokens(src, (uint32_t)n, (uint32_t)base, tid, tl, run_start, tok);
 #pragma unroll
-        for (int j = 0; j < PNG_RUN; ++j) {
-            const int64_t i = i0 + j;
-            e[j] = i < n ? tab[src[i]] : (i == n ? tab[256] : 0u);
-            nb += e[j] >> 16;
+            for (int j = 0; j < PNG_RUN; ++j) {
+                uint32_t v = 0, bits = 0;
+                if (tok[j] < 256u || i0 + j == n) {
+                    const uint32_t c = tab[i0 + j == n ? 256u : tok[j]];
+                    v = c & 0xFFFFu;
+                    bits = c >> 16;
+                } else if (tok[j] != PNG_NONE) {
+                    uint32_t sym, en, ev;
+                    png_length_symbol(tok[j] - 256u, sym, en, ev);
+                    const uint32_t c = tab[sym];
+                    v = (c & 0xFFFFu) | (ev << (c >> 16));
+                    bits = (c >> 16) + en + 1u;
+                }
+                e[j] = v | (bits << SH);
+                nb += bits;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < PNG_RUN; ++j) {
+                const int64_t i = i0 + j;
+                const uint32_t c = i < n ? tab[src[i]] : (i == n ? tab[256] : 0u);
+                e[j] = RUNS ? (c & 0xFFFFu) | (c >> 16 << SH) : c;
+                nb += c >> 16;
+            }
         }
         uint32_t v = nb;
 #pragma unroll
@@ -376,8 +591,8 @@ __global__ __launch_bounds__(256) void png_pack_kernel(const unsigned char* __re
         uint64_t acc = 0;
 #pragma unroll
         for (int j = 0; j < PNG_RUN; ++j) {
-            acc |= (uint64_t)(e[j] & 0xFFFFu) << fill;
-            fill += e[j] >> 16;
+            acc |= (uint64_t)(e[j] & MASK) << fill;
+            fill += e[j] >> SH;
             if (fill >= 32u) {
                 if (word < (uint32_t)PNG_BUF_WORDS) atomicOr(&buf[word], (uint32_t)acc);
                 ++word;

@@ -104,6 +104,8 @@ SYMBOLS = {
     "svr_pack_yuv420p10": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_png_encode_bytes": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "svr_png_encode": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
+    "svr_png_encode_runs_bytes": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "svr_png_encode_runs": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
     "svr_colorfix_workspace_bytes": (C.c_int64, [_i32]),
     "svr_wavelet_reconstruct": (C.c_int, [_vp, _strides, _vp, _strides, _vp, _strides, _i32, _i32, _i32, _i32, _vp]),
     "svr_lab_planes": (C.c_int, [_vp, _strides, _vp, _strides, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),

@@ -584,19 +584,22 @@ class HipOps:
         return out
 
     # ------------------------------------------------------------------ PNG streams
-    def encode_png_bytes(self, T, H, W, Cn, depth=8):
-        """-> (scratch bytes of one encode_png call, capacity in bytes of each frame's slot of ``out``) for a geometry."""
+    def encode_png_bytes(self, T, H, W, Cn, depth=8, runs=False):
+        """-> (scratch bytes of one encode_png call, capacity in bytes of each frame's slot of ``out``) for a geometry.  The
+        capacity is the same with and without ``runs``; the scratch is larger with them."""
         scratch, cap = C.c_int64(0), C.c_int64(0)
-        if self.lib.svr_png_encode_bytes(int(T), int(H), int(W), int(Cn), int(depth), C.byref(scratch), C.byref(cap)) != 0:
+        fn = self.lib.svr_png_encode_runs_bytes if runs else self.lib.svr_png_encode_bytes
+        if fn(int(T), int(H), int(W), int(Cn), int(depth), C.byref(scratch), C.byref(cap)) != 0:
             raise ValueError(f"encode_png: {self.lib.svr_last_error().decode()}")
         return scratch.value, cap.value
 
-    def encode_png(self, frames, depth=8, out=None, sizes=None):
+    def encode_png(self, frames, depth=8, out=None, sizes=None, runs=False):
         """Output frames encoded as PNG zlib streams on the device (pngenc.py is the specification, byte for byte;
         csrc/svr_png.hip): frames [T, H, W, 3 | 4] fp32 / bf16, dense, ``depth`` 8 or 16 -> (out uint8 [T, cap], sizes int64 [T]):
         frame t's stream is out[t, :sizes[t]] (pngenc.png_file frames it as a file); bytes past it are not written.  Three launches
         on the current stream, no host synchronisation.  ``out``: a dense uint8 [T, >= pngenc.frame_bound(H, W, C, depth)] tensor;
-        ``sizes``: a dense int64 [T] tensor."""
+        ``sizes``: a dense int64 [T] tensor.  ``runs``: the stream with run-length matches (pngenc.encode_frames_spec(...,
+        runs=True); svr_png_encode_runs, four launches) -- never longer than the literal one, and decoding to the same samples."""
         if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
             raise ValueError(f"encode_png: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
         T, H, W, Cn = frames.shape
@@ -607,7 +610,7 @@ class HipOps:
         if T < 1 or H < 1 or W < 1:
             raise ValueError(f"encode_png: frames must hold at least one pixel, got {tuple(frames.shape)}")
         self._chk(frames, None, "encode_png: frames")
-        nscratch, cap = self.encode_png_bytes(T, H, W, Cn, depth)
+        nscratch, cap = self.encode_png_bytes(T, H, W, Cn, depth, runs)
         if out is None:
             out = torch.empty((T, cap), dtype=torch.uint8, device=self.device)
         self._chk(out, torch.uint8, "encode_png: out")
@@ -620,8 +623,9 @@ class HipOps:
             raise ValueError(f"encode_png: sizes must be int64 [{T}], got {tuple(sizes.shape)}")
         scratch = torch.empty(nscratch, dtype=torch.uint8, device=self.device)
         kind = 1 if frames.dtype == torch.float32 else 0                     # SVR_STORE_FP32 / SVR_STORE_BF16
-        hip_lib.check(self.lib.svr_png_encode(_ptr(frames), kind, T, H, W, Cn, int(depth), _ptr(scratch), nscratch, _ptr(out),
-                                              out.shape[1], _ptr(sizes), self._stream()), "svr_png_encode")
+        fn, name = (self.lib.svr_png_encode_runs, "svr_png_encode_runs") if runs else (self.lib.svr_png_encode, "svr_png_encode")
+        hip_lib.check(fn(_ptr(frames), kind, T, H, W, Cn, int(depth), _ptr(scratch), nscratch, _ptr(out), out.shape[1], _ptr(sizes),
+                         self._stream()), name)
         return out, sizes
 
     # ------------------------------------------------------------------ colour correction

@@ -37,7 +37,34 @@ Capacity    A segment of n filtered bytes takes at most segment_bound(n) = 139 +
             ceil(1109 / 8) = 139.  A frame takes at most frame_bound(H, W, C, depth) = 2 + the sum of its segments' bounds + 6.  Both
             are asserted here.
 
-No LZ77 matches and no run lengths: Huffman-only output floors at one bit per byte, so a flat frame compresses 8 : 1 and no better.
+Without ``runs`` there are no LZ77 matches and no run lengths: Huffman-only output floors at one bit per byte, so a flat frame
+compresses 8 : 1 and no better.
+
+Runs        ``runs=True`` (RUNS is the switch the command line reads) changes a segment's deflate block and nothing else: filtering,
+            segments, the Adler-32, 78 01 ... 03 00, the empty stored block behind every segment and the framing stay.  Matches are
+            runs of one byte at DISTANCE 1 only -- a scan, not a string search; other distances would need only more distance
+            codes, and there are still no general matches.
+Tokens      The segment's n filtered bytes, type bytes included, split into maximal runs of equal bytes; matches never leave the
+            segment.  Position i lies in the run [s, s + L) and has o = i - s.  o = 0: a literal.  o >= 1: with k = (o - 1) // 258,
+            j = (o - 1) % 258 and c = min(258, L - 1 - 258 k): c < 3 -> a literal; else j = 0 -> a match of length c at distance 1;
+            else the position emits nothing.  So a run of L <= 3 is all literals; a longer one is a literal, (L - 1) // 258 matches
+            of 258 and a remainder that is one match if it is >= 3 and one or two literals otherwise.  (With rem = s + L - i the
+            bytes left in the run: L - 1 - 258 k = rem + j, so a position's token follows from o and min(rem, 258) alone.)
+Code        The histogram over symbols 0..285: the literals that are emitted, symbol 256 with count 1, the length symbols 257..285
+            (RFC 1951, 3.2.5) of the matches.  Lengths by code_lengths, fed 286 counts; codes canonical.  The distance alphabet has
+            ONE code, symbol 0 (distance 1), of length 1.
+Run block     1. BFINAL = 0, BTYPE = 10, HLIT = 29 (286 codes), HDIST = 0, HCLEN = 15;
+              2. the same nineteen 3-bit code-length-code lengths;
+              3. 286 length nibbles, then one distance nibble for length 1;
+              4. the tokens in order: a literal is its code; a match is the length symbol's code, its extra bits (c - base, least
+                 significant bit first), then the one distance bit 0;
+              5. symbol 256, then the empty stored block.
+            The header is RUN_HEADER_BITS = 17 + 57 + 4 * 287 = 1222 bits; the data bits stay <= 15 (n + 1): a match costs at most
+            15 + 5 + 1 = 21 bits and covers at least 3 bytes.
+Choice      Per segment: bits_lit = 1106 + sum hist_lit len_lit, bits_runs = 1222 + sum hist_runs len_runs + the extra bits + the
+            number of matches.  The run block is written iff the segment has at least one match and bits_runs < bits_lit, strictly;
+            otherwise the segment is the literal block, byte for byte.  So no stream is longer than the literal one --
+            segment_bound and frame_bound hold unchanged, asserted here -- and a frame without a useful run gives the same bytes.
 """
 import struct
 import zlib
@@ -50,8 +77,16 @@ from . import frameio
 SIGNATURE = b"\x89PNG\r\n\x1a\n"
 CLC_ORDER = (16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15)
 HEADER_BITS = 1106
+RUN_HEADER_BITS = 1222
 MAX_BITS = 15
 SEGMENT_BYTES = 65536
+MAX_MATCH = 258
+# RFC 1951, 3.2.5: the base length and the number of extra bits of the length symbols 257..285
+LENGTH_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
+LENGTH_EXTRA = (0, 0, 0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 3, 4, 4, 4, 4, 5, 5, 5, 5, 0)
+# The switch the command line reads (inference_cli.py's writer factory): png output is written with run-length matches.
+RUNS = True
+LITERAL, MATCH, COVERED = 0, 1, 2
 
 
 # ---------------------------------------------------------------------------------------------------------------- geometry
@@ -230,31 +265,99 @@ def _pack_bits(values: np.ndarray, nbits: np.ndarray) -> (np.ndarray, int):
     return np.packbits(bits, bitorder="little"), total
 
 
-def encode_segment(data) -> bytes:
-    """One segment's filtered bytes -> its deflate block and the empty stored block behind it (whole bytes)."""
+def length_symbol(c: int):
+    """A match length 3..258 -> (its symbol 257..285, the number of extra bits, their value c - base); 258 is symbol 285."""
+    if not 3 <= c <= MAX_MATCH:
+        raise ValueError(f"a match is 3..{MAX_MATCH} bytes long, got {c}")
+    k = 28 if c == MAX_MATCH else max(i for i, b in enumerate(LENGTH_BASE[:28]) if b <= c)
+    return 257 + k, LENGTH_EXTRA[k], c - LENGTH_BASE[k]
+
+
+def segment_tokens(data):
+    """One segment's filtered bytes -> (kind, length), int64 [n] each: per position LITERAL, MATCH (a match head; ``length`` its
+    length, 0 elsewhere) or COVERED (the position emits nothing), by the token rule of the docstring."""
+    data = np.frombuffer(bytes(data), dtype=np.uint8)
+    n = data.size
+    i = np.arange(n, dtype=np.int64)
+    first = np.ones(n, dtype=bool)
+    first[1:] = data[1:] != data[:-1]
+    s = np.maximum.accumulate(np.where(first, i, 0))                         # the start of the position's run
+    starts = np.flatnonzero(first)
+    run_len = np.diff(np.append(starts, n))
+    L = run_len[np.cumsum(first) - 1]
+    o = i - s
+    k, j = (o - 1) // MAX_MATCH, (o - 1) % MAX_MATCH
+    c = np.minimum(MAX_MATCH, L - 1 - MAX_MATCH * k)
+    kind = np.where((o == 0) | (c < 3), LITERAL, np.where(j == 0, MATCH, COVERED)).astype(np.int64)
+    return kind, np.where(kind == MATCH, c, 0).astype(np.int64)
+
+
+def _bit_reversed_code(hist):
+    lengths = code_lengths(hist)
+    rev = np.array([reverse_bits(c, l) for c, l in zip(canonical_codes(lengths), lengths)], dtype=np.int64)
+    return lengths, rev, np.array(lengths, dtype=np.int64)
+
+
+def _finish_block(head_v, head_n, values, nbits, rev, lens):
+    values = np.concatenate([np.array(head_v, dtype=np.int64), values, rev[256:257], np.zeros(1, dtype=np.int64)])
+    nbits = np.concatenate([np.array(head_n, dtype=np.int64), nbits, lens[256:257], np.full(1, 3, dtype=np.int64)])
+    packed, _ = _pack_bits(values, nbits)
+    return packed.tobytes() + b"\x00\x00\xff\xff"
+
+
+def segment_choice(data) -> bool:
+    """Whether ``runs=True`` writes this segment as a run block: it has a match and bits_runs < bits_lit."""
+    return _encode_segment(data, True)[1]
+
+
+def _encode_segment(data, runs):
     data = np.frombuffer(bytes(data), dtype=np.uint8)
     n = data.size
     hist = np.bincount(data, minlength=256).tolist() + [1]
-    lengths = code_lengths(hist)
-    codes = canonical_codes(lengths)
-    rev = np.array([reverse_bits(c, l) for c, l in zip(codes, lengths)], dtype=np.int64)
-    lens = np.array(lengths, dtype=np.int64)
+    lengths, rev, lens = _bit_reversed_code(hist)
+    bits_lit = HEADER_BITS + sum(h * l for h, l in zip(hist, lengths))
     head_v = [0, 2, 0, 0, 15] + [0 if s > 15 else 4 for s in CLC_ORDER] + [reverse_bits(l, 4) for l in lengths] + [0]
     head_n = [1, 2, 5, 5, 4] + [3] * 19 + [4] * 258
     assert sum(head_n) == HEADER_BITS
-    values = np.concatenate([np.array(head_v, dtype=np.int64), rev[data], rev[256:257], np.zeros(1, dtype=np.int64)])
-    nbits = np.concatenate([np.array(head_n, dtype=np.int64), lens[data], lens[256:257], np.full(1, 3, dtype=np.int64)])
-    packed, _ = _pack_bits(values, nbits)
-    out = packed.tobytes() + b"\x00\x00\xff\xff"
-    assert len(out) <= segment_bound(n), (len(out), segment_bound(n))
-    return out
+    literal = _finish_block(head_v, head_n, rev[data], lens[data], rev, lens)
+    assert len(literal) == (bits_lit + 3 + 7) // 8 + 4 and len(literal) <= segment_bound(n), (len(literal), segment_bound(n))
+    if not runs:
+        return literal, False
+    kind, length = segment_tokens(data)
+    heads = np.flatnonzero(kind == MATCH)
+    if heads.size == 0:
+        return literal, False
+    sym, extra_n, extra_v = (np.array(v, dtype=np.int64) for v in zip(*(length_symbol(int(c)) for c in length[heads])))
+    lit = data[kind == LITERAL]
+    hist_r = (np.bincount(lit, minlength=256).tolist() + [1] + np.bincount(sym - 257, minlength=29).tolist())
+    lengths_r, rev_r, lens_r = _bit_reversed_code(hist_r)
+    bits_runs = RUN_HEADER_BITS + sum(h * l for h, l in zip(hist_r, lengths_r)) + int(extra_n.sum()) + heads.size
+    if not bits_runs < bits_lit:
+        return literal, False
+    head_v = [0, 2, 29, 0, 15] + [0 if s > 15 else 4 for s in CLC_ORDER] + [reverse_bits(l, 4) for l in lengths_r] + [reverse_bits(1, 4)]
+    head_n = [1, 2, 5, 5, 4] + [3] * 19 + [4] * 287
+    assert sum(head_n) == RUN_HEADER_BITS
+    emit = kind != COVERED
+    values, nbits = np.zeros(n, dtype=np.int64), np.zeros(n, dtype=np.int64)
+    values[kind == LITERAL], nbits[kind == LITERAL] = rev_r[lit], lens_r[lit]
+    values[heads] = rev_r[sym] | (extra_v << lens_r[sym])                   # (the distance bit behind them is 0)
+    nbits[heads] = lens_r[sym] + extra_n + 1
+    assert int(nbits.sum()) + int(lens_r[256]) <= MAX_BITS * (n + 1)
+    out = _finish_block(head_v, head_n, values[emit], nbits[emit], rev_r, lens_r)
+    assert len(out) == (bits_runs + 3 + 7) // 8 + 4 and len(out) <= len(literal), (len(out), len(literal))
+    return out, True
 
 
-def encode_filtered(filtered: np.ndarray) -> bytes:
+def encode_segment(data, runs: bool = False) -> bytes:
+    """One segment's filtered bytes -> its deflate block and the empty stored block behind it (whole bytes)."""
+    return _encode_segment(data, runs)[0]
+
+
+def encode_filtered(filtered: np.ndarray, runs: bool = False) -> bytes:
     """uint8 [H, stride] filtered rows -> the frame's zlib stream"""
     H, stride = filtered.shape
     R = max(1, SEGMENT_BYTES // stride)
-    parts = [b"\x78\x01"] + [encode_segment(filtered[r:r + R].tobytes()) for r in range(0, H, R)]
+    parts = [b"\x78\x01"] + [encode_segment(filtered[r:r + R].tobytes(), runs) for r in range(0, H, R)]
     parts += [b"\x03\x00", struct.pack(">I", zlib.adler32(filtered.tobytes()) & 0xFFFFFFFF)]
     return b"".join(parts)
 
@@ -268,12 +371,12 @@ def frame_samples(frames: torch.Tensor, depth: int) -> np.ndarray:
     return q.astype(np.uint8 if depth == 8 else np.uint16)
 
 
-def encode_frames_spec(frames: torch.Tensor, depth: int = 8):
+def encode_frames_spec(frames: torch.Tensor, depth: int = 8, runs: bool = False):
     """-> list of T ``bytes``: one zlib stream per frame"""
     q = frame_samples(frames, depth)
     T, H, W, C = q.shape
     bound = frame_bound(H, W, C, depth)
-    streams = [encode_filtered(filter_rows(q[t], depth)) for t in range(T)]
+    streams = [encode_filtered(filter_rows(q[t], depth), runs) for t in range(T)]
     assert all(len(s) <= bound for s in streams), (max(map(len, streams)), bound)
     return streams
 

@@ -55,7 +55,7 @@
  *                                              16-byte loads and stores where packed and out are 16-byte aligned (and, for the
  *                                              yuv420p formats, W % 16 == 0), element accesses otherwise
  *   svr_dequant_gguf                           blocks 32 (GGUF's own alignment), out 16; anything else is refused
- *   svr_png_encode                             frames element alignment, scratch 16, sizes 8, out any (byte stores)
+ *   svr_png_encode, svr_png_encode_runs        frames element alignment, scratch 16, sizes 8, out any (byte stores)
  *   svr_wavelet_reconstruct, svr_lab_*,        element accesses only: pixel operands by four element strides (input >= 0, output
  *     svr_chan_stats, svr_adain_apply          >= 1), planes and stats dense fp32; svr_chan_stats' workspace 8
  *   svr_sort_f32, svr_rank_match               operands 4 (dense [n]), workspace 16
@@ -93,6 +93,8 @@ extern "C" {
  * keys and the rank matching of the LAB colour transfer on top of it).  New symbols only.
  * v9, additive: + svr_hsv_planes() / svr_hue_match() / svr_hue_match_workspace_bytes() / svr_hsv_merge() / svr_adaptive_blend() (the
  * HSV half of the colour correction: the `hsv` method and the HSV half and blend of `wavelet_adaptive`).  New symbols only.
+ * v9, additive: + svr_png_encode_runs() / svr_png_encode_runs_bytes() (the PNG streams with run-length matches at distance 1; never
+ * longer than svr_png_encode()'s).  New symbols only; svr_png_encode and its bytes are untouched.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -428,6 +430,16 @@ int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H,
 int svr_png_encode_bytes(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes, int64_t* capacity);
 int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, void* scratch,
                    int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream);
+/* The same with run-length matches (pngenc.py "Runs", encode_frames_spec(..., runs=True), byte for byte): a segment's bytes split
+ * into maximal runs of one byte; a run longer than 3 is a literal, matches of up to 258 bytes at DISTANCE 1 and at most two more
+ * literals; a second code over 286 symbols (the same construction; one distance code of length 1; 1222 header bits); per segment
+ * the run block is written iff it has a match and is strictly smaller in bits than the literal block, else the literal block of
+ * svr_png_encode().  So no stream is longer than svr_png_encode()'s, a frame without a useful run gives the same bytes, and the
+ * capacity is the same; the scratch is larger (svr_png_encode_runs_bytes()).  Same arguments, same checks, same guarantees; four
+ * launches on `stream`. */
+int svr_png_encode_runs_bytes(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes, int64_t* capacity);
+int svr_png_encode_runs(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, void* scratch,
+                        int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream);
 
 /* ---- colour correction ------------------------------------------------------------------------ */
 /* colorfix.py (the specification; src/utils/color_fix.py).  Pixel operands are fp32 (kind = SVR_STORE_FP32, the only kind served)

@@ -503,13 +503,14 @@ class PngWriter:
     frame of an image job goes to ``path`` itself.  ``depth`` 8 or 16 bits per sample.  ``streams`` tells FrameSink that the writer
     also takes frames already encoded where they live (pngenc.py / csrc/svr_png.hip): write_streams() frames each zlib stream as a
     file -- chunk CRCs and file I/O, no deflate on this thread.  write() takes uint8 frames (through PIL, as always) or uint16
-    frames (16-bit files through pngenc.write_png)."""
+    frames (16-bit files through pngenc.write_png).  ``runs``: FrameSink asks the backend for streams with run-length matches
+    (pngenc.py "Runs": smaller files of the same samples)."""
     fmt, alpha, streams = "rgb8", True, True
 
-    def __init__(self, path: str, single: bool = False, depth: int = 8):
+    def __init__(self, path: str, single: bool = False, depth: int = 8, runs: bool = False):
         if depth not in (8, 16):
             raise ValueError(f"depth must be 8 or 16, got {depth}")
-        self.path, self.single, self.index, self.depth = path, single, 0, depth
+        self.path, self.single, self.index, self.depth, self.runs = path, single, 0, depth, bool(runs)
 
     def write(self, arr, height, width):
         from PIL import Image
@@ -665,7 +666,7 @@ class FrameSink:
     copies the result into one of TWO host buffers (pinned for device frames) and hands it to ONE writer thread through a queue of depth 2, so the encoder works while the next chunk computes.  The thread makes no GPU
     call.  An exception of the writer is raised in the caller's thread at the next put() or at close().
     A writer whose ``streams`` attribute is true (PngWriter) and a backend with ``encode_png`` on the frames' device: the frames are
-    ENCODED there (pngenc.py / csrc/svr_png.hip, at the writer's ``depth``), only the bytes produced are copied to the host buffer
+    ENCODED there (pngenc.py / csrc/svr_png.hip, at the writer's ``depth``, with run-length matches if its ``runs`` is true), only the bytes produced are copied to the host buffer
     and the thread frames and writes them (EncodedFrames -> write_streams).  A writer of ``depth`` 16 without such a backend is
     handed uint16 samples (frameio.codes(., 65535)); every other case is as above, byte for byte."""
 
@@ -728,7 +729,10 @@ class FrameSink:
         if getattr(self.writer, "streams", False) and hasattr(self.ops, "encode_png") and \
                 frames.device.type == torch.device(getattr(self.ops, "device", "cuda")).type:
             # encoded where the frames live: only the bytes produced cross to the host, the writer thread frames and writes them
-            out, sizes = self.ops.encode_png(frames.contiguous(), depth)
+            if getattr(self.writer, "runs", False):
+                out, sizes = self.ops.encode_png(frames.contiguous(), depth, runs=True)
+            else:
+                out, sizes = self.ops.encode_png(frames.contiguous(), depth)
             sizes = [int(n) for n in sizes.cpu().tolist()]       # (returns when the streams are there)
             nbytes = sum(sizes)
             slot = self.free.get()
@@ -778,7 +782,7 @@ def open_writer(fmt: str, path: str, fps: float, single: bool = False, video_bac
     if fmt == "pt":
         return TensorWriter(path)
     if fmt == "png":
-        return PngWriter(path, single, depth)
+        return PngWriter(path, single, depth, runs=_pngenc().RUNS)
     if video_backend == "ffmpeg":
         return FFmpegWriter(ffmpeg or find_ffmpeg(), path, fps, ten_bit, audio, colour)
     return OpenCVWriter(path, fps)
