@@ -280,7 +280,11 @@ int svr_qknorm_rope(void* qkv, int64_t rows, int32_t heads, const int16_t* pos, 
  * mmattn.py:245-264 (gather by window, text rows appended to every window, scatter back).
  * qkv bf16 [*, 3*heads*D] (q|k|v); seq_rows int32 [total] = source row of each window position;
  * out_rows int32 [total] = destination row in `out` (bf16 [*, heads*D]); cu int32 [n_seq+1].
- * ld_qkv >= 3*heads*D, ld_out >= heads*D; alignment: "Operand layouts" above.                       */
+ * ld_qkv >= 3*heads*D, ld_out >= heads*D; alignment: "Operand layouts" above.
+ * Size limit: the window kernel (head_dim 128, max_len <= 2048) keeps each window row's byte offset
+ * seq_rows[i] * ld_qkv * 2 in 16-byte units in 32 bits, so every row that seq_rows names must start below
+ * byte 2^36 (64 GiB) of qkv.  A row beyond that would wrap silently: the row indices are device data, the
+ * launcher cannot see them.  (The largest qkv of the 7B model, 65 frames at 4K, is 10.2 GB.)          */
 int svr_attn_varlen(const void* qkv, int64_t ld_qkv, void* out, int64_t ld_out,
                     const int32_t* seq_rows, const int32_t* out_rows, const int32_t* cu,
                     int32_t n_seq, int32_t max_len, int32_t heads, int32_t head_dim, float scale,
