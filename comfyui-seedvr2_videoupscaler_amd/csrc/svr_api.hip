@@ -24,6 +24,7 @@
 #include "svr_rank.hip"
 #include "svr_hsv.hip"
 #include "svr_gguf.hip"
+#include "svr_shots.hip"
 
 using namespace svr;
 
@@ -543,6 +544,40 @@ int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H,
     launch_pack_yuv420p10(frames, x_kind, T, H, W, pack_coef(matrix, range), siting == SVR_COLOUR_SITING_LEFT, (unsigned short*)out,
                           (hipStream_t)stream);
     return check(hipGetLastError(), "svr_pack_yuv420p10");
+}
+
+// ---- frame signatures for cut detection (svr_shots.hip)
+int svr_frame_signatures(const void* frames, int32_t kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t* sig,
+                         int64_t sig_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const char* why = nullptr;
+    if (!frames) why = "frames is a null pointer";
+    else if (!sig) why = "sig is a null pointer";
+    else if (kind != SVR_STORE_BF16 && kind != SVR_STORE_FP32) why = "kind must be SVR_STORE_BF16 or SVR_STORE_FP32";
+    else if (T < 1) why = "need T >= 1";
+    else if (H < 4) why = "H must be at least 4 (one pixel row per cell row)";
+    else if (W < 4) why = "W must be at least 4 (one pixel column per cell column)";
+    else if (C != 3 && C != 4) why = "C must be 3 or 4";
+    else if ((int64_t)H * W >= ((int64_t)1 << 31)) why = "H * W must stay below 2^31 pixels (the counters are int32)";
+    else if ((uintptr_t)frames % (kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
+    else if ((uintptr_t)sig % 4) why = "sig is not aligned to 4 bytes";
+    if (why) { snprintf(g_err, sizeof(g_err), "svr_frame_signatures: %s", why); return -1; }
+    if (sig_bytes != (int64_t)T * 4096) {
+        snprintf(g_err, sizeof(g_err), "svr_frame_signatures: sig_bytes is %lld, int32 [T, 1024] is exactly %lld", (long long)sig_bytes,
+                 (long long)T * 4096);
+        return -1;
+    }
+    const int bands = (int)((((int64_t)H + 3) / 4 + SIG_BAND_ROWS - 1) / SIG_BAND_ROWS);      // of the tallest cell row
+    const int64_t grid = (int64_t)T * 4 * bands;
+    if (grid > 0x7fffffffll) return fail("svr_frame_signatures: T * H needs more than 2^31 - 1 workgroups");
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = check(hipMemsetAsync(sig, 0, (size_t)sig_bytes, s), "svr_frame_signatures")) return rc;
+    const int vec = (uintptr_t)frames % 16 == 0;
+#define SVR_SIG(KIND, CH) hipLaunchKernelGGL((signature_kernel<KIND, CH>), dim3((unsigned)grid), dim3(256), 0, s, frames, (int*)sig, H, W, bands, vec)
+    if (kind == SVR_STORE_FP32) { if (C == 3) SVR_SIG(SVR_STORE_FP32, 3); else SVR_SIG(SVR_STORE_FP32, 4); }
+    else { if (C == 3) SVR_SIG(SVR_STORE_BF16, 3); else SVR_SIG(SVR_STORE_BF16, 4); }
+#undef SVR_SIG
+    return check(hipGetLastError(), "svr_frame_signatures");
 }
 
 // ---- PNG streams encoded on the device (svr_png.hip)

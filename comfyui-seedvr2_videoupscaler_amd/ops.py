@@ -583,6 +583,32 @@ class HipOps:
                                                   out.numel() * out.element_size(), self._stream()), "svr_pack_yuv420p10")
         return out
 
+    # ------------------------------------------------------------------ frame signatures (cut detection)
+    def frame_signatures(self, frames, out=None):
+        """Per frame the 4 x 4 grid of 64-bin luma histograms cut detection compares (shots.py is the specification, bit for bit;
+        csrc/svr_shots.hip): frames [T, H, W, 3 | 4] fp32 / bf16, dense, H >= 4, W >= 4 -> int32 [T, 1024].  The call zeroes the
+        result itself; one memset and one launch on the current stream, no host synchronisation.  ``out``: a dense int32 [T, 1024]
+        tensor."""
+        if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
+            raise ValueError(f"frame_signatures: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
+        T, H, W, Cn = frames.shape
+        if Cn not in (3, 4):
+            raise ValueError(f"frame_signatures: frames must have C = 3 or 4, got C = {Cn}")
+        if T < 1 or H < 4 or W < 4:
+            raise ValueError(f"frame_signatures: frames must hold T >= 1 frames of H >= 4, W >= 4, got {tuple(frames.shape)}")
+        if H * W >= 1 << 31:
+            raise ValueError(f"frame_signatures: frames of H * W = {H * W} pixels; the int32 counters hold fewer than 2^31")
+        self._chk(frames, None, "frame_signatures: frames")
+        if out is None:
+            out = torch.empty((T, 1024), dtype=torch.int32, device=self.device)
+        self._chk(out, torch.int32, "frame_signatures: out")
+        if tuple(out.shape) != (T, 1024):
+            raise ValueError(f"frame_signatures: out must be {(T, 1024)}, got {tuple(out.shape)}")
+        kind = 1 if frames.dtype == torch.float32 else 0                       # SVR_STORE_FP32 / SVR_STORE_BF16
+        hip_lib.check(self.lib.svr_frame_signatures(_ptr(frames), kind, T, H, W, Cn, _ptr(out), out.numel() * 4, self._stream()),
+                      "svr_frame_signatures")
+        return out
+
     # ------------------------------------------------------------------ PNG streams
     def encode_png_bytes(self, T, H, W, Cn, depth=8, runs=False):
         """-> (scratch bytes of one encode_png call, capacity in bytes of each frame's slot of ``out``) for a geometry.  The

@@ -24,7 +24,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import alpha as alpha_mod, colorfix, transforms
+from . import alpha as alpha_mod, colorfix, shots, transforms
 
 
 @dataclass
@@ -250,7 +250,80 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
     return (final, spans) if return_spans else final
 
 
-def upscale_stream(chunks, runner, text_pos: torch.Tensor, *, temporal_overlap: int = 0, prepend_frames: int = 0, **upscale_kwargs):
+def _signatures(frames: torch.Tensor, runner) -> torch.Tensor:
+    """shots.signatures of clip frames on the runner's device, through the runner's backend (dense, fp32 unless bf16)."""
+    if frames.dtype not in (torch.float32, torch.bfloat16):
+        frames = frames.float()
+    return shots.signatures(frames.to(runner.dit.device).contiguous(), getattr(runner.dit, "ops", None))
+
+
+def _refuse_for_shots(who: str, upscale_kwargs: dict):
+    for name in ("batch_filter", "exchange_heads", "return_spans"):
+        if upscale_kwargs.get(name):
+            raise ValueError(f"{who}: {name} is not served with cuts (a shot is a clip of its own; sharding one over ranks is out of scope)")
+
+
+@torch.no_grad()
+def upscale_shots(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, cuts, **upscale_kwargs):
+    """``upscale`` with no batch across a cut: every shot is a clip of its own.  ``cuts``: a sorted list of the frame indices that
+    start a shot (shots.split's rule), or a shots.Detector, which is fed the signatures of the clip (shots.signatures through the
+    runner's backend: one launch and one read-back of T distances).  The result is, bit for bit, the concatenation of
+    ``upscale(images[a:b], ...same keyword arguments...)`` over the shots [a, b): ``prepend_frames``, ``uniform_batch_size``, the
+    noise seeds and the overlap blend all apply per shot.  ``batch_filter``, ``exchange_heads`` and ``return_spans`` are refused."""
+    _refuse_for_shots("upscale_shots", upscale_kwargs)
+    if images_thwc.dim() != 4 or images_thwc.shape[-1] not in (3, 4) or images_thwc.shape[0] == 0:
+        raise ValueError(f"images must be [T >= 1, H, W, 3] (RGB) or [T >= 1, H, W, 4] (RGBA), got {tuple(images_thwc.shape)}")
+    if isinstance(cuts, shots.Detector):
+        first = cuts.count
+        cuts = [c - first for c in cuts.feed(_signatures(images_thwc, runner))]
+    spans = shots.split(images_thwc.shape[0], cuts)
+    if len(spans) == 1:
+        return upscale(images_thwc, runner, text_pos, **upscale_kwargs)
+    return torch.cat([upscale(images_thwc[a:b], runner, text_pos, **upscale_kwargs) for a, b in spans], dim=0)
+
+
+def _upscale_stream_shots(chunks, runner, text_pos, cuts, temporal_overlap, prepend_frames, upscale_kwargs):
+    """upscale_stream with ``cuts``: each chunk in pieces that end at its cuts."""
+    _refuse_for_shots("upscale_stream", upscale_kwargs)
+    detector = cuts if isinstance(cuts, shots.Detector) else None
+    if detector is None:
+        cuts = [int(c) for c in cuts]
+        if any(c < 0 for c in cuts) or any(b <= a for a, b in zip(cuts, cuts[1:])):
+            raise ValueError(f"cuts must be strictly increasing frame indices, got {cuts}")
+    tail, base, shot_start = None, 0, 0                  # base: the clip index of the chunk's first frame; shot_start: of its shot's
+    for k, chunk in enumerate(chunks):
+        if chunk.dim() != 4 or chunk.shape[0] == 0:
+            raise ValueError(f"chunk {k} must be [t, H, W, 3 | 4] with t >= 1, got {tuple(chunk.shape)}")
+        t = chunk.shape[0]
+        if detector is not None:
+            first = detector.count
+            local = [c - first for c in detector.feed(_signatures(chunk, runner))]
+        else:
+            local = [c - base for c in cuts if base <= c < base + t]
+        starts_shot = k == 0 or (bool(local) and local[0] == 0)                # (the clip's first frame starts a shot by itself)
+        outs = []
+        for j, (a, b) in enumerate(shots.split(t, [c for c in local if c > 0])):
+            frames, context = chunk[a:b], 0
+            if j == 0 and not starts_shot and tail is not None and temporal_overlap > 0:
+                context = min(temporal_overlap, tail.shape[0], base - shot_start)          # never behind the last cut; >= 1
+                frames = torch.cat([tail[-context:].to(chunk.device), frames], dim=0)
+            out = upscale(frames, runner, text_pos, temporal_overlap=temporal_overlap,
+                          prepend_frames=prepend_frames if (j > 0 or starts_shot) else 0, **upscale_kwargs)
+            outs.append(out[context:] if context > 0 else out)
+            del frames, out
+        if local:
+            shot_start = base + local[-1]
+        base += t
+        tail = chunk[-temporal_overlap:].clone() if temporal_overlap > 0 else None
+        del chunk
+        out = outs[0] if len(outs) == 1 else torch.cat(outs, dim=0)
+        del outs
+        yield out
+        del out
+
+
+def upscale_stream(chunks, runner, text_pos: torch.Tensor, *, temporal_overlap: int = 0, prepend_frames: int = 0, cuts=None,
+                   **upscale_kwargs):
     """A clip too long to hold, as a stream: ``chunks`` is any iterable of [t, H, W, 3 | 4] tensors (consecutive pieces of one
     clip), the generator yields one upscaled [t, H', W', C] tensor per chunk.  The reference's ``_stream_video_chunks``
     (inference_cli.py:621-718): chunk k > 0 is upscaled with the last min(temporal_overlap, t_prev) RAW input frames of chunk k - 1
@@ -261,7 +334,19 @@ def upscale_stream(chunks, runner, text_pos: torch.Tensor, *, temporal_overlap: 
 
     Memory: nothing of chunk k stays referenced here once chunk k + 1 is yielded except its raw input tail (``temporal_overlap``
     input frames), so device memory is bounded by one chunk whatever the clip's length -- provided the caller drops (or packs,
-    frameio.pack_frames) each yielded tensor before asking for the next."""
+    frameio.pack_frames) each yielded tensor before asking for the next.
+
+    ``cuts`` (None: everything above, unchanged): a shots.Detector, which is fed each chunk's signatures, or a sorted list of the clip
+    frame indices that start a shot.  A chunk is then split into pieces at its cuts and each piece goes through ``upscale``; the
+    outputs are concatenated, so the generator still yields one tensor per chunk.  The first piece of a chunk continues the previous
+    chunk's shot: it gets the usual context, shortened so that it never reaches behind the last cut -- none, and ``prepend_frames``
+    instead, if the chunk's first frame is itself a cut.  Every later piece starts a shot: no context, and ``prepend_frames``.  No
+    batch and no context then spans a cut; a clip without cuts streams to the same bits as with ``cuts=None``.  The memory
+    statement holds: besides the raw tail the generator keeps the detector's state (one signature of 4 KB and at most ``window``
+    integers), and the pieces' outputs live only until they are concatenated into the chunk's."""
+    if cuts is not None:
+        yield from _upscale_stream_shots(chunks, runner, text_pos, cuts, temporal_overlap, prepend_frames, upscale_kwargs)
+        return
     tail = None
     for k, chunk in enumerate(chunks):
         if chunk.dim() != 4 or chunk.shape[0] == 0:

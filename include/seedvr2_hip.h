@@ -62,6 +62,8 @@
  *   svr_hsv_planes, svr_hsv_merge,             as svr_lab_*: pixel operands by four element strides, planes dense fp32, element
  *     svr_adaptive_blend                       accesses only
  *   svr_hue_match                              planes 4 (dense [n]), workspace 16
+ *   svr_frame_signatures                       element alignment is enough (frames 4 / 2 bytes for fp32 / bf16, sig 4); 16-byte loads
+ *                                              where frames is 16-byte aligned, element accesses otherwise
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -95,6 +97,8 @@ extern "C" {
  * HSV half of the colour correction: the `hsv` method and the HSV half and blend of `wavelet_adaptive`).  New symbols only.
  * v9, additive: + svr_png_encode_runs() / svr_png_encode_runs_bytes() (the PNG streams with run-length matches at distance 1; never
  * longer than svr_png_encode()'s).  New symbols only; svr_png_encode and its bytes are untouched.
+ * v9, additive: + svr_frame_signatures() (per frame a 4 x 4 grid of 64-bin luma histograms: what cut detection compares).  A new
+ * symbol only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -416,6 +420,18 @@ int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, in
 #define SVR_COLOUR_SITING_LEFT   1
 int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t matrix, int32_t range,
                        int32_t siting, void* out, int64_t out_bytes, void* stream);
+
+/* ---- frame signatures for cut detection ---------------------------------------------------------- */
+/* shots.py (the specification, bit for bit): frames [T, H, W, C] dense, fp32 or bf16 (kind SVR_STORE_FP32 / SVR_STORE_BF16), C = 3 or
+ * 4 (a fourth channel is ignored), H >= 4, W >= 4, H * W < 2^31 -> sig int32 [T, 1024], indexed [cell_row * 4 + cell_col][bin]: the
+ * number of pixels of frame t with cell_row = (y * 4) / H, cell_col = (x * 4) / W and bin = Y8 >> 2, where
+ *   q  = rint(clamp(x, 0, 1) * 255) per channel (ties to even; NaN -> 0, +inf -> 255, -inf -> 0)
+ *   Y8 = (13933 r + 46871 g + 4732 b + 32768) >> 16          (the BT.709 luma weights of SVR_PACK_YUV420P10; 0..255).
+ * Every row of sig sums to H * W.  The call itself zeroes sig on `stream` (what the buffer held does not matter), then one launch
+ * adds the counts with integer atomics: two calls give the same bits.  Every argument is checked before anything is enqueued;
+ * sig_bytes must be EXACTLY T * 4096.  No host synchronisation, no workspace. */
+int svr_frame_signatures(const void* frames, int32_t kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t* sig,
+                         int64_t sig_bytes, void* stream);
 
 /* ---- PNG streams encoded on the device ------------------------------------------------------- */
 /* pngenc.py (the specification, byte for byte): frames [T, H, W, C] dense, fp32 or bf16 (x_kind SVR_STORE_FP32 / SVR_STORE_BF16),

@@ -27,7 +27,10 @@ two parsers by ``ast``), so existing scripts keep working.  What the flags DO is
     copied into an mp4 the ffmpeg writer produces;
   * png output of frames on the device is encoded there (pngenc.py / csrc/svr_png.hip; the writer thread does CRCs and file I/O),
     as 16-bit files where the source is deeper than 8 bits (output_depth: a video read through ffmpeg as rgb16 / yuv420p10, a
-    16-bit RGB / RGBA png still, which load_frames reads with its 16 bits), as 8-bit files otherwise.
+    16-bit RGB / RGBA png still, which load_frames reads with its 16 bits), as 8-bit files otherwise (DESIGN.md 7.3d);
+  * shot-aware batching has no flag -- the flag set equals the reference's: where shots.ENABLED is set (it ships
+    off) and one GPU does the work, hard cuts are found on the device (shots.py / csrc/svr_shots.hip) and no batch, and no
+    --chunk_size context, spans one (``pipeline.upscale_shots`` / ``upscale_stream(cuts=...)``).
 """
 import argparse
 import json
@@ -61,6 +64,29 @@ def _itf():
 def _pngenc():
     import importlib
     return importlib.import_module(f"{PKG}.pngenc")
+
+
+def _shots():
+    import importlib
+    return importlib.import_module(f"{PKG}.shots")
+
+
+_shots_warned = False
+
+
+def shot_detector(rank: int, world: int):
+    """A shots.Detector(**shots.DEFAULTS) where shots.ENABLED is set and one rank does the work, else None: with the switch off
+    (the shipped state) nothing changes; with several ranks a shot cannot be sharded yet, which is said once on rank 0."""
+    global _shots_warned
+    shots = _shots()
+    if not shots.ENABLED:
+        return None
+    if world > 1:
+        if rank == 0 and not _shots_warned:
+            print(f"Warning: shot-aware batching serves one GPU; {world} ranks batch by arithmetic alone", file=sys.stderr)
+        _shots_warned = True
+        return None
+    return shots.Detector(**shots.DEFAULTS)
 
 
 def output_depth(inp: str, info: Optional[dict] = None) -> int:
@@ -864,8 +890,11 @@ def run(args, frames, eng=None, **override):
     runner, text, kw, rank, world = eng if eng is not None else engines(args)
     kw = {**kw, **override}
     t0 = time.time()
+    detector = shot_detector(rank, world)              # (None unless shots.ENABLED: no batch across a cut)
     if world > 1:                                      # only rank 0 writes the result: gather the frames there, not everywhere
         out = dist_mod.upscale_sharded(frames.to(runner.dit.device), runner, text, gather="root", **kw)
+    elif detector is not None:
+        out = pipeline.upscale_shots(frames.to(runner.dit.device), runner, text, cuts=detector, **kw)
     else:
         out = pipeline.upscale(frames.to(runner.dit.device), runner, text, **kw)
     _sync(runner)
@@ -886,8 +915,9 @@ def run_stream(args, chunks, eng=None):
     pipeline = importlib.import_module(f"{PKG}.pipeline")
     eng = eng if eng is not None else engines(args)
     runner, text, kw, rank, world = eng
+    detector = shot_detector(rank, world)              # one detector down the whole stream; None unless shots.ENABLED
     if world == 1:
-        yield from pipeline.upscale_stream((c.to(runner.dit.device) for c in chunks), runner, text, **kw)
+        yield from pipeline.upscale_stream((c.to(runner.dit.device) for c in chunks), runner, text, cuts=detector, **kw)
         return
     tail, overlap = None, args.temporal_overlap
     for k, chunk in enumerate(chunks):
