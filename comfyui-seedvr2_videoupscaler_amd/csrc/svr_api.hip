@@ -25,6 +25,7 @@
 #include "svr_hsv.hip"
 #include "svr_gguf.hip"
 #include "svr_shots.hip"
+#include "svr_active.hip"
 
 using namespace svr;
 
@@ -578,6 +579,40 @@ int svr_frame_signatures(const void* frames, int32_t kind, int32_t T, int32_t H,
     else { if (C == 3) SVR_SIG(SVR_STORE_BF16, 3); else SVR_SIG(SVR_STORE_BF16, 4); }
 #undef SVR_SIG
     return check(hipGetLastError(), "svr_frame_signatures");
+}
+
+// ---- active-area profile of a letterboxed clip (svr_active.hip)
+int svr_active_profile(const void* frames, int32_t kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t dark, int32_t* out,
+                       int64_t out_bytes, void* stream) {
+    StreamDeviceGuard on_stream_device(stream);
+    const char* why = nullptr;
+    if (!frames) why = "frames is a null pointer";
+    else if (!out) why = "out is a null pointer";
+    else if (kind != SVR_STORE_BF16 && kind != SVR_STORE_FP32) why = "kind must be SVR_STORE_BF16 or SVR_STORE_FP32";
+    else if (T < 1) why = "need T >= 1";
+    else if (H < 1) why = "H must be at least 1";
+    else if (W < 1) why = "W must be at least 1";
+    else if (C != 3 && C != 4) why = "C must be 3 or 4";
+    else if (dark < 0 || dark > 255) why = "dark must lie in 0..255";
+    else if ((int64_t)T * (H > W ? H : W) >= ((int64_t)1 << 31)) why = "T * max(H, W) must stay below 2^31 (the counters are int32)";
+    else if ((uintptr_t)frames % (kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
+    else if ((uintptr_t)out % 4) why = "out is not aligned to 4 bytes";
+    if (why) { snprintf(g_err, sizeof(g_err), "svr_active_profile: %s", why); return -1; }
+    if (out_bytes != ((int64_t)H + W) * 4) {
+        snprintf(g_err, sizeof(g_err), "svr_active_profile: out_bytes is %lld, int32 [H + W] is exactly %lld", (long long)out_bytes,
+                 (long long)(((int64_t)H + W) * 4));
+        return -1;
+    }
+    const int bands = (int)(((int64_t)H + ACT_BAND_ROWS - 1) / ACT_BAND_ROWS);
+    const int64_t grid = (int64_t)T * bands;                                                  // <= T * H < 2^31
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = check(hipMemsetAsync(out, 0, (size_t)out_bytes, s), "svr_active_profile")) return rc;
+    const int vec = (uintptr_t)frames % 16 == 0;
+#define SVR_ACT(KIND, CH) hipLaunchKernelGGL((active_profile_kernel<KIND, CH>), dim3((unsigned)grid), dim3(256), 0, s, frames, (int*)out, H, W, bands, (uint32_t)dark, vec)
+    if (kind == SVR_STORE_FP32) { if (C == 3) SVR_ACT(SVR_STORE_FP32, 3); else SVR_ACT(SVR_STORE_FP32, 4); }
+    else { if (C == 3) SVR_ACT(SVR_STORE_BF16, 3); else SVR_ACT(SVR_STORE_BF16, 4); }
+#undef SVR_ACT
+    return check(hipGetLastError(), "svr_active_profile");
 }
 
 // ---- PNG streams encoded on the device (svr_png.hip)

@@ -103,6 +103,7 @@ SYMBOLS = {
     "svr_pack_frames": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_pack_yuv420p10": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_frame_signatures": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "svr_active_profile": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_png_encode_bytes": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "svr_png_encode": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _vp, _vp]),
     "svr_png_encode_runs_bytes": (C.c_int, [_i32, _i32, _i32, _i32, _i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -609,6 +609,34 @@ class HipOps:
                       "svr_frame_signatures")
         return out
 
+    # ------------------------------------------------------------------ active-area profile (letterbox bars)
+    def active_profile(self, frames, dark, out=None):
+        """Per row and per column of a clip the number of pixels, over all frames, whose 8-bit luma exceeds ``dark`` (active.py is
+        the specification, bit for bit; csrc/svr_active.hip): frames [T, H, W, 3 | 4] fp32 / bf16, dense, T * max(H, W) < 2^31,
+        dark an integer in 0..255 -> int32 [H + W], rows first.  The call zeroes the result itself; one memset and one launch on
+        the current stream, no host synchronisation.  ``out``: a dense int32 [H + W] tensor."""
+        if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
+            raise ValueError(f"active_profile: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
+        T, H, W, Cn = frames.shape
+        if Cn not in (3, 4):
+            raise ValueError(f"active_profile: frames must have C = 3 or 4, got C = {Cn}")
+        if T < 1 or H < 1 or W < 1:
+            raise ValueError(f"active_profile: frames must hold T >= 1 frames of H >= 1, W >= 1, got {tuple(frames.shape)}")
+        if T * max(H, W) >= 1 << 31:
+            raise ValueError(f"active_profile: frames of T * max(H, W) = {T * max(H, W)}; the int32 counters hold fewer than 2^31")
+        if isinstance(dark, bool) or not isinstance(dark, int) or not 0 <= dark <= 255:
+            raise ValueError(f"active_profile: dark must be an integer in 0..255, got {dark!r}")
+        self._chk(frames, None, "active_profile: frames")
+        if out is None:
+            out = torch.empty((H + W,), dtype=torch.int32, device=self.device)
+        self._chk(out, torch.int32, "active_profile: out")
+        if tuple(out.shape) != (H + W,):
+            raise ValueError(f"active_profile: out must be {(H + W,)}, got {tuple(out.shape)}")
+        kind = 1 if frames.dtype == torch.float32 else 0                       # SVR_STORE_FP32 / SVR_STORE_BF16
+        hip_lib.check(self.lib.svr_active_profile(_ptr(frames), kind, T, H, W, Cn, dark, _ptr(out), out.numel() * 4, self._stream()),
+                      "svr_active_profile")
+        return out
+
     # ------------------------------------------------------------------ PNG streams
     def encode_png_bytes(self, T, H, W, Cn, depth=8, runs=False):
         """-> (scratch bytes of one encode_png call, capacity in bytes of each frame's slot of ``out``) for a geometry.  The

@@ -24,7 +24,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 
 import torch
 
-from . import alpha as alpha_mod, colorfix, shots, transforms
+from . import active, alpha as alpha_mod, colorfix, shots, transforms
 
 
 @dataclass
@@ -53,11 +53,12 @@ def plan_batches(total_frames: int, batch_size: int, temporal_overlap: int = 0,
 
 
 def prepare_batch(images_thwc: torch.Tensor, plan: BatchPlan, resolution: int, max_resolution: int = 0,
-                  dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+                  dtype: Optional[torch.dtype] = None, size: Optional[Tuple[int, int]] = None) -> torch.Tensor:
     """frames [start, end) -> uniform padding -> 4n+1 padding -> input transform: [3, T', H', W'] in [-1, 1].
     ``dtype``: cast the frames BEFORE padding / resizing, as phase 1 of the reference does (the batch goes to the
     compute dtype at generation_phases.py:377-385, so its resize result, clamp, pad and normalise are rounded to bf16
-    step by step); phase 4 re-transforms the input in its own dtype (generation_phases.py:127-168) -> ``None``."""
+    step by step); phase 4 re-transforms the input in its own dtype (generation_phases.py:127-168) -> ``None``.
+    ``size``: transforms.video_transform's (``upscale(target_size=...)``)."""
     video = images_thwc[plan.start:plan.end]
     if dtype is not None:
         video = video.to(dtype)
@@ -66,18 +67,22 @@ def prepare_batch(images_thwc: torch.Tensor, plan: BatchPlan, resolution: int, m
     video = video.permute(0, 3, 1, 2)                                    # T C H W
     if video.size(0) % 4 != 1:
         video = transforms.pad_video_temporal(video, temporal_dim=0, prepend=False)
-    return transforms.video_transform(video[:, :3], resolution, max_resolution)
+    return transforms.video_transform(video[:, :3], resolution, max_resolution, size=size)
 
 
-def transformed_shape(images_thwc: torch.Tensor, plan: BatchPlan, resolution: int, max_resolution: int = 0) -> Tuple[int, ...]:
+def transformed_shape(images_thwc: torch.Tensor, plan: BatchPlan, resolution: int, max_resolution: int = 0,
+                      size: Optional[Tuple[int, int]] = None) -> Tuple[int, ...]:
     """Shape of prepare_batch()'s result without computing it: [3, T', H', W']."""
     t = plan.end - plan.start + plan.uniform_pad
     if t % 4 != 1:
         t = ((t - 1) // 4 + 1) * 4 + 1
-    h, w = transforms.resized_output_size(images_thwc.shape[1], images_thwc.shape[2], resolution)
-    if max_resolution > 0 and max(h, w) > max_resolution:
-        scale = max_resolution / max(h, w)
-        h, w = round(h * scale), round(w * scale)
+    if size is not None:
+        h, w = transforms.check_size(size)
+    else:
+        h, w = transforms.resized_output_size(images_thwc.shape[1], images_thwc.shape[2], resolution)
+        if max_resolution > 0 and max(h, w) > max_resolution:
+            scale = max_resolution / max(h, w)
+            h, w = round(h * scale), round(w * scale)
     return (3, t, (h + 15) // 16 * 16, (w + 15) // 16 * 16)
 
 
@@ -98,7 +103,8 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
             progress: Optional[Callable[[str, int, int], None]] = None,
             noise_provider: Optional[Callable[[torch.Tensor], Tuple[torch.Tensor, torch.Tensor]]] = None,
             exchange_heads: Optional[Callable[[dict, list, tuple, torch.dtype], dict]] = None,
-            return_spans: bool = False, skip_trimmed_frames: bool = True, output_dtype: Optional[torch.dtype] = torch.float32):
+            return_spans: bool = False, skip_trimmed_frames: bool = True, output_dtype: Optional[torch.dtype] = torch.float32,
+            target_size: Optional[Tuple[int, int]] = None, area=None):
     """images [T, H, W, 3] in [0, 1] (any float dtype, on the runner's device) -> upscaled [T, H', W', 3] in [0, 1].
     [T, H, W, 4] (RGBA) -> [T, H', W', 4]: the RGB channels exactly as for the three-channel clip, the fourth the edge-guided
     upscaled alpha (alpha.py) of each owned span, computed from the span's decoded frames and the input alpha of the same clip
@@ -111,9 +117,42 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
     gathered clip of dist.upscale_sharded.  Memory / xGMI cost: 99.5 MB per 4K frame in fp32 against 49.8 MB in bf16 (a 128-frame
     4K clip: 12.7 GB per rank, 1.6 GB per rank on the wire at 8 ranks -- sized for 288 GB of HBM); ``output_dtype=None`` keeps the
     engines' activation dtype (bf16) as the reference's phase code does, for clips where that matters more than the 0.7 dB.
+
+    ``target_size=(h, w)`` (None: everything above, unchanged): two even positive integers.  The input transform resizes straight
+    to (h, w) with one antialiased bicubic -- no side rule, no ``max_resolution`` step; ``resolution`` and ``max_resolution`` are
+    unused --, clamp, pad-to-16 and normalise follow as ever, and the decoded frames are trimmed to (h, w).  Refused together with
+    ``batch_filter``, ``exchange_heads`` and ``return_spans``.
+
+    ``area`` (None: everything above, unchanged): the active picture area of a letterboxed or pillarboxed clip (active.py, DESIGN.md
+    7.3g), an explicit (y0, y1, x0, x1) in input pixels -- 0 <= y0 < y1 <= H, at least 16 rows, the columns likewise -- or an
+    active.Rule, which is given the profile of the frames this call receives (before ``prepend_frames``, which only mirrors them;
+    active.profile through the runner's backend: one launch and ONE read-back of H + W counts, the feature's only host
+    synchronisation).  An area that is the whole frame is this call without ``area``: the same bits.  Otherwise, with
+    (TH, TW) = transforms.true_target_dims and rect = active.out_rect(area, H, W, TH, TW):
+        canvas = clamp(transforms.side_resize(frames as [T, C, H, W] fp32, resolution, max_resolution), 0, 1)[..., :TH, :TW]
+                 as [T, TH, TW, C] in the output dtype, every channel, alpha too
+        canvas[:, oy0:oy1, ox0:ox1] = upscale(frames[:, y0:y1, x0:x1].contiguous(), ..., target_size=(oy1 - oy0, ox1 - ox0))
+    with every other keyword unchanged: outside the picture the result is the plain resize of what the source had there, inside
+    it the model's output for the picture alone.  Memory: one extra clip-sized buffer, the canvas, next to the crop's output
+    while it is copied in.  Refused together with ``batch_filter``, ``exchange_heads``, ``return_spans`` and ``target_size``.
     """
     if images_thwc.dim() != 4 or images_thwc.shape[-1] not in (3, 4):
         raise ValueError(f"images must be [T, H, W, 3] (RGB) or [T, H, W, 4] (RGBA), got {tuple(images_thwc.shape)}")
+    if area is not None:
+        for name, given in (("batch_filter", batch_filter), ("exchange_heads", exchange_heads), ("return_spans", return_spans),
+                            ("target_size", target_size)):
+            if given:
+                raise ValueError(f"upscale: {name} is not served with area (the picture is a clip of its own, on one GPU)")
+        kw = dict(resolution=resolution, max_resolution=max_resolution, batch_size=batch_size, uniform_batch_size=uniform_batch_size,
+                  temporal_overlap=temporal_overlap, prepend_frames=prepend_frames, color_correction=color_correction,
+                  input_noise_scale=input_noise_scale, latent_noise_scale=latent_noise_scale, seed=seed, progress=progress,
+                  noise_provider=noise_provider, skip_trimmed_frames=skip_trimmed_frames, output_dtype=output_dtype)
+        return _upscale_area(images_thwc, runner, text_pos, area, kw)
+    if target_size is not None:
+        target_size = transforms.check_size(target_size)
+        for name, given in (("batch_filter", batch_filter), ("exchange_heads", exchange_heads), ("return_spans", return_spans)):
+            if given:
+                raise ValueError(f"upscale: {name} is not served with target_size")
     # compute / storage dtype of the phases = the engines' activation dtype (bf16 on the HIP path, as the reference's
     # compute_dtype; fp32 when the CPU tests drive the engines with the fp32 torch double of the C ABI)
     dev, dt = runner.dit.device, getattr(getattr(runner.dit, "ops", None), "act_dtype", torch.bfloat16)
@@ -130,7 +169,8 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
         # (the RGB copy has the strides of a three-channel clip, so phases 1-3 and the colour fix compute the same bits)
         alpha_in, images = images[..., 3], images[..., :3].contiguous()
     total = images.shape[0]
-    true_h, true_w = transforms.true_target_dims(images.shape[1], images.shape[2], resolution, max_resolution)
+    true_h, true_w = (transforms.true_target_dims(images.shape[1], images.shape[2], resolution, max_resolution)
+                      if target_size is None else target_size)
     plans, overlap = plan_batches(total, batch_size, temporal_overlap, uniform_batch_size)
     mine = [i for i in range(len(plans)) if batch_filter is None or batch_filter(i)]
 
@@ -147,12 +187,12 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
     for i, plan in enumerate(plans):
         if i not in owned:
             if input_noise_scale > 0 and i < max(mine, default=-1):
-                c, t, h, w = transformed_shape(images, plan, resolution, max_resolution)
+                c, t, h, w = transformed_shape(images, plan, resolution, max_resolution, size=target_size)
                 # same shape AND strides as prepare_batch's result (a [T, C, H, W] buffer viewed c t h w): the CPU generator
                 # consumes its stream differently for contiguous and strided outputs
                 torch.randn_like(torch.empty((t, c, h, w), dtype=dt, device=dev).permute(1, 0, 2, 3))
             continue
-        x = prepare_batch(images, plan, resolution, max_resolution, dtype=dt)
+        x = prepare_batch(images, plan, resolution, max_resolution, dtype=dt, size=target_size)
         if input_noise_scale > 0:
             noise = torch.randn_like(x) * 0.05
             blend = input_noise_scale * 0.5
@@ -234,7 +274,7 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
             alpha_out[w0:w1] = alpha_mod.upscale_alpha(final[w0:w1], alpha_in[w0:w1], getattr(runner.dit, "ops", None)).to(odt)
         sample = final[w0:w1].permute(0, 3, 1, 2)
         if color_correction != "none":
-            ref = prepare_batch(images, plans[i], resolution, max_resolution).to(odt).permute(1, 0, 2, 3)   # T C H W
+            ref = prepare_batch(images, plans[i], resolution, max_resolution, size=target_size).to(odt).permute(1, 0, 2, 3)   # T C H W
             if i > 0 and overlap > 0:
                 ref = ref[overlap:]
             ref = ref[:sample.shape[0], :, :true_h, :true_w]
@@ -248,6 +288,38 @@ def upscale(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, resolu
         final = final[prepend_frames:]
         spans = {i: (max(a - prepend_frames, 0), max(b - prepend_frames, 0)) for i, (a, b) in spans.items()}
     return (final, spans) if return_spans else final
+
+
+def _upscale_area(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, area, kw: dict) -> torch.Tensor:
+    """``upscale(area=...)``: the statement in its docstring, line by line."""
+    T, H, W, _ = images_thwc.shape
+    if T == 0:
+        raise ValueError("No frames to process")
+    dev = runner.dit.device
+    if isinstance(area, active.Rule):
+        frames = images_thwc if images_thwc.dtype in (torch.float32, torch.bfloat16) else images_thwc.float()
+        counts = active.profile(frames.to(dev).contiguous(), area.dark, getattr(runner.dit, "ops", None)).tolist()   # the one read-back
+        area = area.area(counts, T, H, W)
+    else:
+        ok = isinstance(area, (tuple, list)) and len(area) == 4 and all(isinstance(v, int) and not isinstance(v, bool) for v in area)
+        if not ok:
+            raise ValueError(f"area must be an active.Rule or (y0, y1, x0, x1) in integers, got {area!r}")
+        y0, y1, x0, x1 = area
+        if not (0 <= y0 < y1 <= H and 0 <= x0 < x1 <= W) or y1 - y0 < active.MIN_SIDE or x1 - x0 < active.MIN_SIDE:
+            raise ValueError(f"area must satisfy 0 <= y0 < y1 <= H = {H}, 0 <= x0 < x1 <= W = {W} with at least "
+                             f"{active.MIN_SIDE} rows and columns, got {tuple(area)}")
+    y0, y1, x0, x1 = area
+    if (y0, y1, x0, x1) == (0, H, 0, W):
+        return upscale(images_thwc, runner, text_pos, **kw)
+    true_h, true_w = transforms.true_target_dims(H, W, kw["resolution"], kw["max_resolution"])
+    oy0, oy1, ox0, ox1 = active.out_rect((y0, y1, x0, x1), H, W, true_h, true_w)
+    odt = kw["output_dtype"] if kw["output_dtype"] is not None else getattr(getattr(runner.dit, "ops", None), "act_dtype", torch.bfloat16)
+    images = images_thwc.to(device=dev)
+    canvas = transforms.side_resize(images.permute(0, 3, 1, 2).float(), kw["resolution"], kw["max_resolution"])
+    canvas = canvas.clamp(0.0, 1.0)[..., :true_h, :true_w].permute(0, 2, 3, 1).to(odt).contiguous()
+    out = upscale(images[:, y0:y1, x0:x1].contiguous(), runner, text_pos, target_size=(oy1 - oy0, ox1 - ox0), **kw)
+    canvas[:, oy0:oy1, ox0:ox1] = out
+    return canvas
 
 
 def _signatures(frames: torch.Tensor, runner) -> torch.Tensor:
@@ -269,7 +341,9 @@ def upscale_shots(images_thwc: torch.Tensor, runner, text_pos: torch.Tensor, *, 
     start a shot (shots.split's rule), or a shots.Detector, which is fed the signatures of the clip (shots.signatures through the
     runner's backend: one launch and one read-back of T distances).  The result is, bit for bit, the concatenation of
     ``upscale(images[a:b], ...same keyword arguments...)`` over the shots [a, b): ``prepend_frames``, ``uniform_batch_size``, the
-    noise seeds and the overlap blend all apply per shot.  ``batch_filter``, ``exchange_heads`` and ``return_spans`` are refused."""
+    noise seeds and the overlap blend all apply per shot.  ``batch_filter``, ``exchange_heads`` and ``return_spans`` are refused.
+    ``area=`` is one of the forwarded keyword arguments, so it is served per shot without a line here: a Rule sees each shot's own
+    frames (aspect ratios change at cuts), a letterboxed shot is cropped and its neighbour is not."""
     _refuse_for_shots("upscale_shots", upscale_kwargs)
     if images_thwc.dim() != 4 or images_thwc.shape[-1] not in (3, 4) or images_thwc.shape[0] == 0:
         raise ValueError(f"images must be [T >= 1, H, W, 3] (RGB) or [T >= 1, H, W, 4] (RGBA), got {tuple(images_thwc.shape)}")
@@ -343,7 +417,11 @@ def upscale_stream(chunks, runner, text_pos: torch.Tensor, *, temporal_overlap: 
     instead, if the chunk's first frame is itself a cut.  Every later piece starts a shot: no context, and ``prepend_frames``.  No
     batch and no context then spans a cut; a clip without cuts streams to the same bits as with ``cuts=None``.  The memory
     statement holds: besides the raw tail the generator keeps the detector's state (one signature of 4 KB and at most ``window``
-    integers), and the pieces' outputs live only until they are concatenated into the chunk's."""
+    integers), and the pieces' outputs live only until they are concatenated into the chunk's.
+
+    ``area=`` is one of the forwarded keyword arguments, so it is served per (context + chunk) call, or per piece with ``cuts``,
+    without a line here: a Rule sees the frames of each call, context included, and neighbouring chunks may choose different
+    areas.  The memory statement holds with one more chunk-sized buffer, ``upscale``'s canvas."""
     if cuts is not None:
         yield from _upscale_stream_shots(chunks, runner, text_pos, cuts, temporal_overlap, prepend_frames, upscale_kwargs)
         return

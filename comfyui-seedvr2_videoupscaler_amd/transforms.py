@@ -66,9 +66,20 @@ def true_target_dims(h: int, w: int, resolution: int, max_resolution: int = 0) -
     return (th // 2) * 2, (tw // 2) * 2
 
 
-def video_transform(x_tchw: torch.Tensor, resolution: int, max_resolution: int = 0) -> torch.Tensor:
-    """[T, C, H, W] in [0, 1] -> [C, T, H', W'] in [-1, 1], H', W' multiples of 16."""
-    y = side_resize(x_tchw, resolution, max_resolution)
+def check_size(size) -> Tuple[int, int]:
+    """An explicit output size (h, w) of the input transform: two even positive integers, else a ValueError."""
+    ok = (isinstance(size, (tuple, list)) and len(size) == 2
+          and all(isinstance(v, int) and not isinstance(v, bool) and v > 0 and v % 2 == 0 for v in size))
+    if not ok:
+        raise ValueError(f"target_size must be (h, w), two even positive integers, got {size!r}")
+    return int(size[0]), int(size[1])
+
+
+def video_transform(x_tchw: torch.Tensor, resolution: int, max_resolution: int = 0, size=None) -> torch.Tensor:
+    """[T, C, H, W] in [0, 1] -> [C, T, H', W'] in [-1, 1], H', W' multiples of 16.  ``size=(h, w)``: one antialiased bicubic
+    straight to that size instead of the side rule and the ``max_resolution`` step (``resolution`` and ``max_resolution`` are then
+    unused); clamp, pad and normalise as ever."""
+    y = side_resize(x_tchw, resolution, max_resolution) if size is None else _bicubic(x_tchw, check_size(size))
     y = torch.clamp(y, 0.0, 1.0)
     y = divisible_pad(y, 16)
     y = (y - 0.5) / 0.5

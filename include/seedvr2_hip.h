@@ -64,6 +64,8 @@
  *   svr_hue_match                              planes 4 (dense [n]), workspace 16
  *   svr_frame_signatures                       element alignment is enough (frames 4 / 2 bytes for fp32 / bf16, sig 4); 16-byte loads
  *                                              where frames is 16-byte aligned, element accesses otherwise
+ *   svr_active_profile                         as svr_frame_signatures (frames 4 / 2 bytes, out 4; 16-byte loads where frames is
+ *                                              16-byte aligned, element accesses otherwise)
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -99,6 +101,8 @@ extern "C" {
  * longer than svr_png_encode()'s).  New symbols only; svr_png_encode and its bytes are untouched.
  * v9, additive: + svr_frame_signatures() (per frame a 4 x 4 grid of 64-bin luma histograms: what cut detection compares).  A new
  * symbol only.
+ * v9, additive: + svr_active_profile() (per row and per column the number of pixels brighter than a threshold: what finds the bars
+ * of a letterboxed clip).  A new symbol only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -432,6 +436,16 @@ int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H,
  * sig_bytes must be EXACTLY T * 4096.  No host synchronisation, no workspace. */
 int svr_frame_signatures(const void* frames, int32_t kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t* sig,
                          int64_t sig_bytes, void* stream);
+
+/* ---- active-area profile of a letterboxed clip -------------------------------------------------- */
+/* active.py (the specification, bit for bit): frames [T, H, W, C] dense, fp32 or bf16 (kind SVR_STORE_FP32 / SVR_STORE_BF16), C = 3 or
+ * 4 (a fourth channel is ignored), T, H, W >= 1, T * max(H, W) < 2^31, dark in 0..255 -> out int32 [H + W]: out[y] for y < H is the
+ * number of pixels (t, x) of row y, over all T frames, with Y8 > dark, out[H + x] the same for column x; Y8 as for
+ * svr_frame_signatures.  Both halves have the same sum.  The call itself zeroes out on `stream` (what the buffer held does not
+ * matter), then one launch adds the counts with integer atomics: two calls give the same bits.  Every argument is checked before
+ * anything is enqueued; out_bytes must be EXACTLY (H + W) * 4.  No host synchronisation, no workspace. */
+int svr_active_profile(const void* frames, int32_t kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t dark, int32_t* out,
+                       int64_t out_bytes, void* stream);
 
 /* ---- PNG streams encoded on the device ------------------------------------------------------- */
 /* pngenc.py (the specification, byte for byte): frames [T, H, W, C] dense, fp32 or bf16 (x_kind SVR_STORE_FP32 / SVR_STORE_BF16),

@@ -30,7 +30,11 @@ two parsers by ``ast``), so existing scripts keep working.  What the flags DO is
     16-bit RGB / RGBA png still, which load_frames reads with its 16 bits), as 8-bit files otherwise (DESIGN.md 7.3d);
   * shot-aware batching has no flag -- the flag set equals the reference's: where shots.ENABLED is set (it ships
     off) and one GPU does the work, hard cuts are found on the device (shots.py / csrc/svr_shots.hip) and no batch, and no
-    --chunk_size context, spans one (``pipeline.upscale_shots`` / ``upscale_stream(cuts=...)``).
+    --chunk_size context, spans one (``pipeline.upscale_shots`` / ``upscale_stream(cuts=...)``);
+  * the active picture area has no flag either: where active.ENABLED is set (it ships off) and one GPU does the
+    work, the black bars of a letterboxed or pillarboxed clip are found on the device (active.py / csrc/svr_active.hip), only the
+    picture goes through the model and the bars are a plain resize (``pipeline.upscale(area=...)``), per clip, per shot and per
+    --chunk_size chunk.
 """
 import argparse
 import json
@@ -87,6 +91,29 @@ def shot_detector(rank: int, world: int):
         _shots_warned = True
         return None
     return shots.Detector(**shots.DEFAULTS)
+
+
+def _active():
+    import importlib
+    return importlib.import_module(f"{PKG}.active")
+
+
+_active_warned = False
+
+
+def active_rule(rank: int, world: int) -> dict:
+    """{"area": active.Rule(**active.DEFAULTS)} where active.ENABLED is set and one rank does the work, else {}: with the switch off
+    (the shipped state) no call changes; with several ranks the crop is not served yet, which is said once on rank 0."""
+    global _active_warned
+    active = _active()
+    if not active.ENABLED:
+        return {}
+    if world > 1:
+        if rank == 0 and not _active_warned:
+            print(f"Warning: the active picture area serves one GPU; {world} ranks upscale the whole frame", file=sys.stderr)
+        _active_warned = True
+        return {}
+    return {"area": active.Rule(**active.DEFAULTS)}
 
 
 def output_depth(inp: str, info: Optional[dict] = None) -> int:
@@ -891,6 +918,7 @@ def run(args, frames, eng=None, **override):
     kw = {**kw, **override}
     t0 = time.time()
     detector = shot_detector(rank, world)              # (None unless shots.ENABLED: no batch across a cut)
+    kw = {**kw, **active_rule(rank, world)}            # ({} unless active.ENABLED: only the picture is upscaled)
     if world > 1:                                      # only rank 0 writes the result: gather the frames there, not everywhere
         out = dist_mod.upscale_sharded(frames.to(runner.dit.device), runner, text, gather="root", **kw)
     elif detector is not None:
@@ -916,6 +944,7 @@ def run_stream(args, chunks, eng=None):
     eng = eng if eng is not None else engines(args)
     runner, text, kw, rank, world = eng
     detector = shot_detector(rank, world)              # one detector down the whole stream; None unless shots.ENABLED
+    kw = {**kw, **active_rule(rank, world)}            # ({} unless active.ENABLED)
     if world == 1:
         yield from pipeline.upscale_stream((c.to(runner.dit.device) for c in chunks), runner, text, cuts=detector, **kw)
         return
