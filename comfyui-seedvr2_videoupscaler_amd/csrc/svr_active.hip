@@ -22,9 +22,7 @@ constexpr int ACT_BAND_ROWS = 32;                    // 32 x 1280 pixels = 160 p
 constexpr int ACT_UNIT = 8;                          // pixels per lane and step on the 16-byte route
 constexpr int ACT_LDS_COLS = 4096;                   // columns with an LDS counter (16 KB): every source up to 4096 wide
 
-SVR_DEVICE bool active_lit(float r, float g, float b, uint32_t dark) {
-    return ((13933u * pack_code(r, 255.f) + 46871u * pack_code(g, 255.f) + 4732u * pack_code(b, 255.f) + 32768u) >> 16) > dark;
-}
+SVR_DEVICE bool active_lit(float r, float g, float b, uint32_t dark) { return luma8(r, g, b) > dark; }
 
 // one count for column x (x < W)
 SVR_DEVICE void active_count_col(int* cols, int* __restrict__ out_cols, int x) {

@@ -389,6 +389,58 @@ int svr_affine_slice(const void* in, void* out, int64_t rows, int32_t c_in, int3
     return check(hipGetLastError(), "svr_affine_slice");
 }
 
+}  // extern "C"
+
+// ---- what the entry points below share: one way to refuse a call, one step from a run-time code to a template constant, one
+// capped grid.  An entry point states its name once, in its Entry.
+#include <cstdarg>
+#include <type_traits>
+
+struct Entry {
+    const char* fn;
+    // "<fn>: <message>" left in g_err -> -1
+    __attribute__((format(printf, 2, 3))) int refuse(const char* fmt, ...) const {
+        char msg[sizeof(g_err)];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(msg, sizeof(msg), fmt, ap);
+        va_end(ap);
+        snprintf(g_err, sizeof(g_err), "%s: %s", fn, msg);
+        return -1;
+    }
+    // a byte count that has to be exact: "<arg> is N, <words> exactly M"
+    int wrong_size(const char* arg, int64_t is, const char* words, int64_t exactly) const {
+        return refuse("%s is %lld, %s exactly %lld", arg, (long long)is, words, (long long)exactly);
+    }
+    // a HIP call's status: 0, or the status with "<fn>[: <doing>]: <HIP's words>" left in g_err
+    int hip(int status, const char* doing = "") const {
+        if (status) refuse("%s%s%s", doing, *doing ? ": " : "", hipGetErrorString((hipError_t)status));
+        return status;
+    }
+    int launched() const { return hip(hipGetLastError()); }
+};
+// an entry point that launches: on its stream's device until it returns
+struct Launch : Entry {
+    StreamDeviceGuard on_stream_device;
+    Launch(const char* fn, void* stream) : Entry{fn}, on_stream_device(stream) {}
+};
+
+// f(std::integral_constant<int, V>{}) for the V of the list that equals v -> whether there was one.  Every caller has checked v.
+// At run time the order of a list means nothing; the compiler, though, emits the kernels one call instantiates last value first,
+// and the lists below are written so that the code object keeps the order of its kernels.
+template <int... Vs, class F>
+static bool with_const(int v, F&& f) {
+    return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...);
+}
+template <class F>
+static bool with_kind(int kind, F&& f) { return with_const<SVR_STORE_BF16, SVR_STORE_FP32>(kind, f); }
+
+// one workgroup of 256 per 256 items of work, at most eight per CU (the kernels stride over the rest).  Capped in 64 bits: under the
+// 2^40-pixel limit the block count of the element-wise routes does not fit 32
+static unsigned capped_grid(int64_t work) { return (unsigned)std::min<int64_t>((work + 255) / 256, (int64_t)device_cu_count() * 8); }
+
+extern "C" {
+
 // ---- edge-guided alpha upscaling (svr_alpha.hip).  Workspace: [flags 4 | maxima T, padded to 4 | n map T*H*W] int32.
 static inline int64_t alpha_header_ints(int32_t T) { return 4 + ((int64_t)T + 3) / 4 * 4; }
 
@@ -406,63 +458,57 @@ static const char* alpha_args_error(const void* rgb, int32_t T, int32_t H, int32
     if (workspace_bytes < svr_alpha_workspace_bytes(T, H, W)) return "workspace shorter than svr_alpha_workspace_bytes()";
     return nullptr;
 }
-#define SVR_ALPHA_REFUSE(name, why) do { snprintf(g_err, sizeof(g_err), "%s: %s", name, why); return -1; } while (0)
 
 int svr_alpha_stats(const float* alpha_lo, int64_t n_alpha, const void* rgb, int32_t T, int32_t H, int32_t W, int64_t ld_px,
                     int32_t rgb_kind, void* workspace, int64_t workspace_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_alpha_stats", stream};
     const char* why = alpha_args_error(rgb, T, H, W, ld_px, rgb_kind, workspace, workspace_bytes);
     if (!why && !alpha_lo) why = "null pointer";
     if (!why && (n_alpha < 1 || n_alpha > 0x7fffffff)) why = "need 1 <= n_alpha < 2^31 (the counts are int32)";
-    if (why) SVR_ALPHA_REFUSE("svr_alpha_stats", why);
+    if (why) return e.refuse("%s", why);
     int* flags = (int*)workspace;
-    if (int rc = check(hipMemsetAsync(flags, 0, (size_t)alpha_header_ints(T) * 4, (hipStream_t)stream), "svr_alpha_stats")) return rc;
+    if (int rc = e.hip(hipMemsetAsync(flags, 0, (size_t)alpha_header_ints(T) * 4, (hipStream_t)stream))) return rc;
     const int64_t n_px = (int64_t)T * H * W;
     const unsigned grid = std::min<unsigned>(blocks_for(std::max(n_px, n_alpha), 256 * 8), (unsigned)device_cu_count() * 8);
-    if (rgb_kind == SVR_STORE_FP32) hipLaunchKernelGGL(alpha_stats_kernel<SVR_STORE_FP32>, dim3(grid), dim3(256), 0, (hipStream_t)stream, alpha_lo, n_alpha, rgb, n_px, ld_px, flags);
-    else hipLaunchKernelGGL(alpha_stats_kernel<SVR_STORE_BF16>, dim3(grid), dim3(256), 0, (hipStream_t)stream, alpha_lo, n_alpha, rgb, n_px, ld_px, flags);
-    return check(hipGetLastError(), "svr_alpha_stats");
+    with_kind(rgb_kind, [&](auto K) { hipLaunchKernelGGL(alpha_stats_kernel<K()>, dim3(grid), dim3(256), 0, (hipStream_t)stream, alpha_lo, n_alpha, rgb, n_px, ld_px, flags); });
+    return e.launched();
 }
 
 int svr_alpha_edges(const void* rgb, int32_t T, int32_t H, int32_t W, int64_t ld_px, int32_t rgb_kind, void* workspace,
                     int64_t workspace_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
-    const char* why = alpha_args_error(rgb, T, H, W, ld_px, rgb_kind, workspace, workspace_bytes);
-    if (why) SVR_ALPHA_REFUSE("svr_alpha_edges", why);
+    const Launch e{"svr_alpha_edges", stream};
+    if (const char* why = alpha_args_error(rgb, T, H, W, ld_px, rgb_kind, workspace, workspace_bytes)) return e.refuse("%s", why);
     int* flags = (int*)workspace;
     int* maxima = flags + 4;
     int* nmap = flags + alpha_header_ints(T);
     const dim3 grid(blocks_for(W, ALPHA_TILE), blocks_for(H, ALPHA_TILE), T);
-    if (grid.y > 65535u) SVR_ALPHA_REFUSE("svr_alpha_edges", "H beyond 65535 tiles");
-    if (rgb_kind == SVR_STORE_FP32) hipLaunchKernelGGL(alpha_edges_kernel<SVR_STORE_FP32>, grid, dim3(256), 0, (hipStream_t)stream, rgb, ld_px, H, W, flags, nmap, maxima);
-    else hipLaunchKernelGGL(alpha_edges_kernel<SVR_STORE_BF16>, grid, dim3(256), 0, (hipStream_t)stream, rgb, ld_px, H, W, flags, nmap, maxima);
-    return check(hipGetLastError(), "svr_alpha_edges");
+    if (grid.y > 65535u) return e.refuse("H beyond 65535 tiles");
+    with_kind(rgb_kind, [&](auto K) { hipLaunchKernelGGL(alpha_edges_kernel<K()>, grid, dim3(256), 0, (hipStream_t)stream, rgb, ld_px, H, W, flags, nmap, maxima); });
+    return e.launched();
 }
 
 int svr_alpha_refine(const void* rgb, const float* base, float* out, uint8_t* edge_out, int32_t T, int32_t H, int32_t W,
                      int64_t ld_px, int32_t rgb_kind, int64_t n_alpha, const void* workspace, int64_t workspace_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_alpha_refine", stream};
     const char* why = alpha_args_error(rgb, T, H, W, ld_px, rgb_kind, workspace, workspace_bytes);
     if (!why && (!base || !out)) why = "null pointer";
     if (!why && (n_alpha < 1 || n_alpha > 0x7fffffff)) why = "need 1 <= n_alpha < 2^31 (the counts are int32)";
-    if (why) SVR_ALPHA_REFUSE("svr_alpha_refine", why);
+    if (why) return e.refuse("%s", why);
     const int* flags = (const int*)workspace;
     const int* maxima = flags + 4;
     const int* nmap = flags + alpha_header_ints(T);
     const dim3 grid(blocks_for(W, ALPHA_TILE), blocks_for(H, ALPHA_TILE), T);
-    if (grid.y > 65535u) SVR_ALPHA_REFUSE("svr_alpha_refine", "H beyond 65535 tiles");
-    if (rgb_kind == SVR_STORE_FP32) hipLaunchKernelGGL(alpha_refine_kernel<SVR_STORE_FP32>, grid, dim3(256), 0, (hipStream_t)stream, rgb, ld_px, base, H, W, (float)n_alpha, flags, nmap, maxima, out, edge_out);
-    else hipLaunchKernelGGL(alpha_refine_kernel<SVR_STORE_BF16>, grid, dim3(256), 0, (hipStream_t)stream, rgb, ld_px, base, H, W, (float)n_alpha, flags, nmap, maxima, out, edge_out);
-    return check(hipGetLastError(), "svr_alpha_refine");
+    if (grid.y > 65535u) return e.refuse("H beyond 65535 tiles");
+    with_kind(rgb_kind, [&](auto K) { hipLaunchKernelGGL(alpha_refine_kernel<K()>, grid, dim3(256), 0, (hipStream_t)stream, rgb, ld_px, base, H, W, (float)n_alpha, flags, nmap, maxima, out, edge_out); });
+    return e.launched();
 }
-#undef SVR_ALPHA_REFUSE
 
 // ---- packed output frames (svr_frame_pack.hip: rgb8 / bgr8; svr_frame_pack_colour.hip: yuv420p10, whichever entry point asks)
-// The refusals svr_pack_frames and svr_pack_yuv420p10 share, in the order both report them -> the message, left in g_err behind
-// ``fn``, or nullptr.  ``own``: the caller's refusal of its own format / colour codes (nullptr: none), which ranks between the
-// geometry and the alignment.  ``C8``: bytes per pixel of an 8-bit format, 0 for yuv420p10 planes.  ``needs``: the caller's words.
-static const char* pack_refusal(const char* fn, const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C8,
-                                const char* own, const void* out, int64_t out_bytes, const char* needs) {
+// The refusals svr_pack_frames and svr_pack_yuv420p10 share, in the order both report them -> 0, or -1 with the message in g_err.
+// ``own``: the caller's refusal of its own format / colour codes (nullptr: none), which ranks between the geometry and the
+// alignment.  ``C8``: bytes per pixel of an 8-bit format, 0 for yuv420p10 planes.  ``needs``: the caller's words.
+static int pack_refusal(const Entry& e, const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C8,
+                        const char* own, const void* out, int64_t out_bytes, const char* needs) {
     const char* why = nullptr;
     if (!frames) why = "frames is a null pointer";
     else if (!out) why = "out is a null pointer";
@@ -472,16 +518,11 @@ static const char* pack_refusal(const char* fn, const void* frames, int32_t x_ki
     else if (own) why = own;
     else if ((uintptr_t)frames % (x_kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
     else if (!C8 && (uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
-    if (why) { snprintf(g_err, sizeof(g_err), "%s: %s", fn, why); return g_err; }
+    if (why) return e.refuse("%s", why);
     const int64_t h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
     const int64_t need = C8 ? (int64_t)T * H * W * C8 : 2 * (int64_t)T * ((int64_t)H * W + 2 * h2 * w2);
-    if (out_bytes == need) return nullptr;
-    snprintf(g_err, sizeof(g_err), "%s: out_bytes is %lld, the %s exactly %lld", fn, (long long)out_bytes, needs, (long long)need);
-    return g_err;
+    return out_bytes == need ? 0 : e.wrong_size("out_bytes", out_bytes, needs, need);
 }
-
-// capped in 64 bits: under the 2^40-pixel limit the block count of the element-wise routes does not fit 32
-static unsigned pack_grid(int64_t work) { return (unsigned)std::min<int64_t>((work + 255) / 256, (int64_t)device_cu_count() * 8); }
 
 // Kr, Kb exact decimals, every weight rounded at 2^16, luma deficit to green (frameio.yuv_matrix): wr, wg, wb | cb_r, cb_g | cr_g, cr_b
 static PackCoef pack_coef(int32_t matrix, int32_t range) {
@@ -497,60 +538,57 @@ static void launch_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T,
                                   unsigned short* o, hipStream_t s) {
     const bool vec = (uintptr_t)frames % 16 == 0 && (uintptr_t)o % 16 == 0 && W % 16 == 0;
     const int64_t h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
-    const unsigned grid = pack_grid((int64_t)T * h2 * (vec ? W / 16 : w2));
-#define SVR_PACK_COLOUR(KIND, LEFT) \
-    if (vec) hipLaunchKernelGGL((pack_colour_vec_kernel<KIND, LEFT>), dim3(grid), dim3(256), 0, s, frames, o, T, H, W, k); \
-    else hipLaunchKernelGGL((pack_colour_kernel<KIND, LEFT>), dim3(grid), dim3(256), 0, s, frames, o, T, H, W, k)
-    if (x_kind == SVR_STORE_FP32) { if (left) { SVR_PACK_COLOUR(SVR_STORE_FP32, true); } else { SVR_PACK_COLOUR(SVR_STORE_FP32, false); } }
-    else { if (left) { SVR_PACK_COLOUR(SVR_STORE_BF16, true); } else { SVR_PACK_COLOUR(SVR_STORE_BF16, false); } }
-#undef SVR_PACK_COLOUR
+    const unsigned grid = capped_grid((int64_t)T * h2 * (vec ? W / 16 : w2));
+    with_kind(x_kind, [&](auto K) { with_const<0, 1>(left, [&](auto LEFT) {
+        if (vec) hipLaunchKernelGGL((pack_colour_vec_kernel<K(), LEFT() != 0>), dim3(grid), dim3(256), 0, s, frames, o, T, H, W, k);
+        else hipLaunchKernelGGL((pack_colour_kernel<K(), LEFT() != 0>), dim3(grid), dim3(256), 0, s, frames, o, T, H, W, k);
+    }); });
 }
 
 int svr_pack_frames(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t fmt, void* out,
                     int64_t out_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_pack_frames", stream};
     const bool yuv = fmt == SVR_PACK_YUV420P10;
     const char* own = nullptr;
     if (fmt != SVR_PACK_RGB8 && fmt != SVR_PACK_BGR8 && !yuv) own = "fmt must be SVR_PACK_RGB8, SVR_PACK_BGR8 or SVR_PACK_YUV420P10";
     else if (yuv ? C != 3 : (C != 3 && C != 4)) own = yuv ? "C must be 3 for SVR_PACK_YUV420P10" : "C must be 3 or 4";
-    if (pack_refusal("svr_pack_frames", frames, x_kind, T, H, W, yuv ? 0 : C, own, out, out_bytes, "format needs")) return -1;
+    if (pack_refusal(e, frames, x_kind, T, H, W, yuv ? 0 : C, own, out, out_bytes, "the format needs")) return -1;
     const hipStream_t s = (hipStream_t)stream;
     if (yuv) {                                                     // BT.709, limited range, centre-sited chroma
         launch_pack_yuv420p10(frames, x_kind, T, H, W, pack_coef(SVR_COLOUR_MATRIX_BT709, SVR_COLOUR_RANGE_TV), false, (unsigned short*)out, s);
-        return check(hipGetLastError(), "svr_pack_frames");
+        return e.launched();
     }
     const int64_t n = (int64_t)T * H * W * C;
     const int swap = fmt == SVR_PACK_BGR8 ? C : 0;                 // pack8_kernel's C: 0 = samples in place
     const int unit = swap == 3 ? 48 : 16;
     const int64_t n_units = (uintptr_t)frames % 16 == 0 && (uintptr_t)out % 16 == 0 ? n / unit : 0;
-    const unsigned grid = pack_grid(std::max<int64_t>(n_units, n - n_units * unit));
+    const unsigned grid = capped_grid(std::max<int64_t>(n_units, n - n_units * unit));
     unsigned char* o = (unsigned char*)out;
-#define SVR_PACK8(KIND, CH) hipLaunchKernelGGL((pack8_kernel<KIND, CH>), dim3(grid), dim3(256), 0, s, frames, o, n_units, n)
-    if (x_kind == SVR_STORE_FP32) { if (swap == 0) SVR_PACK8(SVR_STORE_FP32, 0); else if (swap == 3) SVR_PACK8(SVR_STORE_FP32, 3); else SVR_PACK8(SVR_STORE_FP32, 4); }
-    else { if (swap == 0) SVR_PACK8(SVR_STORE_BF16, 0); else if (swap == 3) SVR_PACK8(SVR_STORE_BF16, 3); else SVR_PACK8(SVR_STORE_BF16, 4); }
-#undef SVR_PACK8
-    return check(hipGetLastError(), "svr_pack_frames");
+    with_kind(x_kind, [&](auto K) { with_const<4, 3, 0>(swap, [&](auto CH) {
+        hipLaunchKernelGGL((pack8_kernel<K(), CH()>), dim3(grid), dim3(256), 0, s, frames, o, n_units, n);
+    }); });
+    return e.launched();
 }
 
 // ---- yuv420p10 planes with a chosen matrix, range and chroma siting
 int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t matrix, int32_t range,
                        int32_t siting, void* out, int64_t out_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_pack_yuv420p10", stream};
     const char* own = nullptr;
     if (matrix != SVR_COLOUR_MATRIX_BT709 && matrix != SVR_COLOUR_MATRIX_BT601 && matrix != SVR_COLOUR_MATRIX_BT2020)
         own = "matrix must be SVR_COLOUR_MATRIX_BT709, SVR_COLOUR_MATRIX_BT601 or SVR_COLOUR_MATRIX_BT2020";
     else if (range != SVR_COLOUR_RANGE_TV && range != SVR_COLOUR_RANGE_PC) own = "range must be SVR_COLOUR_RANGE_TV or SVR_COLOUR_RANGE_PC";
     else if (siting != SVR_COLOUR_SITING_CENTER && siting != SVR_COLOUR_SITING_LEFT) own = "siting must be SVR_COLOUR_SITING_CENTER or SVR_COLOUR_SITING_LEFT";
-    if (pack_refusal("svr_pack_yuv420p10", frames, x_kind, T, H, W, 0, own, out, out_bytes, "planes need")) return -1;
+    if (pack_refusal(e, frames, x_kind, T, H, W, 0, own, out, out_bytes, "the planes need")) return -1;
     launch_pack_yuv420p10(frames, x_kind, T, H, W, pack_coef(matrix, range), siting == SVR_COLOUR_SITING_LEFT, (unsigned short*)out,
                           (hipStream_t)stream);
-    return check(hipGetLastError(), "svr_pack_yuv420p10");
+    return e.launched();
 }
 
 // ---- frame signatures for cut detection (svr_shots.hip)
 int svr_frame_signatures(const void* frames, int32_t kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t* sig,
                          int64_t sig_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_frame_signatures", stream};
     const char* why = nullptr;
     if (!frames) why = "frames is a null pointer";
     else if (!sig) why = "sig is a null pointer";
@@ -562,29 +600,24 @@ int svr_frame_signatures(const void* frames, int32_t kind, int32_t T, int32_t H,
     else if ((int64_t)H * W >= ((int64_t)1 << 31)) why = "H * W must stay below 2^31 pixels (the counters are int32)";
     else if ((uintptr_t)frames % (kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
     else if ((uintptr_t)sig % 4) why = "sig is not aligned to 4 bytes";
-    if (why) { snprintf(g_err, sizeof(g_err), "svr_frame_signatures: %s", why); return -1; }
-    if (sig_bytes != (int64_t)T * 4096) {
-        snprintf(g_err, sizeof(g_err), "svr_frame_signatures: sig_bytes is %lld, int32 [T, 1024] is exactly %lld", (long long)sig_bytes,
-                 (long long)T * 4096);
-        return -1;
-    }
+    if (why) return e.refuse("%s", why);
+    if (sig_bytes != (int64_t)T * 4096) return e.wrong_size("sig_bytes", sig_bytes, "int32 [T, 1024] is", (int64_t)T * 4096);
     const int bands = (int)((((int64_t)H + 3) / 4 + SIG_BAND_ROWS - 1) / SIG_BAND_ROWS);      // of the tallest cell row
     const int64_t grid = (int64_t)T * 4 * bands;
-    if (grid > 0x7fffffffll) return fail("svr_frame_signatures: T * H needs more than 2^31 - 1 workgroups");
+    if (grid > 0x7fffffffll) return e.refuse("T * H needs more than 2^31 - 1 workgroups");
     const hipStream_t s = (hipStream_t)stream;
-    if (int rc = check(hipMemsetAsync(sig, 0, (size_t)sig_bytes, s), "svr_frame_signatures")) return rc;
+    if (int rc = e.hip(hipMemsetAsync(sig, 0, (size_t)sig_bytes, s))) return rc;
     const int vec = (uintptr_t)frames % 16 == 0;
-#define SVR_SIG(KIND, CH) hipLaunchKernelGGL((signature_kernel<KIND, CH>), dim3((unsigned)grid), dim3(256), 0, s, frames, (int*)sig, H, W, bands, vec)
-    if (kind == SVR_STORE_FP32) { if (C == 3) SVR_SIG(SVR_STORE_FP32, 3); else SVR_SIG(SVR_STORE_FP32, 4); }
-    else { if (C == 3) SVR_SIG(SVR_STORE_BF16, 3); else SVR_SIG(SVR_STORE_BF16, 4); }
-#undef SVR_SIG
-    return check(hipGetLastError(), "svr_frame_signatures");
+    with_kind(kind, [&](auto K) { with_const<4, 3>(C, [&](auto CH) {
+        hipLaunchKernelGGL((signature_kernel<K(), CH()>), dim3((unsigned)grid), dim3(256), 0, s, frames, (int*)sig, H, W, bands, vec);
+    }); });
+    return e.launched();
 }
 
 // ---- active-area profile of a letterboxed clip (svr_active.hip)
 int svr_active_profile(const void* frames, int32_t kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t dark, int32_t* out,
                        int64_t out_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_active_profile", stream};
     const char* why = nullptr;
     if (!frames) why = "frames is a null pointer";
     else if (!out) why = "out is a null pointer";
@@ -597,22 +630,17 @@ int svr_active_profile(const void* frames, int32_t kind, int32_t T, int32_t H, i
     else if ((int64_t)T * (H > W ? H : W) >= ((int64_t)1 << 31)) why = "T * max(H, W) must stay below 2^31 (the counters are int32)";
     else if ((uintptr_t)frames % (kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
     else if ((uintptr_t)out % 4) why = "out is not aligned to 4 bytes";
-    if (why) { snprintf(g_err, sizeof(g_err), "svr_active_profile: %s", why); return -1; }
-    if (out_bytes != ((int64_t)H + W) * 4) {
-        snprintf(g_err, sizeof(g_err), "svr_active_profile: out_bytes is %lld, int32 [H + W] is exactly %lld", (long long)out_bytes,
-                 (long long)(((int64_t)H + W) * 4));
-        return -1;
-    }
+    if (why) return e.refuse("%s", why);
+    if (out_bytes != ((int64_t)H + W) * 4) return e.wrong_size("out_bytes", out_bytes, "int32 [H + W] is", ((int64_t)H + W) * 4);
     const int bands = (int)(((int64_t)H + ACT_BAND_ROWS - 1) / ACT_BAND_ROWS);
     const int64_t grid = (int64_t)T * bands;                                                  // <= T * H < 2^31
     const hipStream_t s = (hipStream_t)stream;
-    if (int rc = check(hipMemsetAsync(out, 0, (size_t)out_bytes, s), "svr_active_profile")) return rc;
+    if (int rc = e.hip(hipMemsetAsync(out, 0, (size_t)out_bytes, s))) return rc;
     const int vec = (uintptr_t)frames % 16 == 0;
-#define SVR_ACT(KIND, CH) hipLaunchKernelGGL((active_profile_kernel<KIND, CH>), dim3((unsigned)grid), dim3(256), 0, s, frames, (int*)out, H, W, bands, (uint32_t)dark, vec)
-    if (kind == SVR_STORE_FP32) { if (C == 3) SVR_ACT(SVR_STORE_FP32, 3); else SVR_ACT(SVR_STORE_FP32, 4); }
-    else { if (C == 3) SVR_ACT(SVR_STORE_BF16, 3); else SVR_ACT(SVR_STORE_BF16, 4); }
-#undef SVR_ACT
-    return check(hipGetLastError(), "svr_active_profile");
+    with_kind(kind, [&](auto K) { with_const<4, 3>(C, [&](auto CH) {
+        hipLaunchKernelGGL((active_profile_kernel<K(), CH()>), dim3((unsigned)grid), dim3(256), 0, s, frames, (int*)out, H, W, bands, (uint32_t)dark, vec);
+    }); });
+    return e.launched();
 }
 
 // ---- PNG streams encoded on the device (svr_png.hip)
@@ -626,19 +654,17 @@ static const char* png_geometry_refusal(int32_t T, int32_t H, int32_t W, int32_t
     return nullptr;
 }
 
-static int png_encode_bytes(const char* who, bool runs, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes,
+static int png_encode_bytes(const Entry& e, bool runs, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes,
                             int64_t* capacity) {
-    const char* why = png_geometry_refusal(T, H, W, C, depth);
-    if (why) { snprintf(g_err, sizeof(g_err), "%s: %s", who, why); return -1; }
+    if (const char* why = png_geometry_refusal(T, H, W, C, depth)) return e.refuse("%s", why);
     const PngLayout L = png_layout(T, H, W, C, depth, runs);
     if (scratch_bytes) *scratch_bytes = L.scratch_bytes;
     if (capacity) *capacity = L.capacity;
     return 0;
 }
 
-static int png_encode(const char* who, bool runs, const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C,
+static int png_encode(const Entry& e, bool runs, const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C,
                       int32_t depth, void* scratch, int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
     const char* why = nullptr;
     if (!frames) why = "frames is a null pointer";
     else if (!scratch) why = "scratch is a null pointer";
@@ -649,16 +675,12 @@ static int png_encode(const char* who, bool runs, const void* frames, int32_t x_
     else if ((uintptr_t)frames % (x_kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
     else if ((uintptr_t)scratch % 16) why = "scratch is not aligned to 16 bytes";
     else if ((uintptr_t)sizes % 8) why = "sizes is not aligned to 8 bytes";
-    if (why) { snprintf(g_err, sizeof(g_err), "%s: %s", who, why); return -1; }
+    if (why) return e.refuse("%s", why);
     const PngLayout L = png_layout(T, H, W, C, depth, runs);
-    if (scratch_bytes < L.scratch_bytes) {
-        snprintf(g_err, sizeof(g_err), "%s: scratch_bytes is %lld, the geometry needs at least %lld", who, (long long)scratch_bytes, (long long)L.scratch_bytes);
-        return -1;
-    }
-    if (out_capacity < L.capacity) {
-        snprintf(g_err, sizeof(g_err), "%s: out_capacity is %lld per frame, the geometry needs at least %lld", who, (long long)out_capacity, (long long)L.capacity);
-        return -1;
-    }
+    if (scratch_bytes < L.scratch_bytes)
+        return e.refuse("scratch_bytes is %lld, the geometry needs at least %lld", (long long)scratch_bytes, (long long)L.scratch_bytes);
+    if (out_capacity < L.capacity)
+        return e.refuse("out_capacity is %lld per frame, the geometry needs at least %lld", (long long)out_capacity, (long long)L.capacity);
     const hipStream_t s = (hipStream_t)stream;
     unsigned char* base = (unsigned char*)scratch;
     unsigned char* filt = base + L.filt_off;
@@ -667,13 +689,9 @@ static int png_encode(const char* who, bool runs, const void* frames, int32_t x_
     int64_t* segoff = (int64_t*)(base + L.segoff_off);
     uint32_t* table2 = (uint32_t*)(base + L.table2_off);         // (inside the scratch with runs only, and only then used)
     const dim3 grid((unsigned)((int64_t)T * L.nseg)), block(256);
-#define SVR_PNG_FILTER(KIND, DEPTH, CH) hipLaunchKernelGGL((png_filter_kernel<KIND, DEPTH, CH>), grid, block, 0, s, frames, filt, table, meta, H, W, L.R, L.nseg)
-#define SVR_PNG_FILTER_KIND(KIND) \
-    if (depth == 8) { if (C == 3) SVR_PNG_FILTER(KIND, 8, 3); else SVR_PNG_FILTER(KIND, 8, 4); } \
-    else { if (C == 3) SVR_PNG_FILTER(KIND, 16, 3); else SVR_PNG_FILTER(KIND, 16, 4); }
-    if (x_kind == SVR_STORE_FP32) { SVR_PNG_FILTER_KIND(SVR_STORE_FP32) } else { SVR_PNG_FILTER_KIND(SVR_STORE_BF16) }
-#undef SVR_PNG_FILTER_KIND
-#undef SVR_PNG_FILTER
+    with_kind(x_kind, [&](auto K) { with_const<16, 8>(depth, [&](auto DEPTH) { with_const<4, 3>(C, [&](auto CH) {
+        hipLaunchKernelGGL((png_filter_kernel<K(), DEPTH(), CH()>), grid, block, 0, s, frames, filt, table, meta, H, W, L.R, L.nseg);
+    }); }); });
     // (g_png_passes < 3, tools/png_encode_timing.py only: the launches up to that pass, to time them by difference; with runs the
     // token + second code pass counts with the scan, so that the first figure is the same work in both modes)
     if (runs && g_png_passes >= 2) hipLaunchKernelGGL(png_runs_kernel, grid, block, 0, s, filt, table2, meta, H, L.stride, L.R, L.nseg);
@@ -682,25 +700,25 @@ static int png_encode(const char* who, bool runs, const void* frames, int32_t x_
         if (runs) hipLaunchKernelGGL(png_pack_kernel<true>, grid, block, 0, s, filt, table, table2, meta, segoff, (unsigned char*)out, out_capacity, H, L.stride, L.R, L.nseg);
         else hipLaunchKernelGGL(png_pack_kernel<false>, grid, block, 0, s, filt, table, table2, meta, segoff, (unsigned char*)out, out_capacity, H, L.stride, L.R, L.nseg);
     }
-    return check(hipGetLastError(), who);
+    return e.launched();
 }
 
 int svr_png_encode_bytes(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes, int64_t* capacity) {
-    return png_encode_bytes("svr_png_encode_bytes", false, T, H, W, C, depth, scratch_bytes, capacity);
+    return png_encode_bytes(Entry{"svr_png_encode_bytes"}, false, T, H, W, C, depth, scratch_bytes, capacity);
 }
 
 int svr_png_encode(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, void* scratch,
                    int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream) {
-    return png_encode("svr_png_encode", false, frames, x_kind, T, H, W, C, depth, scratch, scratch_bytes, out, out_capacity, sizes, stream);
+    return png_encode(Launch{"svr_png_encode", stream}, false, frames, x_kind, T, H, W, C, depth, scratch, scratch_bytes, out, out_capacity, sizes, stream);
 }
 
 int svr_png_encode_runs_bytes(int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, int64_t* scratch_bytes, int64_t* capacity) {
-    return png_encode_bytes("svr_png_encode_runs_bytes", true, T, H, W, C, depth, scratch_bytes, capacity);
+    return png_encode_bytes(Entry{"svr_png_encode_runs_bytes"}, true, T, H, W, C, depth, scratch_bytes, capacity);
 }
 
 int svr_png_encode_runs(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C, int32_t depth, void* scratch,
                         int64_t scratch_bytes, void* out, int64_t out_capacity, int64_t* sizes, void* stream) {
-    return png_encode("svr_png_encode_runs", true, frames, x_kind, T, H, W, C, depth, scratch, scratch_bytes, out, out_capacity, sizes, stream);
+    return png_encode(Launch{"svr_png_encode_runs", stream}, true, frames, x_kind, T, H, W, C, depth, scratch, scratch_bytes, out, out_capacity, sizes, stream);
 }
 
 // ---- colour correction (svr_colorfix.hip).  Every argument is checked here, before any launch.
@@ -720,10 +738,10 @@ static const char* colorfix_geometry(int32_t T, int32_t H, int32_t W, int32_t ki
     if (((int64_t)H + WAVELET_TILE - 1) / WAVELET_TILE > 65535) return "H beyond 65535 tiles";
     return nullptr;
 }
-#define SVR_COLORFIX_REFUSE(name, arg, why) do { snprintf(g_err, sizeof(g_err), "%s: %s%s%s", name, arg, *(arg) ? " " : "", why); return -1; } while (0)
-#define SVR_COLORFIX_PTR(name, p) do { if (!(p)) SVR_COLORFIX_REFUSE(name, #p, "is a null pointer"); } while (0)
-#define SVR_COLORFIX_STRIDES(name, st, is_output, dst) do { if (const char* w_ = colorfix_strides(st, is_output, dst)) SVR_COLORFIX_REFUSE(name, #st, w_); } while (0)
-#define SVR_COLORFIX_GEOMETRY(name) do { if (const char* w_ = colorfix_geometry(T, H, W, kind)) SVR_COLORFIX_REFUSE(name, "", w_); } while (0)
+// thin over the Entry ``e`` of the entry point that uses them: they name the argument they refuse by its spelling
+#define SVR_COLORFIX_PTR(p) do { if (!(p)) return e.refuse(#p " is a null pointer"); } while (0)
+#define SVR_COLORFIX_STRIDES(st, is_output, dst) do { if (const char* w_ = colorfix_strides(st, is_output, dst)) return e.refuse(#st " %s", w_); } while (0)
+#define SVR_COLORFIX_GEOMETRY() do { if (const char* w_ = colorfix_geometry(T, H, W, kind)) return e.refuse("%s", w_); } while (0)
 
 int64_t svr_colorfix_workspace_bytes(int32_t T) {
     if (T < 1 || T > 21845) return 0;
@@ -732,99 +750,99 @@ int64_t svr_colorfix_workspace_bytes(int32_t T) {
 
 int svr_wavelet_reconstruct(const void* content, const int64_t* content_strides, const void* style, const int64_t* style_strides,
                             void* out, const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_wavelet_reconstruct", stream};
     PixStrides cs, ss, os;
-    SVR_COLORFIX_PTR("svr_wavelet_reconstruct", content);
-    SVR_COLORFIX_PTR("svr_wavelet_reconstruct", style);
-    SVR_COLORFIX_PTR("svr_wavelet_reconstruct", out);
-    SVR_COLORFIX_STRIDES("svr_wavelet_reconstruct", content_strides, false, cs);
-    SVR_COLORFIX_STRIDES("svr_wavelet_reconstruct", style_strides, false, ss);
-    SVR_COLORFIX_STRIDES("svr_wavelet_reconstruct", out_strides, true, os);
-    SVR_COLORFIX_GEOMETRY("svr_wavelet_reconstruct");
+    SVR_COLORFIX_PTR(content);
+    SVR_COLORFIX_PTR(style);
+    SVR_COLORFIX_PTR(out);
+    SVR_COLORFIX_STRIDES(content_strides, false, cs);
+    SVR_COLORFIX_STRIDES(style_strides, false, ss);
+    SVR_COLORFIX_STRIDES(out_strides, true, os);
+    SVR_COLORFIX_GEOMETRY();
     WaveletRadii radii;
     int halo = 0;
     for (int i = 0; i < WAVELET_LEVELS; ++i) halo += radii.r[i] = std::min(1 << i, std::max(1, std::min(H, W) / 8));
     static uint64_t lds_attr_done = 0;               // per device (svr_common.h)
-    if (int e = set_max_dynamic_lds((const void*)wavelet_kernel, WAVELET_LDS_BYTES, lds_attr_done)) return check(e, "svr_wavelet_reconstruct");
+    if (int rc = set_max_dynamic_lds((const void*)wavelet_kernel, WAVELET_LDS_BYTES, lds_attr_done)) return e.hip(rc);
     const dim3 grid(blocks_for(W, WAVELET_TILE), blocks_for(H, WAVELET_TILE), (unsigned)T * 3);
     hipLaunchKernelGGL(wavelet_kernel, grid, dim3(WAVELET_THREADS), WAVELET_LDS_BYTES, (hipStream_t)stream, (const float*)content, cs,
                        (const float*)style, ss, (float*)out, os, H, W, radii, halo);
-    return check(hipGetLastError(), "svr_wavelet_reconstruct");
+    return e.launched();
 }
 
 int svr_lab_planes(const void* base, const int64_t* base_strides, const void* style, const int64_t* style_strides, void* c_lab,
                    void* s_lab, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_lab_planes", stream};
     PixStrides bs, ss;
-    SVR_COLORFIX_PTR("svr_lab_planes", base);
-    SVR_COLORFIX_PTR("svr_lab_planes", style);
-    SVR_COLORFIX_PTR("svr_lab_planes", c_lab);
-    SVR_COLORFIX_PTR("svr_lab_planes", s_lab);
-    SVR_COLORFIX_STRIDES("svr_lab_planes", base_strides, false, bs);
-    SVR_COLORFIX_STRIDES("svr_lab_planes", style_strides, false, ss);
-    SVR_COLORFIX_GEOMETRY("svr_lab_planes");
+    SVR_COLORFIX_PTR(base);
+    SVR_COLORFIX_PTR(style);
+    SVR_COLORFIX_PTR(c_lab);
+    SVR_COLORFIX_PTR(s_lab);
+    SVR_COLORFIX_STRIDES(base_strides, false, bs);
+    SVR_COLORFIX_STRIDES(style_strides, false, ss);
+    SVR_COLORFIX_GEOMETRY();
     const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
     const dim3 grid((unsigned)((int64_t)T * H * chunks), 2);
     hipLaunchKernelGGL(lab_planes_kernel, grid, dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream, (const float*)base, bs,
                        (const float*)style, ss, (float*)c_lab, (float*)s_lab, H, W, chunks, (int64_t)T * H * W);
-    return check(hipGetLastError(), "svr_lab_planes");
+    return e.launched();
 }
 
 int svr_lab_merge(const void* c_L, const void* m_L, const void* m_a, const void* m_b, double luminance_weight, void* out,
                   const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_lab_merge", stream};
     PixStrides os;
     const bool blend = luminance_weight < 1.0;
-    SVR_COLORFIX_PTR("svr_lab_merge", c_L);
-    if (blend) SVR_COLORFIX_PTR("svr_lab_merge", m_L);
-    SVR_COLORFIX_PTR("svr_lab_merge", m_a);
-    SVR_COLORFIX_PTR("svr_lab_merge", m_b);
-    SVR_COLORFIX_PTR("svr_lab_merge", out);
-    SVR_COLORFIX_STRIDES("svr_lab_merge", out_strides, true, os);
-    if (!(luminance_weight == luminance_weight)) SVR_COLORFIX_REFUSE("svr_lab_merge", "luminance_weight", "is not a number");
-    SVR_COLORFIX_GEOMETRY("svr_lab_merge");
+    SVR_COLORFIX_PTR(c_L);
+    if (blend) SVR_COLORFIX_PTR(m_L);
+    SVR_COLORFIX_PTR(m_a);
+    SVR_COLORFIX_PTR(m_b);
+    SVR_COLORFIX_PTR(out);
+    SVR_COLORFIX_STRIDES(out_strides, true, os);
+    if (!(luminance_weight == luminance_weight)) return e.refuse("luminance_weight is not a number");
+    SVR_COLORFIX_GEOMETRY();
     const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
     // (both factors rounded from fp64 once, as torch rounds the Python scalars luminance_weight and 1.0 - luminance_weight)
     hipLaunchKernelGGL(lab_merge_kernel, dim3((unsigned)((int64_t)T * H * chunks)), dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream,
                        (const float*)c_L, blend ? (const float*)m_L : nullptr, (const float*)m_a, (const float*)m_b,
                        (float)luminance_weight, (float)(1.0 - luminance_weight), (float*)out, os, H, W, chunks);
-    return check(hipGetLastError(), "svr_lab_merge");
+    return e.launched();
 }
 
 int svr_chan_stats(const void* content, const int64_t* content_strides, const void* style, const int64_t* style_strides, void* stats,
                    int32_t T, int32_t H, int32_t W, int32_t kind, void* workspace, int64_t workspace_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_chan_stats", stream};
     PixStrides cs, ss;
-    SVR_COLORFIX_PTR("svr_chan_stats", content);
-    SVR_COLORFIX_PTR("svr_chan_stats", style);
-    SVR_COLORFIX_PTR("svr_chan_stats", stats);
-    SVR_COLORFIX_PTR("svr_chan_stats", workspace);
-    SVR_COLORFIX_STRIDES("svr_chan_stats", content_strides, false, cs);
-    SVR_COLORFIX_STRIDES("svr_chan_stats", style_strides, false, ss);
-    SVR_COLORFIX_GEOMETRY("svr_chan_stats");
-    if ((uintptr_t)workspace % 8) SVR_COLORFIX_REFUSE("svr_chan_stats", "workspace", "is not aligned to 8 bytes");
-    if (workspace_bytes < svr_colorfix_workspace_bytes(T)) SVR_COLORFIX_REFUSE("svr_chan_stats", "workspace_bytes", "is below svr_colorfix_workspace_bytes(T)");
+    SVR_COLORFIX_PTR(content);
+    SVR_COLORFIX_PTR(style);
+    SVR_COLORFIX_PTR(stats);
+    SVR_COLORFIX_PTR(workspace);
+    SVR_COLORFIX_STRIDES(content_strides, false, cs);
+    SVR_COLORFIX_STRIDES(style_strides, false, ss);
+    SVR_COLORFIX_GEOMETRY();
+    if ((uintptr_t)workspace % 8) return e.refuse("workspace is not aligned to 8 bytes");
+    if (workspace_bytes < svr_colorfix_workspace_bytes(T)) return e.refuse("workspace_bytes is below svr_colorfix_workspace_bytes(T)");
     hipLaunchKernelGGL(chan_stats_kernel, dim3(CHAN_STATS_PARTS, (unsigned)T * 3, 2), dim3(256), 0, (hipStream_t)stream,
                        (const float*)content, cs, (const float*)style, ss, H, W, (double*)workspace);
     hipLaunchKernelGGL(chan_stats_finish_kernel, dim3(blocks_for((int64_t)2 * T * 3, 256)), dim3(256), 0, (hipStream_t)stream,
                        (const double*)workspace, T * 3, (double)H * (double)W, (float*)stats);
-    return check(hipGetLastError(), "svr_chan_stats");
+    return e.launched();
 }
 
 int svr_adain_apply(const void* content, const int64_t* content_strides, const void* stats, float eps, void* out,
                     const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_adain_apply", stream};
     PixStrides cs, os;
-    SVR_COLORFIX_PTR("svr_adain_apply", content);
-    SVR_COLORFIX_PTR("svr_adain_apply", stats);
-    SVR_COLORFIX_PTR("svr_adain_apply", out);
-    SVR_COLORFIX_STRIDES("svr_adain_apply", content_strides, false, cs);
-    SVR_COLORFIX_STRIDES("svr_adain_apply", out_strides, true, os);
-    SVR_COLORFIX_GEOMETRY("svr_adain_apply");
+    SVR_COLORFIX_PTR(content);
+    SVR_COLORFIX_PTR(stats);
+    SVR_COLORFIX_PTR(out);
+    SVR_COLORFIX_STRIDES(content_strides, false, cs);
+    SVR_COLORFIX_STRIDES(out_strides, true, os);
+    SVR_COLORFIX_GEOMETRY();
     const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
     hipLaunchKernelGGL(adain_apply_kernel, dim3((unsigned)((int64_t)T * H * chunks)), dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream,
                        (const float*)content, cs, (const float*)stats, eps, (float*)out, os, H, W, chunks);
-    return check(hipGetLastError(), "svr_adain_apply");
+    return e.launched();
 }
 
 // ---- rank matching (svr_rank.hip): a stable radix sort of fp32 keys and the scatter that hands out the sorted reference.
@@ -881,14 +899,15 @@ static bool rank_overlap(const void* a, int64_t a_bytes, const void* b, int64_t 
     const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
     return a0 < b0 + (uintptr_t)b_bytes && b0 < a0 + (uintptr_t)a_bytes;
 }
-#define SVR_RANK_N_AND_WORKSPACE(name) do { \
-        if (n < 1 || n > RANK_MAX_N) SVR_COLORFIX_REFUSE(name, "n", "must be in [1, 2^30]"); \
-        if ((uintptr_t)workspace % 16) SVR_COLORFIX_REFUSE(name, "workspace", "is not aligned to 16 bytes"); \
-        if (workspace_bytes < svr_rank_workspace_bytes(n)) SVR_COLORFIX_REFUSE(name, "workspace_bytes", "is below svr_rank_workspace_bytes(n)"); \
+// (``bytes_fn``: svr_rank_workspace_bytes or svr_hue_match_workspace_bytes, named in the refusal)
+#define SVR_RANK_N_AND_WORKSPACE(bytes_fn) do { \
+        if (n < 1 || n > RANK_MAX_N) return e.refuse("n must be in [1, 2^30]"); \
+        if ((uintptr_t)workspace % 16) return e.refuse("workspace is not aligned to 16 bytes"); \
+        if (workspace_bytes < bytes_fn(n)) return e.refuse("workspace_bytes is below " #bytes_fn "(n)"); \
     } while (0)
-#define SVR_RANK_ALIGNED(name, p) do { if ((uintptr_t)(p) % 4) SVR_COLORFIX_REFUSE(name, #p, "is not aligned to 4 bytes"); } while (0)
-#define SVR_RANK_APART(name, a, b) do { if (rank_overlap(a, 4 * n, b, 4 * n)) SVR_COLORFIX_REFUSE(name, #a, "overlaps " #b); } while (0)
-#define SVR_RANK_OFF_WORKSPACE(name, a) do { if (rank_overlap(a, 4 * n, workspace, svr_rank_workspace_bytes(n))) SVR_COLORFIX_REFUSE(name, #a, "overlaps workspace"); } while (0)
+#define SVR_RANK_ALIGNED(p) do { if ((uintptr_t)(p) % 4) return e.refuse(#p " is not aligned to 4 bytes"); } while (0)
+#define SVR_RANK_APART(a, b) do { if (rank_overlap(a, 4 * n, b, 4 * n)) return e.refuse(#a " overlaps " #b); } while (0)
+#define SVR_RANK_OFF_WORKSPACE(a, bytes) do { if (rank_overlap(a, 4 * n, workspace, bytes)) return e.refuse(#a " overlaps workspace"); } while (0)
 
 int64_t svr_rank_workspace_bytes(int64_t n) {
     if (n < 1 || n > RANK_MAX_N) return 0;
@@ -896,120 +915,123 @@ int64_t svr_rank_workspace_bytes(int64_t n) {
 }
 
 int svr_rank_geometry(int32_t* out2) {
-    SVR_COLORFIX_PTR("svr_rank_geometry", out2);
+    const Entry e{"svr_rank_geometry"};
+    SVR_COLORFIX_PTR(out2);
     out2[0] = RANK_TILE;
     out2[1] = 0;                                     // rank_scan_kernel walks a row of any length with a carry
     return 0;
 }
 
 int svr_sort_f32(const void* keys, int64_t n, void* sorted, void* index, void* workspace, int64_t workspace_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
-    SVR_COLORFIX_PTR("svr_sort_f32", keys);
-    SVR_COLORFIX_PTR("svr_sort_f32", sorted);
-    SVR_COLORFIX_PTR("svr_sort_f32", workspace);
-    SVR_RANK_N_AND_WORKSPACE("svr_sort_f32");
-    SVR_RANK_ALIGNED("svr_sort_f32", keys);
-    SVR_RANK_ALIGNED("svr_sort_f32", sorted);
-    SVR_RANK_ALIGNED("svr_sort_f32", index);
-    SVR_RANK_APART("svr_sort_f32", sorted, keys);
+    const Launch e{"svr_sort_f32", stream};
+    SVR_COLORFIX_PTR(keys);
+    SVR_COLORFIX_PTR(sorted);
+    SVR_COLORFIX_PTR(workspace);
+    SVR_RANK_N_AND_WORKSPACE(svr_rank_workspace_bytes);
+    const int64_t need = svr_rank_workspace_bytes(n);
+    SVR_RANK_ALIGNED(keys);
+    SVR_RANK_ALIGNED(sorted);
+    SVR_RANK_ALIGNED(index);
+    SVR_RANK_APART(sorted, keys);
     if (index) {
-        SVR_RANK_APART("svr_sort_f32", index, keys);
-        SVR_RANK_APART("svr_sort_f32", index, sorted);
-        SVR_RANK_OFF_WORKSPACE("svr_sort_f32", index);
+        SVR_RANK_APART(index, keys);
+        SVR_RANK_APART(index, sorted);
+        SVR_RANK_OFF_WORKSPACE(index, need);
     }
-    SVR_RANK_OFF_WORKSPACE("svr_sort_f32", keys);
-    SVR_RANK_OFF_WORKSPACE("svr_sort_f32", sorted);
+    SVR_RANK_OFF_WORKSPACE(keys, need);
+    SVR_RANK_OFF_WORKSPACE(sorted, need);
     const RankPlan p = rank_plan(n, workspace);
     rank_sort_launch(p, keys, index != nullptr, 1, sorted, index, (hipStream_t)stream);
-    return check(hipGetLastError(), "svr_sort_f32");
+    return e.launched();
 }
 
 int svr_rank_match(const void* source, const void* reference, int64_t n, void* out, void* workspace, int64_t workspace_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
-    SVR_COLORFIX_PTR("svr_rank_match", source);
-    SVR_COLORFIX_PTR("svr_rank_match", reference);
-    SVR_COLORFIX_PTR("svr_rank_match", out);
-    SVR_COLORFIX_PTR("svr_rank_match", workspace);
-    if (g_rank_launches != 3) SVR_COLORFIX_REFUSE("svr_rank_match", "", "svr_set_option(\"rank_launches\") below 3 serves svr_sort_f32 only");
-    SVR_RANK_N_AND_WORKSPACE("svr_rank_match");
-    SVR_RANK_ALIGNED("svr_rank_match", source);
-    SVR_RANK_ALIGNED("svr_rank_match", reference);
-    SVR_RANK_ALIGNED("svr_rank_match", out);
-    SVR_RANK_APART("svr_rank_match", out, reference);
-    if (out != source) SVR_RANK_APART("svr_rank_match", out, source);          // out == source: the plane is matched in place
-    SVR_RANK_APART("svr_rank_match", source, reference);
-    SVR_RANK_OFF_WORKSPACE("svr_rank_match", source);
-    SVR_RANK_OFF_WORKSPACE("svr_rank_match", reference);
-    SVR_RANK_OFF_WORKSPACE("svr_rank_match", out);
+    const Launch e{"svr_rank_match", stream};
+    SVR_COLORFIX_PTR(source);
+    SVR_COLORFIX_PTR(reference);
+    SVR_COLORFIX_PTR(out);
+    SVR_COLORFIX_PTR(workspace);
+    if (g_rank_launches != 3) return e.refuse("svr_set_option(\"rank_launches\") below 3 serves svr_sort_f32 only");
+    SVR_RANK_N_AND_WORKSPACE(svr_rank_workspace_bytes);
+    const int64_t need = svr_rank_workspace_bytes(n);
+    SVR_RANK_ALIGNED(source);
+    SVR_RANK_ALIGNED(reference);
+    SVR_RANK_ALIGNED(out);
+    SVR_RANK_APART(out, reference);
+    if (out != source) SVR_RANK_APART(out, source);          // out == source: the plane is matched in place
+    SVR_RANK_APART(source, reference);
+    SVR_RANK_OFF_WORKSPACE(source, need);
+    SVR_RANK_OFF_WORKSPACE(reference, need);
+    SVR_RANK_OFF_WORKSPACE(out, need);
     const RankPlan p = rank_plan(n, workspace);
     const hipStream_t s = (hipStream_t)stream;
     rank_sort_launch(p, reference, false, 1, p.ref, nullptr, s);               // the reference's sorted values stay in the workspace
     rank_sort_launch(p, source, true, 2, nullptr, p.idx[1], s);                // source: only where each rank came from is kept
     hipLaunchKernelGGL(rank_apply_kernel, dim3(blocks_for(n, 1024)), dim3(256), 0, s, (const uint32_t*)p.idx[1], (const uint32_t*)p.ref,
                        p.n, (uint32_t*)out);
-    return check(hipGetLastError(), "svr_rank_match");
+    return e.launched();
 }
 
 // ---- the HSV half (svr_hsv.hip)
 int svr_hsv_planes(const void* content, const int64_t* content_strides, const void* style, const int64_t* style_strides, void* c_hsv,
                    void* s_hs, int32_t T, int32_t H, int32_t W, int32_t kind, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_hsv_planes", stream};
     PixStrides cs, ss;
-    SVR_COLORFIX_PTR("svr_hsv_planes", content);
-    SVR_COLORFIX_PTR("svr_hsv_planes", style);
-    SVR_COLORFIX_PTR("svr_hsv_planes", c_hsv);
-    SVR_COLORFIX_PTR("svr_hsv_planes", s_hs);
-    SVR_COLORFIX_STRIDES("svr_hsv_planes", content_strides, false, cs);
-    SVR_COLORFIX_STRIDES("svr_hsv_planes", style_strides, false, ss);
-    SVR_COLORFIX_GEOMETRY("svr_hsv_planes");
+    SVR_COLORFIX_PTR(content);
+    SVR_COLORFIX_PTR(style);
+    SVR_COLORFIX_PTR(c_hsv);
+    SVR_COLORFIX_PTR(s_hs);
+    SVR_COLORFIX_STRIDES(content_strides, false, cs);
+    SVR_COLORFIX_STRIDES(style_strides, false, ss);
+    SVR_COLORFIX_GEOMETRY();
     const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
     const dim3 grid((unsigned)((int64_t)T * H * chunks), 2);
     hipLaunchKernelGGL(hsv_planes_kernel, grid, dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream, (const float*)content, cs,
                        (const float*)style, ss, (float*)c_hsv, (float*)s_hs, H, W, chunks, (int64_t)T * H * W);
-    return check(hipGetLastError(), "svr_hsv_planes");
+    return e.launched();
 }
 
 int svr_hsv_merge(const void* h, const void* sat, const void* v, void* out, const int64_t* out_strides, int32_t T, int32_t H, int32_t W,
                   int32_t kind, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_hsv_merge", stream};
     PixStrides os;
-    SVR_COLORFIX_PTR("svr_hsv_merge", h);
-    SVR_COLORFIX_PTR("svr_hsv_merge", sat);
-    SVR_COLORFIX_PTR("svr_hsv_merge", v);
-    SVR_COLORFIX_PTR("svr_hsv_merge", out);
-    SVR_COLORFIX_STRIDES("svr_hsv_merge", out_strides, true, os);
-    SVR_COLORFIX_GEOMETRY("svr_hsv_merge");
+    SVR_COLORFIX_PTR(h);
+    SVR_COLORFIX_PTR(sat);
+    SVR_COLORFIX_PTR(v);
+    SVR_COLORFIX_PTR(out);
+    SVR_COLORFIX_STRIDES(out_strides, true, os);
+    SVR_COLORFIX_GEOMETRY();
     const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
     hipLaunchKernelGGL(hsv_merge_kernel, dim3((unsigned)((int64_t)T * H * chunks)), dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream,
                        (const float*)h, (const float*)sat, (const float*)v, (float*)out, os, H, W, chunks);
-    return check(hipGetLastError(), "svr_hsv_merge");
+    return e.launched();
 }
 
 int svr_adaptive_blend(const void* base, const int64_t* base_strides, const void* content, const int64_t* content_strides,
                        const void* style, const int64_t* style_strides, const void* h, const void* sat, const void* v, double threshold,
                        double sharpness, void* out, const int64_t* out_strides, int32_t T, int32_t H, int32_t W, int32_t kind,
                        void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_adaptive_blend", stream};
     PixStrides bs, cs, ss, os;
-    SVR_COLORFIX_PTR("svr_adaptive_blend", base);
-    SVR_COLORFIX_PTR("svr_adaptive_blend", content);
-    SVR_COLORFIX_PTR("svr_adaptive_blend", style);
-    SVR_COLORFIX_PTR("svr_adaptive_blend", h);
-    SVR_COLORFIX_PTR("svr_adaptive_blend", sat);
-    SVR_COLORFIX_PTR("svr_adaptive_blend", v);
-    SVR_COLORFIX_PTR("svr_adaptive_blend", out);
-    SVR_COLORFIX_STRIDES("svr_adaptive_blend", base_strides, false, bs);
-    SVR_COLORFIX_STRIDES("svr_adaptive_blend", content_strides, false, cs);
-    SVR_COLORFIX_STRIDES("svr_adaptive_blend", style_strides, false, ss);
-    SVR_COLORFIX_STRIDES("svr_adaptive_blend", out_strides, true, os);
-    if (!(threshold == threshold)) SVR_COLORFIX_REFUSE("svr_adaptive_blend", "threshold", "is not a number");
-    if (!(sharpness == sharpness)) SVR_COLORFIX_REFUSE("svr_adaptive_blend", "sharpness", "is not a number");
-    SVR_COLORFIX_GEOMETRY("svr_adaptive_blend");
+    SVR_COLORFIX_PTR(base);
+    SVR_COLORFIX_PTR(content);
+    SVR_COLORFIX_PTR(style);
+    SVR_COLORFIX_PTR(h);
+    SVR_COLORFIX_PTR(sat);
+    SVR_COLORFIX_PTR(v);
+    SVR_COLORFIX_PTR(out);
+    SVR_COLORFIX_STRIDES(base_strides, false, bs);
+    SVR_COLORFIX_STRIDES(content_strides, false, cs);
+    SVR_COLORFIX_STRIDES(style_strides, false, ss);
+    SVR_COLORFIX_STRIDES(out_strides, true, os);
+    if (!(threshold == threshold)) return e.refuse("threshold is not a number");
+    if (!(sharpness == sharpness)) return e.refuse("sharpness is not a number");
+    SVR_COLORFIX_GEOMETRY();
     const int chunks = (int)blocks_for(W, COLORFIX_ROW_PIXELS);
     hipLaunchKernelGGL(adaptive_blend_kernel, dim3((unsigned)((int64_t)T * H * chunks)), dim3(COLORFIX_ROW_PIXELS), 0, (hipStream_t)stream,
                        (const float*)base, bs, (const float*)content, cs, (const float*)style, ss, (const float*)h, (const float*)sat,
                        (const float*)v, (float)threshold, (float)(threshold * 0.5), (float)sharpness, (float*)out, os, H, W, chunks);
-    return check(hipGetLastError(), "svr_adaptive_blend");
+    return e.launched();
 }
 
 // Hue-conditional rank matching.  Workspace (bytes; n4 = 4 * n rounded up to 256): [source keys by class n4][source indices by class
@@ -1044,25 +1066,23 @@ static RankPlan hue_run_plan(const RankPlan& whole, uint32_t m) {
     return p;
 }
 // one pass whose digit is the hue's (svr_rank.hip, DIGIT 1: the class, or 2: outside bin 0): keys (and flat indices) of ``sat`` in the
-// stable order of the digit
-#define SVR_HUE_SCATTER(PAIRS, DIGIT, OUT_IDX) \
-    hipLaunchKernelGGL((rank_scatter_kernel<PAIRS, DIGIT>), dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)sat, \
-                       (const uint32_t*)nullptr, (const float*)hue, p.n, 0, 1, 0, (const uint32_t*)p.table, p.tiles_p, \
-                       (const uint32_t*)totals, (uint32_t*)out_keys, (uint32_t*)(OUT_IDX))
+// stable order of the digit.  ``out_idx`` is nullptr where ``pairs`` is false
 static void hue_partition_launch(const RankPlan& p, bool by_class, const void* sat, const void* hue, bool pairs, uint32_t* totals,
                                  void* out_keys, void* out_idx, hipStream_t s) {
-    if (by_class)
-        hipLaunchKernelGGL(rank_hist_kernel<1>, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)sat, (const float*)hue, p.n, 0, 1,
+    with_const<2, 1>(by_class ? 1 : 2, [&](auto DIGIT) {
+        hipLaunchKernelGGL(rank_hist_kernel<DIGIT()>, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)sat, (const float*)hue, p.n, 0, 1,
                            p.table, p.tiles_p);
-    else
-        hipLaunchKernelGGL(rank_hist_kernel<2>, dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)sat, (const float*)hue, p.n, 0, 1,
-                           p.table, p.tiles_p);
+    });
     hipLaunchKernelGGL(rank_scan_kernel, dim3(RANK_RADIX), dim3(RANK_THREADS), 0, s, p.table, p.tiles_p, totals);
-    if (!by_class) SVR_HUE_SCATTER(true, 2, out_idx);             // (the partition of bin 0 serves the source side only)
-    else if (pairs) SVR_HUE_SCATTER(true, 1, out_idx);
-    else SVR_HUE_SCATTER(false, 1, nullptr);
+    auto scatter = [&](auto PAIRS, auto DIGIT) {
+        hipLaunchKernelGGL((rank_scatter_kernel<PAIRS(), DIGIT()>), dim3(p.groups), dim3(RANK_THREADS), 0, s, (const uint32_t*)sat,
+                           (const uint32_t*)nullptr, (const float*)hue, p.n, 0, 1, 0, (const uint32_t*)p.table, p.tiles_p,
+                           (const uint32_t*)totals, (uint32_t*)out_keys, (uint32_t*)out_idx);
+    };
+    if (!by_class) scatter(std::true_type{}, std::integral_constant<int, 2>{});      // (the partition of bin 0 serves the source side only)
+    else if (pairs) scatter(std::true_type{}, std::integral_constant<int, 1>{});
+    else scatter(std::false_type{}, std::integral_constant<int, 1>{});
 }
-#undef SVR_HUE_SCATTER
 
 int64_t svr_hue_match_workspace_bytes(int64_t n) {
     if (n < 1 || n > RANK_MAX_N) return 0;
@@ -1071,50 +1091,46 @@ int64_t svr_hue_match_workspace_bytes(int64_t n) {
 
 int svr_hue_match(const void* c_h, const void* c_s, const void* s_h, const void* s_s, int64_t n, void* out, void* workspace,
                   int64_t workspace_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
-    SVR_COLORFIX_PTR("svr_hue_match", c_h);
-    SVR_COLORFIX_PTR("svr_hue_match", c_s);
-    SVR_COLORFIX_PTR("svr_hue_match", s_h);
-    SVR_COLORFIX_PTR("svr_hue_match", s_s);
-    SVR_COLORFIX_PTR("svr_hue_match", out);
-    SVR_COLORFIX_PTR("svr_hue_match", workspace);
-    if (g_rank_launches != 3) SVR_COLORFIX_REFUSE("svr_hue_match", "", "svr_set_option(\"rank_launches\") below 3 serves svr_sort_f32 only");
-    if (n < 1 || n > RANK_MAX_N) SVR_COLORFIX_REFUSE("svr_hue_match", "n", "must be in [1, 2^30]");
-    if ((uintptr_t)workspace % 16) SVR_COLORFIX_REFUSE("svr_hue_match", "workspace", "is not aligned to 16 bytes");
+    const Launch e{"svr_hue_match", stream};
+    SVR_COLORFIX_PTR(c_h);
+    SVR_COLORFIX_PTR(c_s);
+    SVR_COLORFIX_PTR(s_h);
+    SVR_COLORFIX_PTR(s_s);
+    SVR_COLORFIX_PTR(out);
+    SVR_COLORFIX_PTR(workspace);
+    if (g_rank_launches != 3) return e.refuse("svr_set_option(\"rank_launches\") below 3 serves svr_sort_f32 only");
+    SVR_RANK_N_AND_WORKSPACE(svr_hue_match_workspace_bytes);
     const int64_t need = svr_hue_match_workspace_bytes(n);
-    if (workspace_bytes < need) SVR_COLORFIX_REFUSE("svr_hue_match", "workspace_bytes", "is below svr_hue_match_workspace_bytes(n)");
-#define SVR_HUE_OFF_WORKSPACE(a) do { if (rank_overlap(a, 4 * n, workspace, need)) SVR_COLORFIX_REFUSE("svr_hue_match", #a, "overlaps workspace"); } while (0)
-    SVR_RANK_ALIGNED("svr_hue_match", c_h);
-    SVR_RANK_ALIGNED("svr_hue_match", c_s);
-    SVR_RANK_ALIGNED("svr_hue_match", s_h);
-    SVR_RANK_ALIGNED("svr_hue_match", s_s);
-    SVR_RANK_ALIGNED("svr_hue_match", out);
-    SVR_RANK_APART("svr_hue_match", out, c_h);
-    if (out != c_s) SVR_RANK_APART("svr_hue_match", out, c_s);                 // out == c_s: the saturation plane is matched in place
-    SVR_RANK_APART("svr_hue_match", out, s_h);
-    SVR_RANK_APART("svr_hue_match", out, s_s);
-    SVR_HUE_OFF_WORKSPACE(c_h);
-    SVR_HUE_OFF_WORKSPACE(c_s);
-    SVR_HUE_OFF_WORKSPACE(s_h);
-    SVR_HUE_OFF_WORKSPACE(s_s);
-    SVR_HUE_OFF_WORKSPACE(out);
-#undef SVR_HUE_OFF_WORKSPACE
+    SVR_RANK_ALIGNED(c_h);
+    SVR_RANK_ALIGNED(c_s);
+    SVR_RANK_ALIGNED(s_h);
+    SVR_RANK_ALIGNED(s_s);
+    SVR_RANK_ALIGNED(out);
+    SVR_RANK_APART(out, c_h);
+    if (out != c_s) SVR_RANK_APART(out, c_s);                 // out == c_s: the saturation plane is matched in place
+    SVR_RANK_APART(out, s_h);
+    SVR_RANK_APART(out, s_s);
+    SVR_RANK_OFF_WORKSPACE(c_h, need);
+    SVR_RANK_OFF_WORKSPACE(c_s, need);
+    SVR_RANK_OFF_WORKSPACE(s_h, need);
+    SVR_RANK_OFF_WORKSPACE(s_s, need);
+    SVR_RANK_OFF_WORKSPACE(out, need);
     const HuePlan p = hue_plan(n, workspace);
     const hipStream_t s = (hipStream_t)stream;
     hue_partition_launch(p.sort, true, c_s, c_h, true, p.tot_src, p.cls_k, p.cls_i, s);
     hue_partition_launch(p.sort, true, s_s, s_h, false, p.tot_ref, p.ref_k, nullptr, s);
-    if (int rc = check(hipGetLastError(), "svr_hue_match")) return rc;
+    if (int rc = e.launched()) return rc;
     // the one read of the call: 2 x 256 class counts (source, reference), which decide the bins that are sorted and their runs
     uint32_t counts[2 * RANK_RADIX];
-    if (int rc = check(hipMemcpyAsync(counts, p.tot_src, sizeof(counts), hipMemcpyDeviceToHost, s), "svr_hue_match: class counts")) return rc;
-    if (int rc = check(hipStreamSynchronize(s), "svr_hue_match: class counts")) return rc;
+    if (int rc = e.hip(hipMemcpyAsync(counts, p.tot_src, sizeof(counts), hipMemcpyDeviceToHost, s), "class counts")) return rc;
+    if (int rc = e.hip(hipStreamSynchronize(s), "class counts")) return rc;
     const uint32_t *n_src = counts, *n_ref = counts + RANK_RADIX;
     uint32_t at_src[HUE_CLASSES + 1] = {0}, at_ref[HUE_CLASSES + 1] = {0};
     for (int d = 0; d < HUE_CLASSES; ++d) { at_src[d + 1] = at_src[d] + n_src[d]; at_ref[d + 1] = at_ref[d] + n_ref[d]; }
     if (at_src[HUE_CLASSES] != (uint32_t)n || at_ref[HUE_CLASSES] != (uint32_t)n)
-        SVR_COLORFIX_REFUSE("svr_hue_match", "", "the class counts read back do not add up to n");
+        return e.refuse("the class counts read back do not add up to n");
     if (out != c_s)
-        if (int rc = check(hipMemcpyAsync(out, c_s, (size_t)(4 * n), hipMemcpyDeviceToDevice, s), "svr_hue_match: out = c_s")) return rc;
+        if (int rc = e.hip(hipMemcpyAsync(out, c_s, (size_t)(4 * n), hipMemcpyDeviceToDevice, s), "out = c_s")) return rc;
     for (int bin = 0; bin < HUE_BINS; ++bin) {
         // digits of the bin's classes (svr_rank.hip, rank_hue_class): bin 0 = digits 0..2, bin 11 = digit 2, bin k = digit k + 2
         const int d0 = bin == 0 ? 0 : (bin == HUE_BINS - 1 ? 2 : bin + 2), d1 = bin == 0 ? 3 : d0 + 1;
@@ -1130,7 +1146,7 @@ int svr_hue_match(const void* c_h, const void* c_s, const void* s_h, const void*
         hipLaunchKernelGGL(hue_apply_kernel, dim3(blocks_for(m_src, 256)), dim3(256), 0, s, (const uint32_t*)p.sort.idx[1],
                            (const uint32_t*)p.sort.ref, m_src, m_ref, (uint32_t*)out);
     }
-    return check(hipGetLastError(), "svr_hue_match");
+    return e.launched();
 }
 #undef SVR_RANK_OFF_WORKSPACE
 #undef SVR_RANK_APART
@@ -1139,12 +1155,11 @@ int svr_hue_match(const void* c_h, const void* c_s, const void* s_h, const void*
 #undef SVR_COLORFIX_GEOMETRY
 #undef SVR_COLORFIX_STRIDES
 #undef SVR_COLORFIX_PTR
-#undef SVR_COLORFIX_REFUSE
 
 // ---- packed input frames (svr_frame_unpack.hip)
 int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,
                       int32_t matrix, int32_t range, float* out, int64_t out_bytes, void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_unpack_frames", stream};
     const bool yuv = fmt == SVR_UNPACK_YUV420P8 || fmt == SVR_UNPACK_YUV420P10;
     const bool wide = fmt == SVR_UNPACK_RGB16 || fmt == SVR_UNPACK_YUV420P10;          // 16-bit samples
     const char* why = nullptr;
@@ -1159,52 +1174,40 @@ int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int
     else if (range != SVR_RANGE_TV && range != SVR_RANGE_PC) why = "range must be SVR_RANGE_TV or SVR_RANGE_PC";
     else if (wide && (uintptr_t)packed % 2) why = "packed is not aligned to 2 bytes";
     else if ((uintptr_t)out % 4) why = "out is not aligned to 4 bytes";
-    if (why) { snprintf(g_err, sizeof(g_err), "svr_unpack_frames: %s", why); return -1; }
+    if (why) return e.refuse("%s", why);
     const int64_t px = (int64_t)T * H * W, h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
     const int64_t n = yuv ? (int64_t)T * ((int64_t)H * W + 2 * h2 * w2) : px * C;       // samples
     const int64_t need_in = n * (wide ? 2 : 1), need_out = px * C * 4;
-    if (packed_bytes != need_in) {
-        snprintf(g_err, sizeof(g_err), "svr_unpack_frames: packed_bytes is %lld, the format needs exactly %lld", (long long)packed_bytes, (long long)need_in);
-        return -1;
-    }
-    if (out_bytes != need_out) {
-        snprintf(g_err, sizeof(g_err), "svr_unpack_frames: out_bytes is %lld, fp32 [T, H, W, C] needs exactly %lld", (long long)out_bytes, (long long)need_out);
-        return -1;
-    }
+    if (packed_bytes != need_in) return e.wrong_size("packed_bytes", packed_bytes, "the format needs", need_in);
+    if (out_bytes != need_out) return e.wrong_size("out_bytes", out_bytes, "fp32 [T, H, W, C] needs", need_out);
     const bool aligned = (uintptr_t)packed % 16 == 0 && (uintptr_t)out % 16 == 0;
-    const int64_t cap = (int64_t)device_cu_count() * 8;
-    auto capped = [cap](int64_t work) { return (unsigned)std::min<int64_t>((work + 255) / 256, cap); };
     const hipStream_t s = (hipStream_t)stream;
     if (yuv) {
         // Kr, Kb exact decimals, the four products rounded at 2^16: 2 (1 - Kr), 2 (1 - Kb) Kb / Kg, 2 (1 - Kr) Kr / Kg, 2 (1 - Kb)
         const YuvCoef k = matrix == SVR_MATRIX_BT709 ? YuvCoef{103206, 12276, 30679, 121609} : YuvCoef{91881, 22553, 46802, 116130};
         const bool vec = aligned && W % 16 == 0;
-        const unsigned grid = capped(vec ? (int64_t)T * h2 * (W / 16) : px);
-#define SVR_UNPACK_YUV(BITS, PC) \
-        if (vec) hipLaunchKernelGGL((unpack_yuv_vec_kernel<BITS, PC>), dim3(grid), dim3(256), 0, s, packed, out, T, H, W, k); \
-        else hipLaunchKernelGGL((unpack_yuv_kernel<BITS, PC>), dim3(grid), dim3(256), 0, s, packed, out, T, H, W, k)
-        if (fmt == SVR_UNPACK_YUV420P8) { if (range == SVR_RANGE_TV) { SVR_UNPACK_YUV(8, 0); } else { SVR_UNPACK_YUV(8, 1); } }
-        else { if (range == SVR_RANGE_TV) { SVR_UNPACK_YUV(10, 0); } else { SVR_UNPACK_YUV(10, 1); } }
-#undef SVR_UNPACK_YUV
-        return check(hipGetLastError(), "svr_unpack_frames");
+        const unsigned grid = capped_grid(vec ? (int64_t)T * h2 * (W / 16) : px);
+        with_const<10, 8>(fmt == SVR_UNPACK_YUV420P8 ? 8 : 10, [&](auto BITS) { with_const<SVR_RANGE_PC, SVR_RANGE_TV>(range, [&](auto PC) {
+            if (vec) hipLaunchKernelGGL((unpack_yuv_vec_kernel<BITS(), PC()>), dim3(grid), dim3(256), 0, s, packed, out, T, H, W, k);
+            else hipLaunchKernelGGL((unpack_yuv_kernel<BITS(), PC()>), dim3(grid), dim3(256), 0, s, packed, out, T, H, W, k);
+        }); });
+        return e.launched();
     }
     const int swap = fmt == SVR_UNPACK_BGR8 ? C : 0;               // unpack_rgb_kernel's C: 0 = samples in place
     const int unit = wide ? 8 : swap == 3 ? 48 : 16;
     const int64_t n_units = aligned ? n / unit : 0;
-    const unsigned grid = capped(std::max<int64_t>(n_units, n - n_units * unit));
-#define SVR_UNPACK_RGB(BYTES, CH) hipLaunchKernelGGL((unpack_rgb_kernel<BYTES, CH>), dim3(grid), dim3(256), 0, s, packed, out, n_units, n)
-    if (wide) SVR_UNPACK_RGB(2, 0);
-    else if (swap == 0) SVR_UNPACK_RGB(1, 0);
-    else if (swap == 3) SVR_UNPACK_RGB(1, 3);
-    else SVR_UNPACK_RGB(1, 4);
-#undef SVR_UNPACK_RGB
-    return check(hipGetLastError(), "svr_unpack_frames");
+    const unsigned grid = capped_grid(std::max<int64_t>(n_units, n - n_units * unit));
+    if (wide) hipLaunchKernelGGL((unpack_rgb_kernel<2, 0>), dim3(grid), dim3(256), 0, s, packed, out, n_units, n);
+    else with_const<4, 3, 0>(swap, [&](auto CH) {
+        hipLaunchKernelGGL((unpack_rgb_kernel<1, CH()>), dim3(grid), dim3(256), 0, s, packed, out, n_units, n);
+    });
+    return e.launched();
 }
 
 // ---- GGUF blocks expanded at load (svr_gguf.hip)
 int svr_dequant_gguf(const void* blocks, int32_t ggml_type, int64_t n_blocks, void* out, int32_t out_kind, int64_t out_bytes,
                      void* stream) {
-    StreamDeviceGuard on_stream_device(stream);
+    const Launch e{"svr_dequant_gguf", stream};
     const bool known = ggml_type == SVR_GGML_Q8_0 || ggml_type == SVR_GGML_Q4_K || ggml_type == SVR_GGML_Q5_K || ggml_type == SVR_GGML_Q6_K;
     const int64_t per = ggml_type == SVR_GGML_Q8_0 ? 32 : 256;            // elements per block
     const char* why = nullptr;
@@ -1216,25 +1219,17 @@ int svr_dequant_gguf(const void* blocks, int32_t ggml_type, int64_t n_blocks, vo
     else if (n_blocks > ((int64_t)1 << 40) / per) why = "n_blocks times the block size must not exceed 2^40 elements";
     else if ((uintptr_t)blocks % 32) why = "blocks is not aligned to 32 bytes";
     else if ((uintptr_t)out % 16) why = "out is not aligned to 16 bytes";
-    if (why) { snprintf(g_err, sizeof(g_err), "svr_dequant_gguf: %s", why); return -1; }
+    if (why) return e.refuse("%s", why);
     const int64_t need = n_blocks * per * (out_kind == SVR_STORE_FP32 ? 4 : 2);
-    if (out_bytes != need) {
-        snprintf(g_err, sizeof(g_err), "svr_dequant_gguf: out_bytes is %lld, the type and block count need exactly %lld", (long long)out_bytes, (long long)need);
-        return -1;
-    }
+    if (out_bytes != need) return e.wrong_size("out_bytes", out_bytes, "the type and block count need", need);
     const int64_t n_units = n_blocks * (per / 8);                          // eight outputs per lane
-    const unsigned grid = (unsigned)std::min<int64_t>((n_units + 255) / 256, (int64_t)device_cu_count() * 8);
+    const unsigned grid = capped_grid(n_units);
     const unsigned char* b = (const unsigned char*)blocks;
     const hipStream_t s = (hipStream_t)stream;
-#define SVR_DEQUANT(TYPE) \
-    if (out_kind == SVR_STORE_FP32) hipLaunchKernelGGL((dequant_gguf_kernel<TYPE, SVR_STORE_FP32>), dim3(grid), dim3(256), 0, s, b, out, n_units); \
-    else hipLaunchKernelGGL((dequant_gguf_kernel<TYPE, SVR_STORE_BF16>), dim3(grid), dim3(256), 0, s, b, out, n_units)
-    if (ggml_type == SVR_GGML_Q8_0) { SVR_DEQUANT(SVR_GGML_Q8_0); }
-    else if (ggml_type == SVR_GGML_Q4_K) { SVR_DEQUANT(SVR_GGML_Q4_K); }
-    else if (ggml_type == SVR_GGML_Q5_K) { SVR_DEQUANT(SVR_GGML_Q5_K); }
-    else { SVR_DEQUANT(SVR_GGML_Q6_K); }
-#undef SVR_DEQUANT
-    return check(hipGetLastError(), "svr_dequant_gguf");
+    with_const<SVR_GGML_Q6_K, SVR_GGML_Q5_K, SVR_GGML_Q4_K, SVR_GGML_Q8_0>(ggml_type, [&](auto TYPE) { with_kind(out_kind, [&](auto K) {
+        hipLaunchKernelGGL((dequant_gguf_kernel<TYPE(), K()>), dim3(grid), dim3(256), 0, s, b, out, n_units);
+    }); });
+    return e.launched();
 }
 
 }  // extern "C"

@@ -30,6 +30,11 @@ SVR_DEVICE uint32_t pack_code(float x, float full_scale) {
     return (uint32_t)__builtin_rintf(fminf(fmaxf(x, 0.f), 1.f) * full_scale);
 }
 
+// 8-bit BT.709 luma of the 8-bit codes, weights rounded at 2^16 (shots.luma8): what cut detection and the active area look at
+SVR_DEVICE uint32_t luma8(float r, float g, float b) {
+    return (13933u * pack_code(r, 255.f) + 46871u * pack_code(g, 255.f) + 4732u * pack_code(b, 255.f) + 32768u) >> 16;
+}
+
 // C == 0: rgb8 (samples in place); C == 3 / 4: bgr8 of C-channel pixels (channels 0 and 2 swapped, a fourth in place)
 template <int KIND, int C>
 __global__ __launch_bounds__(256) void pack8_kernel(const void* __restrict__ x, unsigned char* __restrict__ out, int64_t n_units,

@@ -24,10 +24,7 @@ namespace svr {
 constexpr int SIG_BAND_ROWS = 16;                    // 16 x 1280 pixels = 80 per lane at 720p; 45 bands per cell row and frame
 constexpr int SIG_UNIT = 8;                          // pixels per lane and step on the 16-byte route
 
-SVR_DEVICE uint32_t signature_bin(float r, float g, float b) {
-    const uint32_t y8 = (13933u * pack_code(r, 255.f) + 46871u * pack_code(g, 255.f) + 4732u * pack_code(b, 255.f) + 32768u) >> 16;
-    return y8 >> 2;
-}
+SVR_DEVICE uint32_t signature_bin(float r, float g, float b) { return luma8(r, g, b) >> 2; }
 
 // one count for ``key`` in this wave's histogram; call with any set of active lanes
 SVR_DEVICE void signature_count(int* hist, uint32_t key) {

@@ -32,6 +32,38 @@ def h16_to_float(t: torch.Tensor) -> torch.Tensor:
     return t.float() * (1.0 / H16_SCALE) if t.dtype == H16 else t.float()
 
 
+def on_device(t: torch.Tensor, device: torch.device) -> bool:
+    return t.device == device or (t.device.type == "cuda" == device.type and t.device.index == (device.index or 0))
+
+
+def clip_args(name, frames, device, *, channels="frames must have C = 3 or 4", min_hw=None, before=None, after=None):
+    """What the entry points that read a clip check first -> (T, H, W, C, kind): frames [T, H, W, C] in fp32 or bf16, C = 3 or 4
+    said in the caller's words (``channels``; None: the caller's ``before`` judges C), every size positive (``min_hw``: H and W at
+    least that, spelled out; None: "at least one pixel"), dense and on ``device``.  ``before`` / ``after``: the caller's own
+    checks of (T, H, W, C), run just before / just after the sizes; each returns its complaint or None."""
+    if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
+        raise ValueError(f"{name}: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
+    T, H, W, Cn = frames.shape
+    if channels and Cn not in (3, 4):
+        raise ValueError(f"{name}: {channels}, got C = {Cn}")
+
+    def own(check):
+        why = check(T, H, W, Cn) if check else None
+        if why:
+            raise ValueError(f"{name}: {why}")
+
+    own(before)
+    if T < 1 or min(H, W) < (min_hw or 1):
+        sizes = "at least one pixel" if min_hw is None else f"T >= 1 frames of H >= {min_hw}, W >= {min_hw}"
+        raise ValueError(f"{name}: frames must hold {sizes}, got {tuple(frames.shape)}")
+    own(after)
+    if not on_device(frames, device):
+        raise ValueError(f"{name}: frames must live on {device}, got {frames.device}")
+    if not frames.is_contiguous():
+        raise ValueError(f"{name}: frames must be contiguous")
+    return T, H, W, Cn, store_kind(frames)                  # (fp32 or bf16 by now: SVR_STORE_FP32 / SVR_STORE_BF16)
+
+
 @dataclass
 class Conv3dGeom:
     """Causal conv geometry over an NDHWC input (see svr_conv_geom in include/seedvr2_hip.h)."""
@@ -191,13 +223,22 @@ class HipOps:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _chk(self, t, dtype=None, name="tensor"):
-        if t.device != self.device and not (t.device.type == "cuda" and t.device.index == (self.device.index or 0)):
+        if not on_device(t, self.device):
             raise ValueError(f"{name} must live on {self.device}, got {t.device}")
         if dtype is not None and t.dtype != dtype:
             raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
         if not t.is_contiguous():
             raise ValueError(f"{name} must be contiguous")
         return t
+
+    def _out(self, name, out, shape, dtype, suffix=""):
+        """A result tensor: allocated where ``out`` is None, else checked -- on the device, ``dtype``, dense, exactly ``shape``."""
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        self._chk(out, dtype, f"{name}: out")
+        if tuple(out.shape) != tuple(shape):
+            raise ValueError(f"{name}: out must be {tuple(shape)}{suffix}, got {tuple(out.shape)}")
+        return out
 
     def _opt(self, t, dtype, name, numel=None):
         """Optional (or small side) operand: None -> NULL, else device / dtype / contiguity (and element count) checked."""
@@ -542,25 +583,18 @@ class HipOps:
         """What pack_frames and pack_yuv420p10 check before their launch -> (T, H, W, Cn, x_kind, out); ``out`` allocated where it
         was None.  ``colour``: pack_yuv420p10's (matrix, range_, siting), refused with the format."""
         from . import frameio
-        if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
-            raise ValueError(f"{name}: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
-        T, H, W, Cn = frames.shape
-        try:
-            if colour is not None:
-                frameio.check_colour(*colour)
-            shape = frameio.packed_shape(T, H, W, Cn, fmt)
-        except ValueError as e:
-            raise ValueError(f"{name}: {e}") from None
-        if T < 1 or H < 1 or W < 1:
-            raise ValueError(f"{name}: frames must hold at least one pixel, got {tuple(frames.shape)}")
-        self._chk(frames, None, f"{name}: frames")
-        dtype = frameio.packed_dtype(fmt)
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=self.device)
-        self._chk(out, dtype, f"{name}: out")
-        if tuple(out.shape) != tuple(shape):
-            raise ValueError(f"{name}: out must be {tuple(shape)}{'' if colour else f' for {fmt}'}, got {tuple(out.shape)}")
-        return T, H, W, Cn, 1 if frames.dtype == torch.float32 else 0, out     # SVR_STORE_FP32 / SVR_STORE_BF16
+
+        def codes_and_channels(T, H, W, Cn):                   # (the format judges the channel count)
+            try:
+                if colour is not None:
+                    frameio.check_colour(*colour)
+                frameio.packed_shape(T, H, W, Cn, fmt)
+            except ValueError as e:
+                return str(e)
+
+        T, H, W, Cn, kind = clip_args(name, frames, self.device, channels=None, before=codes_and_channels)
+        out = self._out(name, out, frameio.packed_shape(T, H, W, Cn, fmt), frameio.packed_dtype(fmt), suffix="" if colour else f" for {fmt}")
+        return T, H, W, Cn, kind, out
 
     def pack_frames(self, frames, fmt, out=None):
         """Output frames narrowed on the device (frameio.py is the specification; csrc/svr_frame_pack.hip, yuv420p10 through
@@ -589,22 +623,9 @@ class HipOps:
         csrc/svr_shots.hip): frames [T, H, W, 3 | 4] fp32 / bf16, dense, H >= 4, W >= 4 -> int32 [T, 1024].  The call zeroes the
         result itself; one memset and one launch on the current stream, no host synchronisation.  ``out``: a dense int32 [T, 1024]
         tensor."""
-        if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
-            raise ValueError(f"frame_signatures: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
-        T, H, W, Cn = frames.shape
-        if Cn not in (3, 4):
-            raise ValueError(f"frame_signatures: frames must have C = 3 or 4, got C = {Cn}")
-        if T < 1 or H < 4 or W < 4:
-            raise ValueError(f"frame_signatures: frames must hold T >= 1 frames of H >= 4, W >= 4, got {tuple(frames.shape)}")
-        if H * W >= 1 << 31:
-            raise ValueError(f"frame_signatures: frames of H * W = {H * W} pixels; the int32 counters hold fewer than 2^31")
-        self._chk(frames, None, "frame_signatures: frames")
-        if out is None:
-            out = torch.empty((T, 1024), dtype=torch.int32, device=self.device)
-        self._chk(out, torch.int32, "frame_signatures: out")
-        if tuple(out.shape) != (T, 1024):
-            raise ValueError(f"frame_signatures: out must be {(T, 1024)}, got {tuple(out.shape)}")
-        kind = 1 if frames.dtype == torch.float32 else 0                       # SVR_STORE_FP32 / SVR_STORE_BF16
+        T, H, W, Cn, kind = clip_args("frame_signatures", frames, self.device, min_hw=4, after=lambda T, H, W, _: (
+            f"frames of H * W = {H * W} pixels; the int32 counters hold fewer than 2^31" if H * W >= 1 << 31 else None))
+        out = self._out("frame_signatures", out, (T, 1024), torch.int32)
         hip_lib.check(self.lib.svr_frame_signatures(_ptr(frames), kind, T, H, W, Cn, _ptr(out), out.numel() * 4, self._stream()),
                       "svr_frame_signatures")
         return out
@@ -615,24 +636,14 @@ class HipOps:
         the specification, bit for bit; csrc/svr_active.hip): frames [T, H, W, 3 | 4] fp32 / bf16, dense, T * max(H, W) < 2^31,
         dark an integer in 0..255 -> int32 [H + W], rows first.  The call zeroes the result itself; one memset and one launch on
         the current stream, no host synchronisation.  ``out``: a dense int32 [H + W] tensor."""
-        if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
-            raise ValueError(f"active_profile: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
-        T, H, W, Cn = frames.shape
-        if Cn not in (3, 4):
-            raise ValueError(f"active_profile: frames must have C = 3 or 4, got C = {Cn}")
-        if T < 1 or H < 1 or W < 1:
-            raise ValueError(f"active_profile: frames must hold T >= 1 frames of H >= 1, W >= 1, got {tuple(frames.shape)}")
-        if T * max(H, W) >= 1 << 31:
-            raise ValueError(f"active_profile: frames of T * max(H, W) = {T * max(H, W)}; the int32 counters hold fewer than 2^31")
-        if isinstance(dark, bool) or not isinstance(dark, int) or not 0 <= dark <= 255:
-            raise ValueError(f"active_profile: dark must be an integer in 0..255, got {dark!r}")
-        self._chk(frames, None, "active_profile: frames")
-        if out is None:
-            out = torch.empty((H + W,), dtype=torch.int32, device=self.device)
-        self._chk(out, torch.int32, "active_profile: out")
-        if tuple(out.shape) != (H + W,):
-            raise ValueError(f"active_profile: out must be {(H + W,)}, got {tuple(out.shape)}")
-        kind = 1 if frames.dtype == torch.float32 else 0                       # SVR_STORE_FP32 / SVR_STORE_BF16
+        def counters_and_dark(T, H, W, _):
+            if T * max(H, W) >= 1 << 31:
+                return f"frames of T * max(H, W) = {T * max(H, W)}; the int32 counters hold fewer than 2^31"
+            if isinstance(dark, bool) or not isinstance(dark, int) or not 0 <= dark <= 255:
+                return f"dark must be an integer in 0..255, got {dark!r}"
+
+        T, H, W, Cn, kind = clip_args("active_profile", frames, self.device, min_hw=1, after=counters_and_dark)
+        out = self._out("active_profile", out, (H + W,), torch.int32)
         hip_lib.check(self.lib.svr_active_profile(_ptr(frames), kind, T, H, W, Cn, dark, _ptr(out), out.numel() * 4, self._stream()),
                       "svr_active_profile")
         return out
@@ -654,16 +665,8 @@ class HipOps:
         on the current stream, no host synchronisation.  ``out``: a dense uint8 [T, >= pngenc.frame_bound(H, W, C, depth)] tensor;
         ``sizes``: a dense int64 [T] tensor.  ``runs``: the stream with run-length matches (pngenc.encode_frames_spec(...,
         runs=True); svr_png_encode_runs, four launches) -- never longer than the literal one, and decoding to the same samples."""
-        if frames.dim() != 4 or frames.dtype not in (torch.float32, BF16):
-            raise ValueError(f"encode_png: frames must be [T, H, W, C] in fp32 or bf16, got {tuple(frames.shape)} {frames.dtype}")
-        T, H, W, Cn = frames.shape
-        if Cn not in (3, 4):
-            raise ValueError(f"encode_png: C must be 3 or 4, got C = {Cn}")
-        if depth not in (8, 16):
-            raise ValueError(f"encode_png: depth must be 8 or 16, got {depth}")
-        if T < 1 or H < 1 or W < 1:
-            raise ValueError(f"encode_png: frames must hold at least one pixel, got {tuple(frames.shape)}")
-        self._chk(frames, None, "encode_png: frames")
+        T, H, W, Cn, kind = clip_args("encode_png", frames, self.device, channels="C must be 3 or 4", before=lambda *_: (
+            None if depth in (8, 16) else f"depth must be 8 or 16, got {depth}"))
         nscratch, cap = self.encode_png_bytes(T, H, W, Cn, depth, runs)
         if out is None:
             out = torch.empty((T, cap), dtype=torch.uint8, device=self.device)
@@ -676,7 +679,6 @@ class HipOps:
         if tuple(sizes.shape) != (T,):
             raise ValueError(f"encode_png: sizes must be int64 [{T}], got {tuple(sizes.shape)}")
         scratch = torch.empty(nscratch, dtype=torch.uint8, device=self.device)
-        kind = 1 if frames.dtype == torch.float32 else 0                     # SVR_STORE_FP32 / SVR_STORE_BF16
         fn, name = (self.lib.svr_png_encode_runs, "svr_png_encode_runs") if runs else (self.lib.svr_png_encode, "svr_png_encode")
         hip_lib.check(fn(_ptr(frames), kind, T, H, W, Cn, int(depth), _ptr(scratch), nscratch, _ptr(out), out.shape[1], _ptr(sizes),
                          self._stream()), name)
@@ -690,7 +692,7 @@ class HipOps:
         if t.dim() != 4 or t.shape[1] != 3 or t.dtype != torch.float32 or (shape is not None and tuple(t.shape) != tuple(shape)):
             want = "[T, 3, H, W]" if shape is None else str(tuple(shape))
             raise ValueError(f"{name} must be fp32 {want}, got {t.dtype} {tuple(t.shape)}")
-        if t.device != self.device and not (t.device.type == "cuda" and t.device.index == (self.device.index or 0)):
+        if not on_device(t, self.device):
             raise ValueError(f"{name} must live on {self.device}, got {t.device}")
         if t.numel() == 0:
             raise ValueError(f"{name} must hold at least one pixel, got {tuple(t.shape)}")
@@ -914,11 +916,7 @@ class HipOps:
         except ValueError as e:
             raise ValueError(f"unpack_frames: {e}") from None
         self._chk(packed, None, "unpack_frames: packed")
-        if out is None:
-            out = torch.empty((T, H, W, C), dtype=torch.float32, device=self.device)
-        self._chk(out, torch.float32, "unpack_frames: out")
-        if tuple(out.shape) != (T, H, W, C):
-            raise ValueError(f"unpack_frames: out must be {(T, H, W, C)}, got {tuple(out.shape)}")
+        out = self._out("unpack_frames", out, (T, H, W, C), torch.float32)
         hip_lib.check(self.lib.svr_unpack_frames(_ptr(packed), packed.numel() * packed.element_size(), hip_lib.UNPACK_FORMATS[fmt],
                                                  T, H, W, C, hip_lib.YUV_MATRICES[matrix], hip_lib.YUV_RANGES[range_], _ptr(out),
                                                  out.numel() * out.element_size(), self._stream()), "svr_unpack_frames")
@@ -941,11 +939,7 @@ class HipOps:
             raise ValueError(f"dequant_gguf: blocks must hold whole {gguf.type_name(ggml_type)} blocks of {size} bytes, got "
                              f"{blocks.numel()} bytes")
         n = blocks.numel() // size
-        if out is None:
-            out = torch.empty((n, per), dtype=out_dtype, device=self.device)
-        self._chk(out, out_dtype, "dequant_gguf: out")
-        if tuple(out.shape) != (n, per):
-            raise ValueError(f"dequant_gguf: out must be {(n, per)}, got {tuple(out.shape)}")
+        out = self._out("dequant_gguf", out, (n, per), out_dtype)
         if blocks.data_ptr() % 32:
             blocks = blocks.clone()
         kind = 1 if out_dtype == torch.float32 else 0                        # SVR_STORE_FP32 / SVR_STORE_BF16
