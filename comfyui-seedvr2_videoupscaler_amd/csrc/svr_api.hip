@@ -26,6 +26,7 @@
 #include "svr_gguf.hip"
 #include "svr_shots.hip"
 #include "svr_active.hip"
+#include "svr_deinterlace.hip"
 
 using namespace svr;
 
@@ -1202,6 +1203,60 @@ int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int
         hipLaunchKernelGGL((unpack_rgb_kernel<1, CH()>), dim3(grid), dim3(256), 0, s, packed, out, n_units, n);
     });
     return e.launched();
+}
+
+// ---- interlaced sources made progressive on the packed planes (svr_deinterlace.hip): one launch per plane
+int svr_deinterlace(const void* packed, int64_t packed_bytes, const void* before, const void* after, int32_t fmt, int32_t T, int32_t H,
+                    int32_t W, int32_t C, int32_t order, int32_t rate, void* out, int64_t out_bytes, void* stream) {
+    const Launch e{"svr_deinterlace", stream};
+    const bool yuv = fmt == SVR_UNPACK_YUV420P8 || fmt == SVR_UNPACK_YUV420P10;
+    const bool wide = fmt == SVR_UNPACK_RGB16 || fmt == SVR_UNPACK_YUV420P10;          // 16-bit samples
+    const char* why = nullptr;
+    if (!packed) why = "packed is a null pointer";
+    else if (!out) why = "out is a null pointer";
+    else if (T < 1 || H < 1 || W < 1) why = "need T >= 1, H >= 1, W >= 1";
+    else if ((int64_t)H * W > ((int64_t)1 << 40) / T) why = "T * H * W must not exceed 2^40 pixels";
+    else if (fmt != SVR_UNPACK_RGB8 && fmt != SVR_UNPACK_BGR8 && fmt != SVR_UNPACK_RGB16 && !yuv)
+        why = "fmt must be SVR_UNPACK_RGB8, SVR_UNPACK_BGR8, SVR_UNPACK_RGB16, SVR_UNPACK_YUV420P8 or SVR_UNPACK_YUV420P10";
+    else if (yuv ? C != 3 : (C != 3 && C != 4)) why = yuv ? "C must be 3 for the yuv420p formats" : "C must be 3 or 4";
+    else if (order != SVR_FIELD_TFF && order != SVR_FIELD_BFF) why = "order must be SVR_FIELD_TFF or SVR_FIELD_BFF";
+    else if (rate != SVR_DEINT_FRAME && rate != SVR_DEINT_FIELD) why = "rate must be SVR_DEINT_FRAME or SVR_DEINT_FIELD";
+    else if (wide && (uintptr_t)packed % 2) why = "packed is not aligned to 2 bytes";
+    else if (wide && (uintptr_t)before % 2) why = "before is not aligned to 2 bytes";
+    else if (wide && (uintptr_t)after % 2) why = "after is not aligned to 2 bytes";
+    else if (wide && (uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
+    if (why) return e.refuse("%s", why);
+    const int size = wide ? 2 : 1;
+    const int64_t h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
+    const int64_t frame = yuv ? (int64_t)H * W + 2 * h2 * w2 : (int64_t)H * W * C;      // samples
+    const int64_t need_in = (int64_t)T * frame * size, need_out = need_in * (rate == SVR_DEINT_FIELD ? 2 : 1);
+    if (packed_bytes != need_in) return e.wrong_size("packed_bytes", packed_bytes, "the format needs", need_in);
+    if (out_bytes != need_out) return e.wrong_size("out_bytes", out_bytes, "the format and rate need", need_out);
+    if (rank_overlap(out, need_out, packed, need_in)) return e.refuse("out overlaps packed");
+    if (before && rank_overlap(out, need_out, before, frame * size)) return e.refuse("out overlaps before");
+    if (after && rank_overlap(out, need_out, after, frame * size)) return e.refuse("out overlaps after");
+    const bool aligned = (uintptr_t)packed % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)before % 16 == 0 &&
+                         (uintptr_t)after % 16 == 0 && frame * size % 16 == 0;
+    // the planes of a frame: offset, rows, samples per row, column step (deinterlace.planes)
+    struct Plane { int64_t off; int R, N, s; };
+    const Plane planes[3] = {{0, H, yuv ? W : W * C, yuv ? 1 : C}, {(int64_t)H * W, (int)h2, (int)w2, 1}, {(int64_t)H * W + h2 * w2, (int)h2, (int)w2, 1}};
+    const hipStream_t s = (hipStream_t)stream;
+    const int64_t n_out = (int64_t)T * (rate == SVR_DEINT_FIELD ? 2 : 1);
+    for (int pl = 0; pl < (yuv ? 3 : 1); ++pl) {
+        const Plane& p = planes[pl];
+        const bool vec = aligned && p.off * size % 16 == 0 && (int64_t)p.N * size % 16 == 0;       // every row starts on 16 bytes
+        const unsigned grid = capped_grid(n_out * p.R * (vec ? p.N / (16 / size) : p.N));
+        with_const<2, 1>(size, [&](auto BYTES) { with_const<SVR_DEINT_FIELD, SVR_DEINT_FRAME>(rate, [&](auto FIELD) {
+            typedef typename std::conditional<BYTES() == 2, unsigned short, unsigned char>::type S;
+            const DeintClip<S> clip{(const S*)packed, (const S*)before, (const S*)after, T, frame};
+            if (vec) with_const<4, 3, 1>(p.s, [&](auto STEP) {
+                hipLaunchKernelGGL((deint_vec_kernel<S, STEP(), FIELD()>), dim3(grid), dim3(256), 0, s, clip, (S*)out, p.off, p.R, p.N, order);
+            });
+            else hipLaunchKernelGGL((deint_elem_kernel<S, FIELD()>), dim3(grid), dim3(256), 0, s, clip, (S*)out, p.off, p.R, p.N, p.s, order);
+        }); });
+        if (int rc = e.launched()) return rc;
+    }
+    return 0;
 }
 
 // ---- GGUF blocks expanded at load (svr_gguf.hip)

@@ -22,6 +22,8 @@ EPI_BIAS, EPI_BIAS_SILU, EPI_RESID_GATE, EPI_SWIGLU, EPI_BIAS_GELU = 0, 1, 2, 3,
 ABI_VERSION = 9
 PACK_FORMATS = {"rgb8": 0, "bgr8": 1, "yuv420p10": 2}      # SVR_PACK_* (include/seedvr2_hip.h)
 UNPACK_FORMATS = {"rgb8": 0, "bgr8": 1, "yuv420p10": 2, "rgb16": 3, "yuv420p8": 4}      # SVR_UNPACK_*
+FIELD_ORDERS = {"tff": 0, "bff": 1}                        # SVR_FIELD_* (svr_deinterlace)
+DEINT_RATES = {"frame": 0, "field": 1}                     # SVR_DEINT_*
 YUV_MATRICES = {"bt709": 0, "bt601": 1}                    # SVR_MATRIX_*
 YUV_RANGES = {"tv": 0, "pc": 1}                            # SVR_RANGE_*
 COLOUR_MATRICES = {"bt709": 0, "bt601": 1, "bt2020": 2}    # SVR_COLOUR_MATRIX_* (svr_pack_yuv420p10 only)
@@ -125,6 +127,7 @@ SYMBOLS = {
     "svr_adaptive_blend": (C.c_int, [_vp, _strides, _vp, _strides, _vp, _strides, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _strides,
                                      _i32, _i32, _i32, _i32, _vp]),
     "svr_unpack_frames": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "svr_deinterlace": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_dequant_gguf": (C.c_int, [_vp, _i32, _i64, _vp, _i32, _i64, _vp]),
     "svr_set_option": (C.c_int, [C.c_char_p, _i32]),
     "svr_mfma_calibrate_workspace_bytes": (C.c_int64, []),

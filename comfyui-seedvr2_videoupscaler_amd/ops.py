@@ -922,6 +922,30 @@ class HipOps:
                                                  out.numel() * out.element_size(), self._stream()), "svr_unpack_frames")
         return out
 
+    # ------------------------------------------------------------------ interlaced sources
+    def deinterlace(self, packed, fmt, T, H, W, C, order, rate, before=None, after=None, out=None):
+        """Woven frames made progressive on the packed planes (deinterlace.py is the specification; csrc/svr_deinterlace.hip):
+        ``packed`` as unpack_frames takes it, ``order`` "tff" | "bff", ``rate`` "frame" | "field", ``before`` / ``after`` one packed
+        frame each or None (the clip is mirrored at that end) -> T or 2 T frames in the same dtype and layout.  One launch per plane
+        on the current stream, no host synchronisation.  ``out``: a dense tensor of exactly that shape and dtype, apart from every
+        input."""
+        from . import deinterlace
+        try:
+            shape = deinterlace.check_arguments(packed, fmt, T, H, W, C, order, rate, before, after)
+        except ValueError as e:
+            raise ValueError(f"deinterlace: {e}") from None
+        self._chk(packed, None, "deinterlace: packed")
+        for name, frame in (("before", before), ("after", after)):
+            if frame is not None:
+                self._chk(frame, None, f"deinterlace: {name}")
+        n_out = T * (2 if rate == "field" else 1)
+        out = self._out("deinterlace", out, (n_out,) + tuple(shape[1:]), packed.dtype)
+        hip_lib.check(self.lib.svr_deinterlace(_ptr(packed), packed.numel() * packed.element_size(), _ptr(before), _ptr(after),
+                                               hip_lib.UNPACK_FORMATS[fmt], T, H, W, C, hip_lib.FIELD_ORDERS[order],
+                                               hip_lib.DEINT_RATES[rate], _ptr(out), out.numel() * out.element_size(), self._stream()),
+                      "svr_deinterlace")
+        return out
+
     # ------------------------------------------------------------------ GGUF blocks expanded at load
     def dequant_gguf(self, blocks, ggml_type, out_dtype=BF16, out=None):
         """GGUF blocks expanded on the device (gguf.py is the specification, bit for bit; csrc/svr_gguf.hip): ``blocks`` a dense uint8

@@ -66,6 +66,9 @@
  *                                              where frames is 16-byte aligned, element accesses otherwise
  *   svr_active_profile                         as svr_frame_signatures (frames 4 / 2 bytes, out 4; 16-byte loads where frames is
  *                                              16-byte aligned, element accesses otherwise)
+ *   svr_deinterlace                            element alignment is enough (2 bytes for the 16-bit formats); per plane, 16-byte loads and
+ *                                              stores where packed, before, after and out are 16-byte aligned and the frame, the
+ *                                              plane's offset and its rows are multiples of 16 bytes, element accesses otherwise
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -103,6 +106,8 @@ extern "C" {
  * symbol only.
  * v9, additive: + svr_active_profile() (per row and per column the number of pixels brighter than a threshold: what finds the bars
  * of a letterboxed clip).  A new symbol only.
+ * v9, additive: + svr_deinterlace() (the woven frames of an interlaced source made progressive on the packed planes, before
+ * svr_unpack_frames widens them).  A new symbol only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -591,6 +596,27 @@ int svr_adaptive_blend(const void* base, const int64_t* base_strides, const void
 #define SVR_RANGE_PC 1
 int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,
                       int32_t matrix, int32_t range, float* out, int64_t out_bytes, void* stream);
+
+/* ---- interlaced sources ------------------------------------------------------------------------ */
+/* deinterlace.py (the specification, bit for bit): `packed` T woven frames in one of the SVR_UNPACK_* formats (same layouts and
+ * element types as svr_unpack_frames takes) -> `out` T (SVR_DEINT_FRAME) or 2 T (SVR_DEINT_FIELD) progressive frames in the same
+ * format.  Per plane -- the one plane of the RGB formats, whose channels lie C elements apart, or Y, Cb and Cr each with its own
+ * rows -- the rows of the kept field are copied and the others are computed by a motion-adaptive, edge-directed rule in exact
+ * integers (temporal average of the neighbouring fields of the missing parity, clamped around it by the largest of three temporal
+ * differences; the spatial prediction searches five directions).  `order`: SVR_FIELD_TFF the first field in time is the even rows,
+ * SVR_FIELD_BFF the odd ones.  SVR_DEINT_FRAME keeps the first field of every frame; SVR_DEINT_FIELD gives output 2 t the first and
+ * output 2 t + 1 the second field of frame t.  `before` / `after`: one packed frame each, the frame ahead of the clip and the one
+ * behind it, or NULL: the clip is then mirrored at that end (F[-1] = F[min(1, T-1)], F[T] = F[max(T-2, 0)]).
+ * Every argument is checked before the first launch: null packed / out, an unknown fmt, order or rate, a C the format does not
+ * take, sizes below 1 (T * H * W <= 2^40 pixels), packed_bytes and out_bytes other than EXACTLY the format's sizes, a pointer not
+ * aligned to its element, out overlapping packed, before or after.  One launch per plane on `stream`, no host synchronisation, no
+ * workspace. */
+#define SVR_FIELD_TFF 0
+#define SVR_FIELD_BFF 1
+#define SVR_DEINT_FRAME 0
+#define SVR_DEINT_FIELD 1
+int svr_deinterlace(const void* packed, int64_t packed_bytes, const void* before, const void* after, int32_t fmt, int32_t T, int32_t H,
+                    int32_t W, int32_t C, int32_t order, int32_t rate, void* out, int64_t out_bytes, void* stream);
 
 /* ---- GGUF block-quantised weights, expanded at load ------------------------------------------- */
 /* gguf.py (the specification, bit for bit): `n_blocks` consecutive blocks of one ggml type -> n_blocks * block size values, each

@@ -34,7 +34,13 @@ two parsers by ``ast``), so existing scripts keep working.  What the flags DO is
   * the active picture area has no flag either: where active.ENABLED is set (it ships off) and one GPU does the
     work, the black bars of a letterboxed or pillarboxed clip are found on the device (active.py / csrc/svr_active.hip), only the
     picture goes through the model and the bars are a plain resize (``pipeline.upscale(area=...)``), per clip, per shot and per
-    --chunk_size chunk.
+    --chunk_size chunk;
+  * interlaced sources have no flag either: where deinterlace.ENABLED is set (it ships off) and ffprobe's
+    field_order tag names an order, FrameSource makes the woven frames progressive on the device, on the packed planes, between the
+    upload and the unpack (deinterlace.py / csrc/svr_deinterlace.hip), at deinterlace.RATE: "field" gives two frames per source
+    frame and the writer twice the source's frame rate.  --skip_first_frames, --load_cap and --chunk_size count SOURCE frames;
+    --batch_size and --temporal_overlap count the frames the model sees.  With the switch off a source tagged interlaced is
+    upscaled as stored, which is said once per job.  ffmpeg backend only.
 """
 import argparse
 import json
@@ -114,6 +120,27 @@ def active_rule(rank: int, world: int) -> dict:
         _active_warned = True
         return {}
     return {"area": active.Rule(**active.DEFAULTS)}
+
+
+def _deinterlace():
+    import importlib
+    return importlib.import_module(f"{PKG}.deinterlace")
+
+
+def source_fields(tag, rank: int):
+    """ffprobe's field_order tag -> FrameSource's ``fields``: (order, deinterlace.RATE) where the tag names an order and
+    deinterlace.ENABLED is set, else None -- with one warning line on rank 0 where the tag says interlaced and the switch is off
+    (the shipped state): the frames are then upscaled as stored."""
+    deinterlace = _deinterlace()
+    order = deinterlace.field_order(tag)
+    if order is None:
+        return None
+    if not deinterlace.ENABLED:
+        if rank == 0:
+            print(f"Warning: the source is tagged interlaced (field_order {tag}); deinterlacing is off, the frames are upscaled as stored",
+                  file=sys.stderr)
+        return None
+    return order, deinterlace.RATE
 
 
 def output_depth(inp: str, info: Optional[dict] = None) -> int:
@@ -329,9 +356,9 @@ def _tail(errlog) -> str:
 COLOUR_FIELDS = ("color_space", "color_primaries", "color_transfer", "color_range", "chroma_location")
 
 
-def probe_source(ffprobe: str, path: str):
-    """One ffprobe run (JSON) -> (probe_video's dictionary, probe_colour's dictionary) of the FIRST video stream -- the one
-    FrameSource maps."""
+def probe_stream(ffprobe: str, path: str):
+    """One ffprobe run (JSON) -> (the FIRST video stream's dictionary as ffprobe wrote it -- the stream FrameSource maps --, the
+    list of all streams)."""
     r = subprocess.run([ffprobe, "-v", "error", "-print_format", "json", "-show_streams", path], stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE)
     if r.returncode != 0:
@@ -340,7 +367,11 @@ def probe_source(ffprobe: str, path: str):
     video = [st for st in streams if st.get("codec_type") == "video"]
     if not video:
         raise ValueError(f"{path}: ffprobe found no video stream")
-    v = video[0]
+    return video[0], streams
+
+
+def source_tags(v: dict, streams: list):
+    """probe_stream's answer -> (probe_video's dictionary, probe_colour's dictionary)"""
     fps = Fraction(30)
     for key in ("r_frame_rate", "avg_frame_rate"):
         try:
@@ -354,6 +385,11 @@ def probe_source(ffprobe: str, path: str):
     info = dict(width=int(v["width"]), height=int(v["height"]), fps=fps, pix_fmt=v.get("pix_fmt"), color_space=named("color_space"),
                 color_range=named("color_range"), has_audio=any(st.get("codec_type") == "audio" for st in streams))
     return info, {key: named(key) for key in COLOUR_FIELDS}
+
+
+def probe_source(ffprobe: str, path: str):
+    """One ffprobe run -> (probe_video's dictionary, probe_colour's dictionary) of the first video stream."""
+    return source_tags(*probe_stream(ffprobe, path))
 
 
 def probe_video(ffprobe: str, path: str) -> dict:
@@ -432,9 +468,17 @@ class FrameSource:
     widens them with frameio_in.unpack_frames(..., ops): [t <= chunk_size, H, W, 3 | 4] fp32 tensors already on the device, which
     pipeline.upscale_stream takes as they are.  ``skip`` frames are read and dropped, after ``cap`` frames the child is
     terminated; a short last chunk and an empty stream behave as in open_chunks; a child that exits non-zero raises with the tail
-    of its stderr.  ``exe``: the executable (find_ffmpeg(), resolved before any GPU work; a test passes its own)."""
+    of its stderr.  ``exe``: the executable (find_ffmpeg(), resolved before any GPU work; a test passes its own).
 
-    def __init__(self, exe: str, path: str, info: dict, chunk_size: int, skip: int = 0, cap: int = 0, ops=None, device="cpu"):
+    ``fields`` = (order, rate) (source_fields): an interlaced source.  The decoder's command is the same; ``chunks()`` makes the woven
+    frames progressive on the packed bytes, between the upload and the unpack (deinterlace.py / csrc/svr_deinterlace.hip), with
+    the previous buffer's last frame and the NEXT buffer's first frame as context -- so it stays one buffer ahead: buffer k + 1 is
+    uploaded and its host slot handed back to the reader thread before buffer k is deinterlaced, at the cost of one more packed
+    chunk on the device.  The chunks, concatenated, are deinterlace_torch of the whole clip followed by unpack_frames_torch, for
+    any chunk size; a chunk has as many frames as were read, twice that at rate "field", where ``fps`` doubles too."""
+
+    def __init__(self, exe: str, path: str, info: dict, chunk_size: int, skip: int = 0, cap: int = 0, ops=None, device="cpu",
+                 fields=None):
         import importlib
         import tempfile
         import torch
@@ -443,6 +487,14 @@ class FrameSource:
         self.frameio_in = importlib.import_module(f"{PKG}.frameio_in")
         self.raw, self.fmt, self.C, self.matrix, self.range_ = route_input(info)
         self.H, self.W, self.fps = info["height"], info["width"], info["fps"]
+        self.fields = fields
+        if fields is not None:
+            self.deinterlace = _deinterlace()
+            order, rate = fields
+            if order not in self.deinterlace.ORDERS or rate not in self.deinterlace.RATES:
+                raise ValueError(f"fields must be (one of {self.deinterlace.ORDERS}, one of {self.deinterlace.RATES}), got {fields!r}")
+            if rate == "field":
+                self.fps = 2 * Fraction(info["fps"])
         self.chunk_size, self.skip, self.cap, self.ops, self.device = chunk_size, skip, cap, ops, torch.device(device)
         self.frame_bytes = self.frameio_in.frame_bytes(self.H, self.W, self.C, self.fmt)
         pinned = self.device.type == "cuda"
@@ -503,28 +555,57 @@ class FrameSource:
         except BaseException as e:                               # noqa: BLE001 (handed to the caller's thread)
             self.work.put(e)
 
-    def chunks(self):
-        import torch
+    def _uploads(self):
+        """the buffers the reader filled, in order: (packed samples where the frames are wanted, frames); the host slot is free
+        again when one is yielded"""
         first = True
+        while True:
+            item = self.work.get()
+            if isinstance(item, RuntimeError):                   # (the decoder's own failure: its message as it is)
+                raise item
+            if isinstance(item, BaseException):
+                raise RuntimeError(f"reading frames failed: {type(item).__name__}: {item}") from item
+            if item is None:
+                if first:
+                    raise ValueError("No frames to process")
+                return
+            slot, t = item
+            first = False
+            host = self.buffers[slot][:t * self.frame_bytes]
+            packed = host.to(self.device) if self.device.type == "cuda" else host.clone()         # (returns when the bytes are there)
+            self.free.put(slot)
+            ready = [packed.view(self.frameio_in.packed_dtype(self.fmt))]
+            del packed, host                                     # (the caller's reference is the only one while this waits for the next)
+            yield ready.pop(), t
+
+    def _unpack(self, packed, t):
+        return self.frameio_in.unpack_frames(packed, self.fmt, t, self.H, self.W, self.C, self.matrix, self.range_, ops=self.ops)
+
+    def _progressive(self, packed, t, before, after):
+        """buffer ``packed`` of t woven frames between its neighbours' frames -> the fp32 frames of its T or 2 T outputs"""
+        order, rate = self.fields
+        if t == 1:                                               # nothing of its own to mirror at an end of the clip: the clip's mirror
+            before, after = (after if before is None else before), (before if after is None else after)
+        frames = self.deinterlace.deinterlace(packed, self.fmt, t, self.H, self.W, self.C, order, rate, before=before, after=after,
+                                              ops=self.ops)
+        return self._unpack(frames.reshape(-1), t * (2 if rate == "field" else 1))
+
+    def chunks(self):
         try:
-            while True:
-                item = self.work.get()
-                if isinstance(item, RuntimeError):               # (the decoder's own failure: its message as it is)
-                    raise item
-                if isinstance(item, BaseException):
-                    raise RuntimeError(f"reading frames failed: {type(item).__name__}: {item}") from item
-                if item is None:
-                    if first:
-                        raise ValueError("No frames to process")
-                    return
-                slot, t = item
-                first = False
-                host = self.buffers[slot][:t * self.frame_bytes]
-                packed = host.to(self.device) if self.device.type == "cuda" else host.clone()     # (returns when the bytes are there)
-                self.free.put(slot)
-                packed = packed.view(self.frameio_in.packed_dtype(self.fmt))
-                yield self.frameio_in.unpack_frames(packed, self.fmt, t, self.H, self.W, self.C, self.matrix, self.range_, ops=self.ops)
+            if self.fields is None:
+                for packed, t in self._uploads():
+                    yield self._unpack(packed, t)
+                    del packed
+                return
+            held, before = None, None                            # the buffer waiting for its successor; the last frame ahead of it
+            for packed, t in self._uploads():
+                packed = packed.reshape(t, -1)
+                if held is not None:
+                    yield self._progressive(held, held.shape[0], before, packed[0])
+                    before = held[-1].clone()                    # (a copy of one frame: the buffer itself goes)
+                held = packed
                 del packed
+            yield self._progressive(held, held.shape[0], before, None)
         finally:
             self.close()
 
@@ -996,9 +1077,11 @@ def main(argv: Optional[List[str]] = None) -> int:
     writer_kw = dict(video_backend=args.video_backend, ten_bit=args.use_10bit and args.video_backend == "ffmpeg", ffmpeg=ffmpeg)
     for inp in jobs:                                   # the engines stay resident between jobs (interfaces.get_runner)
         fmt = fmt_of(inp)
-        info, colour = probe_source(ffprobe, inp) if via_ffmpeg(inp) else (None, None)      # (before the engines: a file ffprobe refuses costs no model load)
+        probed = probe_stream(ffprobe, inp) if via_ffmpeg(inp) else None      # (before the engines: a file ffprobe refuses costs no model load)
+        info, colour = source_tags(*probed) if probed else (None, None)
         eng = engines(args)
         rank, ops = eng[3], getattr(eng[0].dit, "ops", None)    # (the runner's backend also narrows the frames for the writers)
+        fields = source_fields(probed[0].get("field_order"), rank) if probed else None         # an interlaced source
         job_kw = dict(writer_kw)
         if fmt == "png":                               # a source deeper than 8 bits leaves as 16-bit files
             job_kw["depth"] = output_depth(inp, info)
@@ -1010,11 +1093,12 @@ def main(argv: Optional[List[str]] = None) -> int:
                 print(warning, file=sys.stderr)
             if out_colour is not None:
                 job_kw["colour"] = out_colour
-        source = lambda n: FrameSource(ffmpeg, inp, info, n, args.skip_first_frames, args.load_cap, ops, eng[0].dit.device)
+        source = lambda n: FrameSource(ffmpeg, inp, info, n, args.skip_first_frames, args.load_cap, ops, eng[0].dit.device, fields)
         if args.chunk_size > 0 and ext_of(inp) not in IMAGE_EXT:
             # streaming: read, upscale, pack and write --chunk_size frames at a time
             if info is not None:
-                chunks, fps = source(args.chunk_size).chunks(), info["fps"]
+                src = source(args.chunk_size)
+                chunks, fps = src.chunks(), src.fps              # (info["fps"]; twice that where fields come out as frames)
             else:
                 chunks, fps = open_chunks(inp, args.chunk_size, args.skip_first_frames, args.load_cap)
             path = output_path(args, inp, fmt, len(jobs), single=False)
@@ -1038,7 +1122,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             continue
         if info is not None:                           # the whole clip, read in chunks and concatenated on the device
             import torch
-            frames, fps = torch.cat(list(source(WHOLE_CLIP_READ_FRAMES).chunks())), info["fps"]
+            src = source(WHOLE_CLIP_READ_FRAMES)
+            frames, fps = torch.cat(list(src.chunks())), src.fps
         else:
             frames, fps = load_frames(inp, args.skip_first_frames, args.load_cap)
         out, rank = run(args, frames, eng)
