@@ -27,6 +27,7 @@
 #include "svr_shots.hip"
 #include "svr_active.hip"
 #include "svr_deinterlace.hip"
+#include "svr_fieldmatch.hip"
 
 using namespace svr;
 
@@ -1253,6 +1254,140 @@ int svr_deinterlace(const void* packed, int64_t packed_bytes, const void* before
                 hipLaunchKernelGGL((deint_vec_kernel<S, STEP(), FIELD()>), dim3(grid), dim3(256), 0, s, clip, (S*)out, p.off, p.R, p.N, order);
             });
             else hipLaunchKernelGGL((deint_elem_kernel<S, FIELD()>), dim3(grid), dim3(256), 0, s, clip, (S*)out, p.off, p.R, p.N, p.s, order);
+        }); });
+        if (int rc = e.launched()) return rc;
+    }
+    return 0;
+}
+
+// ---- field matching on the packed planes (svr_fieldmatch.hip).  What its two entry points share with svr_deinterlace: the formats,
+// the frame's size and planes, the refusals of the clip's own arguments
+struct FieldClip {
+    bool yuv, wide;
+    int size;                                           // bytes per sample
+    int64_t h2, w2, frame;                              // chroma rows and columns; samples per frame
+    struct Plane { int64_t off; int R; int64_t N; int s; } planes[3];
+    int n_planes;
+};
+static const char* field_clip_error(const void* packed, const void* before, const void* after, int32_t fmt, int32_t T, int32_t H,
+                                    int32_t W, int32_t C, int32_t order) {
+    const bool yuv = fmt == SVR_UNPACK_YUV420P8 || fmt == SVR_UNPACK_YUV420P10;
+    const bool wide = fmt == SVR_UNPACK_RGB16 || fmt == SVR_UNPACK_YUV420P10;
+    if (T < 1 || H < 1 || W < 1) return "need T >= 1, H >= 1, W >= 1";
+    if ((int64_t)H * W > ((int64_t)1 << 40) / T) return "T * H * W must not exceed 2^40 pixels";
+    if (fmt != SVR_UNPACK_RGB8 && fmt != SVR_UNPACK_BGR8 && fmt != SVR_UNPACK_RGB16 && !yuv)
+        return "fmt must be SVR_UNPACK_RGB8, SVR_UNPACK_BGR8, SVR_UNPACK_RGB16, SVR_UNPACK_YUV420P8 or SVR_UNPACK_YUV420P10";
+    if (yuv ? C != 3 : (C != 3 && C != 4)) return yuv ? "C must be 3 for the yuv420p formats" : "C must be 3 or 4";
+    if (order != SVR_FIELD_TFF && order != SVR_FIELD_BFF) return "order must be SVR_FIELD_TFF or SVR_FIELD_BFF";
+    if (wide && (uintptr_t)packed % 2) return "packed is not aligned to 2 bytes";
+    if (wide && (uintptr_t)before % 2) return "before is not aligned to 2 bytes";
+    if (wide && (uintptr_t)after % 2) return "after is not aligned to 2 bytes";
+    return nullptr;
+}
+static FieldClip field_clip(int32_t fmt, int32_t H, int32_t W, int32_t C) {
+    FieldClip c;
+    c.yuv = fmt == SVR_UNPACK_YUV420P8 || fmt == SVR_UNPACK_YUV420P10;
+    c.wide = fmt == SVR_UNPACK_RGB16 || fmt == SVR_UNPACK_YUV420P10;
+    c.size = c.wide ? 2 : 1;
+    c.h2 = ((int64_t)H + 1) / 2, c.w2 = ((int64_t)W + 1) / 2;
+    c.frame = c.yuv ? (int64_t)H * W + 2 * c.h2 * c.w2 : (int64_t)H * W * C;
+    c.planes[0] = {0, H, c.yuv ? (int64_t)W : (int64_t)W * C, c.yuv ? 1 : C};
+    c.planes[1] = {(int64_t)H * W, (int)c.h2, c.w2, 1};
+    c.planes[2] = {(int64_t)H * W + c.h2 * c.w2, (int)c.h2, c.w2, 1};
+    c.n_planes = c.yuv ? 3 : 1;
+    return c;
+}
+
+int svr_comb_counts(const void* packed, int64_t packed_bytes, const void* before, const void* after, int32_t fmt, int32_t T, int32_t H,
+                    int32_t W, int32_t C, int32_t order, int32_t thr, void* cnt, int64_t cnt_bytes, void* stream) {
+    const Launch e{"svr_comb_counts", stream};
+    const char* why = nullptr;
+    if (!packed) why = "packed is a null pointer";
+    else if (!cnt) why = "cnt is a null pointer";
+    else if ((why = field_clip_error(packed, before, after, fmt, T, H, W, C, order))) {}
+    else if ((int64_t)H * W * C > ((int64_t)1 << 31)) why = "H * W * C must not exceed 2^31 samples (the counters are int32)";
+    else if (thr < 0 || thr > 255) why = "thr must lie in 0..255";
+    else if ((uintptr_t)cnt % 4) why = "cnt is not aligned to 4 bytes";
+    if (why) return e.refuse("%s", why);
+    const FieldClip c = field_clip(fmt, H, W, C);
+    const int64_t need_in = (int64_t)T * c.frame * c.size, need_cnt = (int64_t)T * 24;
+    if (packed_bytes != need_in) return e.wrong_size("packed_bytes", packed_bytes, "the format needs", need_in);
+    if (cnt_bytes != need_cnt) return e.wrong_size("cnt_bytes", cnt_bytes, "int32 [T, 3, 2] needs", need_cnt);
+    if (rank_overlap(cnt, need_cnt, packed, need_in)) return e.refuse("cnt overlaps packed");
+    if (before && rank_overlap(cnt, need_cnt, before, c.frame * c.size)) return e.refuse("cnt overlaps before");
+    if (after && rank_overlap(cnt, need_cnt, after, c.frame * c.size)) return e.refuse("cnt overlaps after");
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = e.hip(hipMemsetAsync(cnt, 0, (size_t)need_cnt, s), "zeroing cnt")) return rc;
+    const FieldClip::Plane& p = c.planes[0];
+    if (p.R < 3) return 0;                                                   // no tested row: the counts are zero
+    const bool vec = (uintptr_t)packed % 16 == 0 && (uintptr_t)before % 16 == 0 && (uintptr_t)after % 16 == 0 &&
+                     c.frame * c.size % 16 == 0 && p.N * c.size % 16 == 0;
+    const int unit = vec ? 16 / c.size : 1;                                  // samples per lane column
+    const int per = FM_BLOCK * p.s / unit, cb = FM_LANES / per;              // lanes per block column, block columns per workgroup
+    const int64_t block_cols = (p.N / p.s + FM_BLOCK - 1) / FM_BLOCK;
+    const int chunks = (int)((block_cols + cb - 1) / cb);
+    const int thr_code = thr << (fmt == SVR_UNPACK_RGB16 ? 8 : fmt == SVR_UNPACK_YUV420P10 ? 2 : 0);
+    const unsigned grid = capped_grid((int64_t)T * ((p.R + FM_BLOCK - 1) / FM_BLOCK) * chunks * 256);
+    with_const<2, 1>(c.size, [&](auto BYTES) { with_const<1, 0>(vec ? 1 : 0, [&](auto VEC) {
+        typedef typename std::conditional<BYTES() == 2, unsigned short, unsigned char>::type S;
+        const DeintClip<S> clip{(const S*)packed, (const S*)before, (const S*)after, T, c.frame};
+        hipLaunchKernelGGL((comb_kernel<S, VEC()>), dim3(grid), dim3(FM_LANES), 0, s, clip, p.R, p.N, per, cb, chunks, p.N / unit, order,
+                           thr_code, (int*)cnt);
+    }); });
+    return e.launched();
+}
+
+int svr_field_select(const void* packed, int64_t packed_bytes, const void* before, const void* after, const void* deint,
+                     int64_t deint_bytes, const void* cnt, int64_t cnt_bytes, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,
+                     int32_t order, int32_t mi, void* out, int64_t out_bytes, void* modes, void* stats, void* stream) {
+    const Launch e{"svr_field_select", stream};
+    const bool wide = fmt == SVR_UNPACK_RGB16 || fmt == SVR_UNPACK_YUV420P10;
+    const char* why = nullptr;
+    if (!packed) why = "packed is a null pointer";
+    else if (!deint) why = "deint is a null pointer";
+    else if (!cnt) why = "cnt is a null pointer";
+    else if (!out) why = "out is a null pointer";
+    else if ((why = field_clip_error(packed, before, after, fmt, T, H, W, C, order))) {}
+    else if (mi < 0) why = "mi must not be negative";
+    else if (wide && (uintptr_t)deint % 2) why = "deint is not aligned to 2 bytes";
+    else if (wide && (uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
+    else if ((uintptr_t)cnt % 4) why = "cnt is not aligned to 4 bytes";
+    else if ((uintptr_t)modes % 4) why = "modes is not aligned to 4 bytes";
+    else if ((uintptr_t)stats % 8) why = "stats is not aligned to 8 bytes";
+    if (why) return e.refuse("%s", why);
+    const FieldClip c = field_clip(fmt, H, W, C);
+    const int64_t need = (int64_t)T * c.frame * c.size, need_cnt = (int64_t)T * 24, one = c.frame * c.size;
+    if (packed_bytes != need) return e.wrong_size("packed_bytes", packed_bytes, "the format needs", need);
+    if (deint_bytes != need) return e.wrong_size("deint_bytes", deint_bytes, "the format needs", need);
+    if (cnt_bytes != need_cnt) return e.wrong_size("cnt_bytes", cnt_bytes, "int32 [T, 3, 2] needs", need_cnt);
+    if (out_bytes != need) return e.wrong_size("out_bytes", out_bytes, "the format needs", need);
+    // no output may overlap an input, or another output
+    struct Span { const char* name; const void* at; int64_t bytes; };
+    const Span inputs[] = {{"packed", packed, need}, {"before", before, one}, {"after", after, one}, {"deint", deint, need}, {"cnt", cnt, need_cnt}};
+    const Span outputs[] = {{"out", out, need}, {"modes", modes, (int64_t)T * 4}, {"stats", stats, 48}};
+    for (int o = 0; o < 3; ++o) {
+        if (!outputs[o].at) continue;
+        for (const Span& in : inputs)
+            if (in.at && rank_overlap(outputs[o].at, outputs[o].bytes, in.at, in.bytes)) return e.refuse("%s overlaps %s", outputs[o].name, in.name);
+        for (int q = 0; q < o; ++q)
+            if (outputs[q].at && rank_overlap(outputs[o].at, outputs[o].bytes, outputs[q].at, outputs[q].bytes))
+                return e.refuse("%s overlaps %s", outputs[o].name, outputs[q].name);
+    }
+    const bool aligned = (uintptr_t)packed % 16 == 0 && (uintptr_t)out % 16 == 0 && (uintptr_t)before % 16 == 0 &&
+                         (uintptr_t)after % 16 == 0 && (uintptr_t)deint % 16 == 0 && one % 16 == 0;
+    const int64_t bound = (int64_t)mi * c.planes[0].s;
+    const hipStream_t s = (hipStream_t)stream;
+    for (int pl = 0; pl < c.n_planes; ++pl) {
+        const FieldClip::Plane& p = c.planes[pl];
+        const bool vec = aligned && p.off * c.size % 16 == 0 && p.N * c.size % 16 == 0;            // every row starts on 16 bytes
+        const int64_t cols = vec ? p.N / (16 / c.size) : p.N;
+        const unsigned grid = capped_grid((int64_t)T * p.R * cols);
+        with_const<2, 1>(c.size, [&](auto BYTES) { with_const<1, 0>(vec ? 1 : 0, [&](auto VEC) {
+            typedef typename std::conditional<BYTES() == 2, unsigned short, unsigned char>::type S;
+            const DeintClip<S> clip{(const S*)packed, (const S*)before, (const S*)after, T, c.frame};
+            hipLaunchKernelGGL((select_kernel<S, VEC()>), dim3(grid), dim3(FM_LANES), 0, s, clip, (const S*)deint, (const int*)cnt, bound,
+                               (S*)out, p.off, p.R, p.N, cols, order, pl == 0 ? 1 : 0, pl == 0 ? (int*)modes : nullptr,
+                               pl == 0 ? (unsigned long long*)stats : nullptr);
         }); });
         if (int rc = e.launched()) return rc;
     }

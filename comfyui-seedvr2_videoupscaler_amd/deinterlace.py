@@ -55,6 +55,8 @@ Known limits:
   * no telecine / pulldown handling: 3:2 material comes out with its repeated fields interpolated, not matched;
   * a one-frame clip has no temporal neighbour but itself and comes back woven;
   * the field order is taken for the whole clip; a stream that changes order midway is not followed.
+fieldmatch.py answers the first two: it counts the combing of every stored frame and hands only the frames without a clean weave to
+the rule above.
 """
 import torch
 

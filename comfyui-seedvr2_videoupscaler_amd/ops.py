@@ -946,6 +946,58 @@ class HipOps:
                       "svr_deinterlace")
         return out
 
+    # ------------------------------------------------------------------ field matching
+    def comb_counts(self, packed, fmt, T, H, W, C, order, thr, before=None, after=None, out=None):
+        """Per frame the combing of the three weaves its kept field can make (fieldmatch.py is the specification;
+        csrc/svr_fieldmatch.hip): ``packed``, ``before`` / ``after`` and ``order`` as deinterlace takes them, ``thr`` in 0..255 ->
+        int32 [T, 3, 2]: (total, peak) of the candidates cur, prev, next.  The counts are zeroed and one kernel is launched on the
+        current stream, no host synchronisation.  ``out``: a dense int32 [T, 3, 2] tensor apart from every input."""
+        from . import fieldmatch
+        try:
+            fieldmatch.check_arguments(packed, fmt, T, H, W, C, order, thr, before, after)
+        except ValueError as e:
+            raise ValueError(f"comb_counts: {e}") from None
+        self._chk(packed, None, "comb_counts: packed")
+        for name, frame in (("before", before), ("after", after)):
+            if frame is not None:
+                self._chk(frame, None, f"comb_counts: {name}")
+        out = self._out("comb_counts", out, (T, 3, 2), torch.int32)
+        hip_lib.check(self.lib.svr_comb_counts(_ptr(packed), packed.numel() * packed.element_size(), _ptr(before), _ptr(after),
+                                               hip_lib.UNPACK_FORMATS[fmt], T, H, W, C, hip_lib.FIELD_ORDERS[order], thr, _ptr(out),
+                                               out.numel() * 4, self._stream()), "svr_comb_counts")
+        return out
+
+    def field_select(self, packed, deint, cnt, fmt, T, H, W, C, order, mi, before=None, after=None, out=None, modes=None, stats=None):
+        """The progressive frames field matching chooses (fieldmatch.select_torch of fieldmatch.modes_torch(cnt, mi, s);
+        csrc/svr_fieldmatch.hip): ``deint`` the clip deinterlaced at rate "frame", ``cnt`` comb_counts' int32 [T, 3, 2], both read on
+        the device in stream order; ``mi`` >= 0 -> T frames in packed's dtype and layout.  ``modes`` int32 [T] receives the modes,
+        ``stats`` int64 [6] (fieldmatch.Stats.counts) is added to; both may be None.  One launch per plane on the current stream, no
+        host synchronisation.  ``out``: a dense tensor of packed's shape and dtype, apart from every input."""
+        from . import deinterlace, fieldmatch
+        try:
+            shape = deinterlace.check_arguments(packed, fmt, T, H, W, C, order, "frame", before, after)
+            fieldmatch.check_mi(mi)
+        except ValueError as e:
+            raise ValueError(f"field_select: {e}") from None
+        self._chk(packed, None, "field_select: packed")
+        for name, frame in (("before", before), ("after", after)):
+            if frame is not None:
+                self._chk(frame, None, f"field_select: {name}")
+        self._chk(deint, packed.dtype, "field_select: deint")
+        if deint.numel() != packed.numel():
+            raise ValueError(f"field_select: deint must hold the {packed.numel()} samples of packed, got {tuple(deint.shape)}")
+        self._chk(cnt, torch.int32, "field_select: cnt")
+        if tuple(cnt.shape) != (T, 3, 2):
+            raise ValueError(f"field_select: cnt must be {(T, 3, 2)}, got {tuple(cnt.shape)}")
+        out = self._out("field_select", out, tuple(shape), packed.dtype)
+        hip_lib.check(self.lib.svr_field_select(_ptr(packed), packed.numel() * packed.element_size(), _ptr(before), _ptr(after),
+                                                _ptr(deint), deint.numel() * deint.element_size(), _ptr(cnt), cnt.numel() * 4,
+                                                hip_lib.UNPACK_FORMATS[fmt], T, H, W, C, hip_lib.FIELD_ORDERS[order], mi, _ptr(out),
+                                                out.numel() * out.element_size(), self._opt(modes, torch.int32, "field_select: modes", T),
+                                                self._opt(stats, torch.int64, "field_select: stats", 6), self._stream()),
+                      "svr_field_select")
+        return out
+
     # ------------------------------------------------------------------ GGUF blocks expanded at load
     def dequant_gguf(self, blocks, ggml_type, out_dtype=BF16, out=None):
         """GGUF blocks expanded on the device (gguf.py is the specification, bit for bit; csrc/svr_gguf.hip): ``blocks`` a dense uint8

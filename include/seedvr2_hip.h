@@ -69,6 +69,11 @@
  *   svr_deinterlace                            element alignment is enough (2 bytes for the 16-bit formats); per plane, 16-byte loads and
  *                                              stores where packed, before, after and out are 16-byte aligned and the frame, the
  *                                              plane's offset and its rows are multiples of 16 bytes, element accesses otherwise
+ *   svr_comb_counts                            element alignment is enough (2 bytes for the 16-bit formats, cnt 4); 16-byte loads where
+ *                                              packed, before and after are 16-byte aligned and the frame and plane 0's rows are
+ *                                              multiples of 16 bytes, element accesses otherwise
+ *   svr_field_select                           as svr_deinterlace, deint counting as an input (cnt and modes 4, stats 8); per plane,
+ *                                              16-byte loads and stores or element accesses by svr_deinterlace's rule
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -108,6 +113,8 @@ extern "C" {
  * of a letterboxed clip).  A new symbol only.
  * v9, additive: + svr_deinterlace() (the woven frames of an interlaced source made progressive on the packed planes, before
  * svr_unpack_frames widens them).  A new symbol only.
+ * v9, additive: + svr_comb_counts() / svr_field_select() (field matching: per frame the combing of the three weaves its kept field
+ * can make, and the frames copied from the first clean weave or from the deinterlaced clip).  New symbols only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -617,6 +624,34 @@ int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int
 #define SVR_DEINT_FIELD 1
 int svr_deinterlace(const void* packed, int64_t packed_bytes, const void* before, const void* after, int32_t fmt, int32_t T, int32_t H,
                     int32_t W, int32_t C, int32_t order, int32_t rate, void* out, int64_t out_bytes, void* stream);
+
+/* ---- field matching ---------------------------------------------------------------------------- */
+/* fieldmatch.py (the specification, bit for bit).  `packed`, `before`, `after`, fmt, T, H, W, C and `order` are svr_deinterlace's: T
+ * woven frames in one of the SVR_UNPACK_* formats, one context frame ahead and one behind or NULL (the mirror).  p = order is the
+ * parity of the kept (first) field.
+ * svr_comb_counts: `cnt` int32 [T, 3, 2].  Only plane 0 is read (Y, or the interleaved RGB plane: R = H rows of N samples, channels s
+ *   apart).  thr' = thr << shift, shift 0 for the 8-bit formats, 2 for SVR_UNPACK_YUV420P10, 8 for SVR_UNPACK_RGB16; thr in 0..255.
+ *   Tested rows: r % 2 == 1 - p, 1 <= r <= R - 2.  Candidate k takes row r from X_0 = F[t], X_1 = F[t-1], X_2 = F[t+1]; with
+ *   u = F[t][r-1][i], l = F[t][r+1][i], m = X_k[r][i], sample i is combed iff m < min(u, l) - thr' or m > max(u, l) + thr'.  Blocks are
+ *   16 plane rows by 16 pixel columns (block row r / 16, block column (i / s) / 16).  cnt[t][k] = (total, peak): the combed samples
+ *   of the frame, and the largest count of any one block.  R < 3: all zero.  The call zeroes `cnt` on `stream`; ONE launch follows
+ *   (block counters in LDS, integer atomic add / max to `cnt`: two runs give the same bits).
+ * svr_field_select: `deint` the T frames of svr_deinterlace(..., SVR_DEINT_FRAME) of the same clip, `cnt` as above, both read from
+ *   device memory in stream order -> `out` T frames.  With pc, pa, pb the peaks of candidates 0, 1, 2 and bound = mi * s (s of plane
+ *   0, mi >= 0): mode 0 if pc <= bound; else (q, m) = (pa, 1) if pa <= pb else (pb, 2), mode m if q <= bound, else 3.  In every
+ *   plane rows of parity p (and the only row of a one-row plane) are F[t]'s, the other rows F[t]'s, F[t-1]'s, F[t+1]'s for modes 0,
+ *   1, 2; in mode 3 the whole frame is deint[t].  `modes` int32 [T] and `stats` int64 [6] may be NULL: modes[t] is the mode; stats
+ *   is ADDED to: entries 0..3 the frames per mode, 4 and 5 the sums of cnt[t][1][0] and cnt[t][2][0] over the mode-3 frames (one
+ *   lane per frame, 64-bit integer atomic adds).  One launch per plane.
+ * Every argument is checked before anything is enqueued: null pointers, an unknown fmt or order, a C the format does not take,
+ * sizes below 1 (T * H * W <= 2^40 pixels; svr_comb_counts: H * W * C <= 2^31, the counters are int32), thr outside 0..255, mi < 0,
+ * byte counts other than EXACTLY the format's and 24 T for cnt, a pointer not aligned to its element, an output (cnt; out, modes,
+ * stats) overlapping an input or another output.  No host synchronisation, no workspace. */
+int svr_comb_counts(const void* packed, int64_t packed_bytes, const void* before, const void* after, int32_t fmt, int32_t T, int32_t H,
+                    int32_t W, int32_t C, int32_t order, int32_t thr, void* cnt, int64_t cnt_bytes, void* stream);
+int svr_field_select(const void* packed, int64_t packed_bytes, const void* before, const void* after, const void* deint,
+                     int64_t deint_bytes, const void* cnt, int64_t cnt_bytes, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,
+                     int32_t order, int32_t mi, void* out, int64_t out_bytes, void* modes, void* stats, void* stream);
 
 /* ---- GGUF block-quantised weights, expanded at load ------------------------------------------- */
 /* gguf.py (the specification, bit for bit): `n_blocks` consecutive blocks of one ggml type -> n_blocks * block size values, each

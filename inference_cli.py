@@ -40,7 +40,13 @@ two parsers by ``ast``), so existing scripts keep working.  What the flags DO is
     upload and the unpack (deinterlace.py / csrc/svr_deinterlace.hip), at deinterlace.RATE: "field" gives two frames per source
     frame and the writer twice the source's frame rate.  --skip_first_frames, --load_cap and --chunk_size count SOURCE frames;
     --batch_size and --temporal_overlap count the frames the model sees.  With the switch off a source tagged interlaced is
-    upscaled as stored, which is said once per job.  ffmpeg backend only.
+    upscaled as stored, which is said once per job.  ffmpeg backend only;
+  * field matching has no flag either: where fieldmatch.ENABLED is set (it ships off) and the tag names an order,
+    FrameSource counts, per stored frame, the combing of the three weaves its kept field can make, copies the first clean weave
+    (a progressive or telecined picture comes back bit for bit) and deinterlaces only the frames without one (fieldmatch.py /
+    csrc/svr_fieldmatch.hip), with fieldmatch.DEFAULTS.  One frame out per frame in, the source's frame rate.  The job ends with
+    one line: the frames per decision, and whether the comb counts agree with the tag's order.  It takes precedence over
+    deinterlace.ENABLED.
 """
 import argparse
 import json
@@ -127,20 +133,37 @@ def _deinterlace():
     return importlib.import_module(f"{PKG}.deinterlace")
 
 
+def _fieldmatch():
+    import importlib
+    return importlib.import_module(f"{PKG}.fieldmatch")
+
+
 def source_fields(tag, rank: int):
-    """ffprobe's field_order tag -> FrameSource's ``fields``: (order, deinterlace.RATE) where the tag names an order and
-    deinterlace.ENABLED is set, else None -- with one warning line on rank 0 where the tag says interlaced and the switch is off
+    """ffprobe's field_order tag -> FrameSource's ``fields``: (order, fieldmatch.RATE) where the tag names an order and
+    fieldmatch.ENABLED is set (it ships off); else (order, deinterlace.RATE) where the tag names an order and
+    deinterlace.ENABLED is set, else None -- with one warning line on rank 0 where the tag says interlaced and both switches are off
     (the shipped state): the frames are then upscaled as stored."""
     deinterlace = _deinterlace()
     order = deinterlace.field_order(tag)
     if order is None:
         return None
+    fieldmatch = _fieldmatch()
+    if fieldmatch.ENABLED:
+        return order, fieldmatch.RATE
     if not deinterlace.ENABLED:
         if rank == 0:
             print(f"Warning: the source is tagged interlaced (field_order {tag}); deinterlacing is off, the frames are upscaled as stored",
                   file=sys.stderr)
         return None
     return order, deinterlace.RATE
+
+
+def field_summary(stats, order: str) -> str:
+    """The one line a field-matched job ends with (fieldmatch.Stats.report(): the feature's only read-back)."""
+    r = stats.report()
+    return (f"Field matching ({order}): {r['stored']} frames as stored, {r['prev']} matched to the previous frame, {r['next']} matched to "
+            f"the next, {r['deinterlaced']} deinterlaced; combed samples against the previous : next frame over the deinterlaced ones "
+            f"{r['sum_prev']} : {r['sum_next']}, which {r['verdict']} the field_order tag")
 
 
 def output_depth(inp: str, info: Optional[dict] = None) -> int:
@@ -475,10 +498,14 @@ class FrameSource:
     the previous buffer's last frame and the NEXT buffer's first frame as context -- so it stays one buffer ahead: buffer k + 1 is
     uploaded and its host slot handed back to the reader thread before buffer k is deinterlaced, at the cost of one more packed
     chunk on the device.  The chunks, concatenated, are deinterlace_torch of the whole clip followed by unpack_frames_torch, for
-    any chunk size; a chunk has as many frames as were read, twice that at rate "field", where ``fps`` doubles too."""
+    any chunk size; a chunk has as many frames as were read, twice that at rate "field", where ``fps`` doubles too.
+    ``fields`` = (order, "match") (fieldmatch.RATE): field matching instead, with the same context and the same one-buffer lead: the
+    chunks, concatenated, are fieldmatch.field_match_torch of the whole clip followed by unpack_frames_torch; as many frames as were
+    read, ``fps`` unchanged.  ``match``: dict(thr=, mi=), fieldmatch.DEFAULTS where None.  ``field_stats``: the fieldmatch.Stats the
+    chunks add to on the device (None for every other source)."""
 
     def __init__(self, exe: str, path: str, info: dict, chunk_size: int, skip: int = 0, cap: int = 0, ops=None, device="cpu",
-                 fields=None):
+                 fields=None, match=None):
         import importlib
         import tempfile
         import torch
@@ -487,14 +514,19 @@ class FrameSource:
         self.frameio_in = importlib.import_module(f"{PKG}.frameio_in")
         self.raw, self.fmt, self.C, self.matrix, self.range_ = route_input(info)
         self.H, self.W, self.fps = info["height"], info["width"], info["fps"]
-        self.fields = fields
+        self.fields, self.match, self.field_stats = fields, None, None
         if fields is not None:
             self.deinterlace = _deinterlace()
+            self.fieldmatch = _fieldmatch()
             order, rate = fields
-            if order not in self.deinterlace.ORDERS or rate not in self.deinterlace.RATES:
-                raise ValueError(f"fields must be (one of {self.deinterlace.ORDERS}, one of {self.deinterlace.RATES}), got {fields!r}")
+            rates = self.deinterlace.RATES + (self.fieldmatch.RATE,)
+            if order not in self.deinterlace.ORDERS or rate not in rates:
+                raise ValueError(f"fields must be (one of {self.deinterlace.ORDERS}, one of {rates}), got {fields!r}")
             if rate == "field":
                 self.fps = 2 * Fraction(info["fps"])
+            if rate == self.fieldmatch.RATE:                     # field matching: its two parameters, and what it did on the device
+                self.match = dict(self.fieldmatch.DEFAULTS if match is None else match)
+                self.field_stats = self.fieldmatch.Stats(torch.device(device))
         self.chunk_size, self.skip, self.cap, self.ops, self.device = chunk_size, skip, cap, ops, torch.device(device)
         self.frame_bytes = self.frameio_in.frame_bytes(self.H, self.W, self.C, self.fmt)
         pinned = self.device.type == "cuda"
@@ -586,6 +618,10 @@ class FrameSource:
         order, rate = self.fields
         if t == 1:                                               # nothing of its own to mirror at an end of the clip: the clip's mirror
             before, after = (after if before is None else before), (before if after is None else after)
+        if rate == self.fieldmatch.RATE:                         # t woven frames -> t progressive ones
+            frames = self.fieldmatch.field_match(packed, self.fmt, t, self.H, self.W, self.C, order, self.match["thr"], self.match["mi"],
+                                                 before=before, after=after, ops=self.ops, stats=self.field_stats)
+            return self._unpack(frames.reshape(-1), t)
         frames = self.deinterlace.deinterlace(packed, self.fmt, t, self.H, self.W, self.C, order, rate, before=before, after=after,
                                               ops=self.ops)
         return self._unpack(frames.reshape(-1), t * (2 if rate == "field" else 1))
@@ -1119,7 +1155,10 @@ def main(argv: Optional[List[str]] = None) -> int:
                 dt = time.time() - t0
                 print(f"Streamed {sink.frames} frames in chunks of {args.chunk_size} in {dt:.2f}s ({sink.frames / dt:.2f} FPS)")
                 print(f"Saved: {path}")
+            if rank == 0 and info is not None and src.field_stats is not None:
+                print(field_summary(src.field_stats, fields[0]))
             continue
+        src = None
         if info is not None:                           # the whole clip, read in chunks and concatenated on the device
             import torch
             src = source(WHOLE_CLIP_READ_FRAMES)
@@ -1131,6 +1170,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             path = output_path(args, inp, fmt, len(jobs), single=out.shape[0] == 1)
             save_frames(out, path, fmt, fps, ops=ops, **job_kw)
             print(f"Saved: {path}")
+            if src is not None and src.field_stats is not None:                 # what field matching did
+                print(field_summary(src.field_stats, fields[0]))
     return 0
 
 
