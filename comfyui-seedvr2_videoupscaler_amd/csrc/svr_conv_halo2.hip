@@ -121,6 +121,7 @@ __device__ unsigned long long g_conv_ep[4096][16];      // DBG 256: stamps insid
 // DBG (builds with -DSVR_ABLATIONS only; results invalid): 1 no weight loads, 2 no halo LDS-DMA, 4 no global stores,
 // 8 no workgroup barrier in the K loop, 16 halo staged once in the prologue (real data) and never again,
 // 32 weights always from the same four (L1-hot) units, 64 halo-row fragments read from LDS in the first A step only, 128 halo re-staged every step but always from the same (cache-hot) addresses
+// (32 and 128: the 4-row kernel only -- the 8-row kernel's running weight pointer and counted frame pointer do not take them)
 template <int TY, int MODE, int DBG = 0>
 __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void conv_halo2_kernel(const svr_gemm_args a, const int band_rows) {
 #ifndef SVR_ABLATIONS
@@ -195,9 +196,8 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
     char* const wave_dst = smem + wave * 1024;
 
     // input frame of A step s (+ channel slice): frame to + dt - pt, the halo tensor or frame 0 before the slice
-    auto frame_ptr = [&](int s) -> const char* {
-        const int dt = s / cpk;
-        const int c0 = (s - dt * cpk) * 32;
+    auto frame_ptr_at = [&](int dt, int c) -> const char* {      // temporal tap dt, 32-channel slice c
+        const int c0 = c * 32;
         int f = to + dt - g.pt;
         const char* basep = (const char*)a.A;
         if (f < 0) {
@@ -205,6 +205,10 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
             else f = 0;
         }
         return basep + (int64_t)f * frame_bytes + c0 * 2;
+    };
+    auto frame_ptr = [&](int s) -> const char* {
+        const int dt = s / cpk;
+        return frame_ptr_at(dt, s - dt * cpk);
     };
     auto stage_a_piece = [&](auto qc, const char* fptr, int buf) {
         constexpr int Q = decltype(qc)::value;
@@ -367,9 +371,7 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
             };
             const char* p0 = uniform_ptr(wp0 + (int64_t)min(k, P - 1) * 2048);
             const char* p1 = uniform_ptr(wp1 + (int64_t)min(k, P - 1) * 2048);
-            if constexpr ((DBG & 1) != 0 && W8) {
-                if (k > 2) return;                                  // 8-row kernel: the three register sets keep their first (real) contents
-            } else if constexpr (DBG & 1) {
+            if constexpr (DBG & 1) {
                 const bf16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
                 w[0][0] = z; w[0][1] = z; w[1][0] = z; w[1][1] = z;
                 return;
@@ -416,100 +418,138 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
         // 10 halo rows per 8 output rows instead of 6 per 4 (-17 % LDS bytes) and an 18 x 34 halo per 16 x 32 patch (-10 %
         // staged bytes).
         // With no second wave on the SIMD to cover latencies the wave runs ONE continuous MFMA stream: a halo row's fragments
-        // are re-read into the registers of a row the running burst has finished with (rows 8, 9 of this column shift at the
-        // start of dy = 0; row 0 of the next shift under dy = 0, row 1 under dy = 1, rows 2..7 under dy = 2 as their pairs
-        // retire), the weight loads and the LDS-DMA pieces of the next A step sit between MFMA groups, and every wait is
-        // counted and retires operations issued at least a quarter burst (256 cycles) earlier.  One workgroup barrier per A
-        // step, at the end of interval 6: by then every wave has finished reading this step's buffer (rows 8, 9 of dx = 2
-        // were the last) and its pieces of the next halo have landed; the first reads of the next buffer follow in interval 7.
+        // are re-read into the registers of a row the running interval has finished with (rows 8, 9 of this column shift under
+        // dy = 0; row 0 of the next shift under dy = 0, row 1 under dy = 1, rows 2..7 under dy = 2 as they retire), the weight
+        // loads and the LDS-DMA pieces of the next A step sit between MFMAs, and every wait is counted and retires operations
+        // issued at least a quarter interval (256 cycles) earlier.  One workgroup barrier per A step, at the end of interval 6:
+        // by then every wave has finished reading this step's buffer (rows 8, 9 of dx = 2 were the last) and its pieces of the
+        // next halo have landed; the first reads of the next buffer follow in interval 7.
+        // One slot per side operation: an interval is 16 units of four MFMAs (one 32-voxel row x one 32-cout block), each
+        // fenced, and behind a unit sits at most ONE side operation -- a halo row's read pair, one weight load, the address of
+        // a halo piece, or its LDS-DMA issue.  A 16x16x32 MFMA holds the vector issue port for 8 of its 16 cycles: about two
+        // ordinary instructions per gap are free, every further one costs its 4 cycles in full, and the form this replaces
+        // (four 16-MFMA quarter bursts per interval, 10..19 instructions in the gaps between them) was written for the 32-cycle
+        // instruction.  Unit U = patch row U / 2, cout block U & 1, halo row U / 2 + dy: the quarter bursts' MFMA order and
+        // operands, so every accumulator sums the same products in the same order (bit-identical;
+        // profiles/r8_conv_slots_kernel_ab.txt, static record profiles/r8_conv_slots_static.txt).
         const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char*)smem;
         unsigned fa[3];
 #pragma unroll
         for (int dx = 0; dx < 3; ++dx) fa[dx] = lds0 + (unsigned)rd_a0[dx];
-        auto stage_full = [&](auto qc, const char* fptr, int buf) {
+        auto piece_src = [&](auto qc, const char* fptr) -> const char* {
             constexpr int Q = decltype(qc)::value;
             const int ck = (akeys >> (2 * Q)) & 3;
             const char* src = (poff[Q] == 0xffffffffu || fptr == nullptr) ? (const char*)g.zeros
                                                                           : fptr + ((int64_t)poff[Q] * g.Cin + ck * 8) * 2;
+            asm volatile("" : "+v"(src));                 // the address is formed HERE, not where the DMA issues
+            return src;
+        };
+        auto piece_dma = [&](auto qc, const char* src, int buf) {
+            constexpr int Q = decltype(qc)::value;
             glds16(src, wave_dst + buf * CG_ABUF + Q * (NT * 16));
         };
+        auto stage_full = [&](auto qc, const char* fptr, int buf) { piece_dma(qc, piece_src(qc, fptr), buf); };   // prologue
         static_assert(CG_PIECES == 10, "piece schedule below is written for ten pieces, two per interval 0..4");
         // (measurement builds, results invalid: DBG 16 no halo staging in the loop, 1 no weight loads, 64 no fragment reads in
         // the loop -- the counted waits that would then be wrong are dropped with them)
         constexpr bool ABL_NO_DMA = (DBG & 16) != 0, ABL_NO_W = (DBG & 1) != 0, ABL_NO_RD = (DBG & 64) != 0;
-#define SVR_RD(ROW, R, DXV, BUFOFF) do { if constexpr (!ABL_NO_RD) cg_rd2<((R) * CG_HX + (DXV)) * 64>(ROW, fa[DXV] + (BUFOFF)); } while (0)
-        // a quarter burst: two patch rows x two 32-cout blocks = 16 matrix instructions
-#define SVR_MM8(W, RA, MA, RB, MB) \
-        cg_mm4(acc[MA][0], W[0], RA); cg_mm4(acc[MA][1], W[1], RA); cg_mm4(acc[MB][0], W[0], RB); cg_mm4(acc[MB][1], W[1], RB)
         // (The last A step runs the same code: its "next halo" pieces stage the zero page into the idle buffer and its
         // look-ahead reads fetch those zeros -- one code path keeps every vmcnt count a compile-time constant, and a peeled
         // copy made hipcc shuffle the 256 accumulators between register files at its entry.)
-        auto interval8 = [&](auto jc, int s, const char* fnext, bf16x8 (&wc)[NTW][2], bf16x8 (&wn_)[NTW][2]) {
+        // Weights: ONE running wave-uniform pointer (the unit of the next load) and two per-lane offsets, the second a 32-cout
+        // block (nstride bytes) further on -- an s_add_u32 / s_addc_u32 per interval instead of a shift and two 64-bit adds.
+        int voff0 = voff, voff1 = voff + (int)nstride;    // (not const: a generic lambda must capture them for its asm operands)
+        const char* wq = wp0;
+        auto wl = [&](auto ic, bf16x8 (&w)[NTW][2]) {
+            constexpr int I = decltype(ic)::value;
+            const int o0 = voff0, o1 = voff1;             // (named outside the if constexpr chain so that the generic lambda captures them)
+            const char* const q = wq;
+            if constexpr (I == 0) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(w[0][0]) : "v"(o0), "s"(q) : "memory");
+            else if constexpr (I == 1) asm volatile("global_load_dwordx4 %0, %1, %2 offset:256" : "=v"(w[0][1]) : "v"(o0), "s"(q) : "memory");
+            else if constexpr (I == 2) asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(w[1][0]) : "v"(o1), "s"(q) : "memory");
+            else asm volatile("global_load_dwordx4 %0, %1, %2 offset:256" : "=v"(w[1][1]) : "v"(o1), "s"(q) : "memory");
+        };
+        auto wload_all = [&](bf16x8 (&w)[NTW][2]) {      // prologue: units 0, 1 (P >= 9: no clamp)
+            wl(std::integral_constant<int, 0>{}, w); wl(std::integral_constant<int, 1>{}, w);
+            wl(std::integral_constant<int, 2>{}, w); wl(std::integral_constant<int, 3>{}, w);
+            wq += 2048;
+        };
+        auto rowref = [&](auto rc) -> bf16x8 (&)[2] {
+            constexpr int R = decltype(rc)::value;
+            static_assert(R >= 0 && R <= 9, "ten halo rows per column shift");
+            if constexpr (R == 0) return ar0; else if constexpr (R == 1) return ar1; else if constexpr (R == 2) return ar2;
+            else if constexpr (R == 3) return ar3; else if constexpr (R == 4) return ar4; else if constexpr (R == 5) return ar5;
+            else if constexpr (R == 6) return ar6; else if constexpr (R == 7) return ar7; else if constexpr (R == 8) return ar8;
+            else return ar9;
+        };
+        auto interval8 = [&](auto jc, int s, const char* fnext, int wadv, bf16x8 (&wc)[NTW][2], bf16x8 (&wn_)[NTW][2]) {
             constexpr int J = decltype(jc)::value;
             constexpr int DY = J % 3, DX = J / 3;
-            const int k = s * 9 + J;
+            constexpr int NDX = DX < 2 ? DX + 1 : 0;      // the column shift the look-ahead reads belong to ...
             const unsigned cur = (unsigned)((s & 1) * CG_ABUF), nxt = (unsigned)(((s + 1) & 1) * CG_ABUF);
-            // VMEM issue order per interval: 4 weight loads, then (J < 5) 2 halo pieces.  Younger than the
-            // weights of interval J (issued in J - 2): the pieces of J - 2, the weights and pieces of J - 1.
+            const unsigned nbuf = DX < 2 ? cur : nxt;     // ... and its buffer (dx = 2 looks ahead into the next A step's)
+            // VMEM issue order per interval: 4 weight loads (slots 2..9), then (J < 5) 2 halo pieces (slots 12 and 14).  Younger
+            // than the weights of interval J (issued in J - 2): the pieces of J - 2, the weights and pieces of J - 1 -- no
+            // VMEM operation crosses an interval start, so the count does not depend on the slots.
             constexpr int NPC[9] = {2, 2, 2, 2, 2, 0, 0, 0, 0};
             constexpr int NV = 4 + NPC[(J + 8) % 9] + NPC[(J + 7) % 9];
-            if constexpr (DY == 0) {
-                cg_wait_rows<0>(ar0, ar1, ar2, ar3, ar4, ar5, ar6, ar7);
-                SVR_RD(ar8, 8, DX, cur);
-                SVR_RD(ar9, 9, DX, cur);
-            } else if constexpr (DY == 1 && J != 7) {
-                cg_wait_rows<4>(ar8);                    // in flight behind it: row 9, row 0 of the next shift
-            } else if constexpr (DY == 2 && J != 8) {
-                cg_wait_rows<4>(ar9);                    // row 0 and row 1 of the next shift
-            }
+            // LGKM issue order per A step, dx by dx: rows 8, 9 (dy = 0, slots 0, 1), row 0 of the next shift (dy = 0, slot 2;
+            // dx = 2: interval 7, slot 0, behind the barrier), row 1 (dy = 1, slot 1), rows 2..7 (dy = 2, slots 1, 3, .. 11).
+            // At the start of dy = 1 the pairs behind row 8 are row 9 and row 0: lgkmcnt(4); at the start of dy = 2 behind row 9:
+            // row 0 and row 1: lgkmcnt(4).  No read crosses an interval start either.
+            if constexpr (DY == 0) cg_wait_rows<0>(ar0, ar1, ar2, ar3, ar4, ar5, ar6, ar7);
+            else if constexpr (DY == 1 && J != 7) cg_wait_rows<4>(ar8);
+            else if constexpr (DY == 2 && J != 8) cg_wait_rows<4>(ar9);
             if constexpr (!ABL_NO_DMA && !ABL_NO_W) cg_wait_w<NV>(wc);
             else if constexpr (ABL_NO_DMA && !ABL_NO_W) cg_wait_w<4>(wc);
-            if constexpr (J == 7) SVR_RD(ar0, 0, 0, nxt);
             __builtin_amdgcn_sched_barrier(0);
-            // group 1
-            if constexpr (DY == 0) { SVR_MM8(wc, ar0, 0, ar1, 1); }
-            else if constexpr (DY == 1) { SVR_MM8(wc, ar1, 0, ar2, 1); }
-            else { SVR_MM8(wc, ar2, 0, ar3, 1); }
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (DX < 2) {
-                if constexpr (DY == 0) SVR_RD(ar0, 0, DX + 1, cur);
-                else if constexpr (DY == 1) SVR_RD(ar1, 1, DX + 1, cur);
-                else { SVR_RD(ar2, 2, DX + 1, cur); SVR_RD(ar3, 3, DX + 1, cur); }
-            } else {
-                if constexpr (DY == 1) SVR_RD(ar1, 1, 0, nxt);
-                else if constexpr (DY == 2) { SVR_RD(ar2, 2, 0, nxt); SVR_RD(ar3, 3, 0, nxt); }
-            }
-            wload(wn_, k + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            // group 2
-            if constexpr (DY == 0) { SVR_MM8(wc, ar2, 2, ar3, 3); }
-            else if constexpr (DY == 1) { SVR_MM8(wc, ar3, 2, ar4, 3); }
-            else { SVR_MM8(wc, ar4, 2, ar5, 3); }
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (DY == 2) {
-                if constexpr (DX < 2) { SVR_RD(ar4, 4, DX + 1, cur); SVR_RD(ar5, 5, DX + 1, cur); }
-                else { SVR_RD(ar4, 4, 0, nxt); SVR_RD(ar5, 5, 0, nxt); }
-            }
-            if constexpr (J < 5 && !ABL_NO_DMA) {
-                stage_full(std::integral_constant<int, (J < 5 ? 2 * J : 0)>{}, fnext, (s + 1) & 1);
-                stage_full(std::integral_constant<int, (J < 5 ? 2 * J + 1 : 0)>{}, fnext, (s + 1) & 1);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // group 3
-            if constexpr (DY == 0) { SVR_MM8(wc, ar4, 4, ar5, 5); }
-            else if constexpr (DY == 1) { SVR_MM8(wc, ar5, 4, ar6, 5); }
-            else { SVR_MM8(wc, ar6, 4, ar7, 5); }
-            __builtin_amdgcn_sched_barrier(0);
-            if constexpr (DY == 2) {
-                if constexpr (DX < 2) { SVR_RD(ar6, 6, DX + 1, cur); SVR_RD(ar7, 7, DX + 1, cur); }
-                else { SVR_RD(ar6, 6, 0, nxt); SVR_RD(ar7, 7, 0, nxt); }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            // group 4
-            if constexpr (DY == 0) { SVR_MM8(wc, ar6, 6, ar7, 7); }
-            else if constexpr (DY == 1) { SVR_MM8(wc, ar7, 6, ar8, 7); }
-            else { SVR_MM8(wc, ar8, 6, ar9, 7); }
-            __builtin_amdgcn_sched_barrier(0);
+            constexpr bool PIECES_HERE = J < 5 && !ABL_NO_DMA;
+            constexpr int QA = J < 5 ? 2 * J : 0, QB = J < 5 ? 2 * J + 1 : 0;
+            const char* srca = nullptr;
+            const char* srcb = nullptr;
+            auto rd = [&](auto rc, auto dxc, unsigned bufoff) {
+                constexpr int R = decltype(rc)::value, DXV = decltype(dxc)::value;
+                if constexpr (!ABL_NO_RD) cg_rd2<(R * CG_HX + DXV) * 64>(rowref(rc), fa[DXV] + bufoff);
+            };
+            auto rdn = [&](auto rc) { rd(rc, std::integral_constant<int, NDX>{}, nbuf); };     // a row of the next column shift
+            // slot U: what sits behind unit U.  A register is re-read behind the last unit that multiplies it: row R of dy feeds
+            // units 2 (R - dy) and 2 (R - dy) + 1.
+            auto side = [&](auto uc) {
+                constexpr int U = decltype(uc)::value;
+                constexpr int WL0 = DY == 2 ? 2 : 3;      // weight loads every other slot (dy = 2: the even ones, between its reads)
+                if constexpr (!ABL_NO_W && U >= WL0 && U <= WL0 + 6 && (U - WL0) % 2 == 0) {
+                    wl(std::integral_constant<int, (U - WL0) / 2>{}, wn_);
+                    if constexpr (U == WL0 + 6) {         // unit k + 3 next; intervals 6, 7 of the last step stay on unit P - 1
+                        if constexpr (J == 6 || J == 7) wq += wadv; else wq += 2048;
+                    }
+                }
+                if constexpr (DY == 0) {
+                    if constexpr (U == 0) rd(std::integral_constant<int, 8>{}, std::integral_constant<int, DX>{}, cur);
+                    else if constexpr (U == 1) rd(std::integral_constant<int, 9>{}, std::integral_constant<int, DX>{}, cur);
+                    else if constexpr (U == 2 && DX < 2) rdn(std::integral_constant<int, 0>{});
+                } else if constexpr (DY == 1) {
+                    if constexpr (U == 0 && J == 7) rdn(std::integral_constant<int, 0>{});   // first read of the next buffer
+                    else if constexpr (U == 1) rdn(std::integral_constant<int, 1>{});
+                } else {
+                    if constexpr (U <= 11 && U % 2 == 1) rdn(std::integral_constant<int, 2 + U / 2>{});
+                }
+                if constexpr (PIECES_HERE) {
+                    if constexpr (U == 10) srca = piece_src(std::integral_constant<int, QA>{}, fnext);
+                    else if constexpr (U == 12) piece_dma(std::integral_constant<int, QA>{}, srca, (s + 1) & 1);
+                    else if constexpr (U == 13) srcb = piece_src(std::integral_constant<int, QB>{}, fnext);
+                    else if constexpr (U == 14) piece_dma(std::integral_constant<int, QB>{}, srcb, (s + 1) & 1);
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            auto unit = [&](auto uc) {
+                constexpr int U = decltype(uc)::value;
+                cg_mm4(acc[U / 2][U & 1], wc[U & 1], rowref(std::integral_constant<int, U / 2 + DY>{}));
+                __builtin_amdgcn_sched_barrier(0);
+            };
+#define SVR_US(U) unit(std::integral_constant<int, U>{}); side(std::integral_constant<int, U>{})
+            SVR_US(0); SVR_US(1); SVR_US(2); SVR_US(3); SVR_US(4); SVR_US(5); SVR_US(6); SVR_US(7);
+            SVR_US(8); SVR_US(9); SVR_US(10); SVR_US(11); SVR_US(12); SVR_US(13); SVR_US(14); SVR_US(15);
+#undef SVR_US
             if constexpr (J == 6) {
                 cg_wait_rows<0>(ar8, ar9);                // the last reads of this step's buffer
                 if constexpr (!ABL_NO_DMA && !ABL_NO_W) cg_wait_vmcnt<8>();   // the pieces of interval 4 (younger: the weight loads of 5 and 6)
@@ -529,9 +569,9 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
             stage_full(std::integral_constant<int, 7>{}, f0, 0);
             stage_full(std::integral_constant<int, 8>{}, f0, 0);
             stage_full(std::integral_constant<int, 9>{}, f0, 0);
-            wload(w0, 0);
-            wload(w1, 1);
-            if constexpr (ABL_NO_W) wload(w2, 2);
+            wload_all(w0);
+            wload_all(w1);
+            if constexpr (ABL_NO_W) wload_all(w2);
             // hipcc materialises the 256 zeroed accumulators where the first MFMA needs them -- 249 v_accvgpr_write BEHIND this wait
             // and barrier, ~1 000 issue cycles per tile with nothing in flight.  Pinning them here puts the writes under the latency
             // of the first halo and weight loads (behind the sched_barrier, so that they do not delay the loads' issue): bit-identical,
@@ -554,24 +594,26 @@ __global__ __launch_bounds__((cg_geom<TY, MODE>::NT), (MODE == 3 ? 1 : 2)) void 
 #ifdef SVR_ABLATIONS
         if constexpr ((DBG & 256) != 0) { if (tid == 0 && blockIdx.x < 4096) g_conv_tl[blockIdx.x][1] = __builtin_amdgcn_s_memtime(); }
 #endif
+        int ndt = 0, nc = 0;                              // (temporal tap, channel slice) of step s + 1, counted instead of divided
         for (int s = 0; s < nA; ++s) {
-            const char* fnext = s + 1 < nA ? frame_ptr((DBG & 128) ? 0 : s + 1) : nullptr;     // (128: always the same, cache-hot halo)
-            interval8(std::integral_constant<int, 0>{}, s, fnext, w0, w2);
-            interval8(std::integral_constant<int, 1>{}, s, fnext, w1, w0);
-            interval8(std::integral_constant<int, 2>{}, s, fnext, w2, w1);
-            interval8(std::integral_constant<int, 3>{}, s, fnext, w0, w2);
-            interval8(std::integral_constant<int, 4>{}, s, fnext, w1, w0);
-            interval8(std::integral_constant<int, 5>{}, s, fnext, w2, w1);
-            interval8(std::integral_constant<int, 6>{}, s, fnext, w0, w2);
-            interval8(std::integral_constant<int, 7>{}, s, fnext, w1, w0);
-            interval8(std::integral_constant<int, 8>{}, s, fnext, w2, w1);
+            if (++nc == cpk) { nc = 0; ++ndt; }
+            const bool more = s + 1 < nA;
+            const char* fnext = more ? frame_ptr_at(ndt, nc) : nullptr;
+            const int wadv = more ? 2048 : 0;
+            interval8(std::integral_constant<int, 0>{}, s, fnext, wadv, w0, w2);
+            interval8(std::integral_constant<int, 1>{}, s, fnext, wadv, w1, w0);
+            interval8(std::integral_constant<int, 2>{}, s, fnext, wadv, w2, w1);
+            interval8(std::integral_constant<int, 3>{}, s, fnext, wadv, w0, w2);
+            interval8(std::integral_constant<int, 4>{}, s, fnext, wadv, w1, w0);
+            interval8(std::integral_constant<int, 5>{}, s, fnext, wadv, w2, w1);
+            interval8(std::integral_constant<int, 6>{}, s, fnext, wadv, w0, w2);
+            interval8(std::integral_constant<int, 7>{}, s, fnext, wadv, w1, w0);
+            interval8(std::integral_constant<int, 8>{}, s, fnext, wadv, w2, w1);
         }
         // drain: the hand-issued weight loads (the epilogue reuses their registers) and the look-ahead fragment reads
         cg_wait_vmcnt<0>();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_sched_barrier(0);
-#undef SVR_RD
-#undef SVR_MM8
         } else {
         bool a_prev3 = false;
         auto interval3 = [&](auto jc, int s, const char* fnext, const bf16x8 (&wc)[NTW][2], bf16x8 (&wn_)[NTW][2]) {

@@ -3,6 +3,7 @@
 
     python tools/loop_instruction_mix.py attn_win_kernel            # every instantiation whose mangled name contains the text
     python tools/loop_instruction_mix.py conv_sub_kernel --ops      # + the opcode histogram of the loop
+    python tools/loop_instruction_mix.py conv_halo2_kernelILi16ELi3 --clusters   # + MFMA run lengths and what sits between the runs
 
 For each matching kernel: the loop (backward branch) that holds the most MFMAs, its instruction counts by issue class, and the
 issue slots the VALU port needs per MFMA (v_exp / v_log / v_rcp / v_rsq / v_sqrt / v_sin / v_cos are quarter rate: 4 slots).  A
@@ -24,10 +25,10 @@ sys.path.insert(0, ROOT)
 QUARTER = ("v_exp_", "v_log_", "v_rcp_", "v_rsq_", "v_sqrt_", "v_sin_", "v_cos_")
 
 
-def device_asm() -> str:
+def device_asm(defines=()) -> str:
     hip_lib = importlib.import_module("comfyui-seedvr2_videoupscaler_amd.hip_lib")
     out = os.path.join(tempfile.mkdtemp(prefix="svr_asm_"), "svr_api.s")
-    cmd = ["/opt/rocm/bin/hipcc"] + [f for f in hip_lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + \
+    cmd = ["/opt/rocm/bin/hipcc"] + [f for f in hip_lib.HIPCC_FLAGS if f not in ("-shared", "-fPIC")] + ["-D" + d for d in defines] + \
           ["-S", "--cuda-device-only", os.path.join(hip_lib.CSRC, "svr_api.hip"), "-o", out]
     subprocess.run(cmd, check=True, capture_output=True)
     return open(out).read()
@@ -63,13 +64,50 @@ def hot_loop(body: str):
     return lines[best[1]:best[2] + 1]
 
 
+def clusters(ops):
+    """MFMA runs and the non-MFMA clusters between them, in loop order, the loop taken as a ring (the cluster that spans the
+    backward branch is one cluster).  Returns (run lengths, clusters), a cluster being the list of its opcodes."""
+    first = next(i for i, o in enumerate(ops) if o.startswith("v_mfma"))
+    ring = ops[first:] + ops[:first]
+    runs, cl = [], []                     # run i is followed by cluster i
+    for o in ring:
+        if o.startswith("v_mfma"):
+            if len(runs) == len(cl):      # the first MFMA, or the first one behind a cluster
+                runs.append(0)
+            runs[-1] += 1
+        else:
+            if len(cl) < len(runs):
+                cl.append([])
+            cl[-1].append(o)
+    return runs, cl
+
+
+def print_clusters(ops, big):
+    runs, cl = clusters(ops)
+    sizes = [len(c) for c in cl]
+    print(f"  MFMA runs ({len(runs)}): {collections.Counter(runs).most_common()}  (length, how often)")
+    print(f"  clusters between them ({len(cl)}), sizes in loop order: {sizes}")
+    print(f"  instructions in clusters: {sum(sizes)}; largest {max(sizes)}; clusters of >= {big}: {sum(1 for n in sizes if n >= big)} "
+          f"holding {sum(n for n in sizes if n >= big)}")
+    # static issue-cost model (16x16x32 MFMAs): an MFMA gap hides about two 4-cycle instructions (8 of the 16 cycles), each further one costs 4
+    print(f"  static exposure, sum over clusters of max(0, 4 n - 8): {sum(max(0, 4 * n - 8) for n in sizes)} cycles")
+    for i, c in enumerate(cl):
+        if len(c) >= big:
+            why = [k for k in ("s_waitcnt", "s_barrier") if any(o.startswith(k) for o in c)]
+            print(f"    cluster {i} ({len(c)}){' [' + ', '.join(why) + ']' if why else ''}: " + " ".join(c))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("kernel", help="text the mangled kernel name must contain")
     ap.add_argument("--ops", action="store_true", help="opcode histogram of the loop")
     ap.add_argument("--dump", action="store_true", help="print the loop's assembly")
+    ap.add_argument("--clusters", action="store_true", help="MFMA run lengths and the sizes of the non-MFMA clusters between them")
+    ap.add_argument("--big", type=int, default=6, help="with --clusters: list the opcodes of clusters of at least this size")
+    ap.add_argument("-D", dest="defines", action="append", default=[], help="extra preprocessor define for the compile (NAME=VALUE)")
+    ap.add_argument("--asm", help="read this device assembly file instead of compiling")
     args = ap.parse_args()
-    asm = device_asm()
+    asm = open(args.asm).read() if args.asm else device_asm(args.defines)
     for m in re.finditer(r"^(_Z\w*" + re.escape(args.kernel) + r"\w*):[^\n]*\n(.*?)s_endpgm", asm, re.S | re.M):
         loop = hot_loop(m.group(2))
         if loop is None:
@@ -85,6 +123,8 @@ def main():
         if args.ops:
             hist = collections.Counter(o for o in ops if classify(o) in ("valu", "valu_quarter_rate", "accvgpr_move"))
             print("  " + ", ".join(f"{k} {v}" for k, v in hist.most_common(24)))
+        if args.clusters:
+            print_clusters(ops, args.big)
         if args.dump:
             print("\n".join(loop))
 
