@@ -222,6 +222,10 @@ class HipOps:
     def _stream(self):
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
+    def _launch(self, name, *args):
+        """An entry point that takes the stream last: called on the current stream, its status checked under its own name."""
+        hip_lib.check(getattr(self.lib, name)(*args, self._stream()), name)
+
     def _chk(self, t, dtype=None, name="tensor"):
         if not on_device(t, self.device):
             raise ValueError(f"{name} must live on {self.device}, got {t.device}")
@@ -260,8 +264,7 @@ class HipOps:
             def run(iters):
                 s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 s.record()
-                hip_lib.check(self.lib.svr_mfma_calibrate(C.c_void_p(ws.data_ptr()), int(iters), C.byref(flops), self._stream()),
-                              "svr_mfma_calibrate")
+                self._launch("svr_mfma_calibrate", C.c_void_p(ws.data_ptr()), int(iters), C.byref(flops))
                 e.record()
                 e.synchronize()
                 return flops.value / (s.elapsed_time(e) * 1e-3) / 1e12
@@ -289,8 +292,7 @@ class HipOps:
             return None
         self._chk(W, BF16, "W")
         out = torch.empty(N * W.shape[1], dtype=BF16, device=self.device)
-        hip_lib.check(self.lib.svr_conv_pack_frag_taps(_ptr(W), _ptr(out), N, W.shape[1], kt, kh, kw, Cin, self._stream()),
-                      "svr_conv_pack_frag_taps")
+        self._launch("svr_conv_pack_frag_taps", _ptr(W), _ptr(out), N, W.shape[1], kt, kh, kw, Cin)
         return out
 
     def pack_gemm_frag(self, W):
@@ -302,7 +304,7 @@ class HipOps:
             return None
         self._chk(W, BF16, "W")
         out = torch.empty(n * k, dtype=BF16, device=self.device)
-        hip_lib.check(self.lib.svr_gemm_pack_frag(_ptr(W), _ptr(out), n, k, self._stream()), "svr_gemm_pack_frag")
+        self._launch("svr_gemm_pack_frag", _ptr(W), _ptr(out), n, k)
         return out
 
     def gemm(self, A, W, out, *, N, K, M=None, bias=None, epilogue=EPI_BIAS, gate=None, resid=None,
@@ -352,11 +354,10 @@ class HipOps:
                 a.gn_groups = 0
         if self.record_kernel_class:                      # (bench.py: which kernel does the library pick for this launch)
             self.last_kernel_class = hip_lib.KERNEL_CLASSES.get(int(self.lib.svr_gemm_kernel_class(C.byref(a))), "invalid")
-        hip_lib.check(self.lib.svr_gemm_bf16(C.byref(a), self._stream()), "svr_gemm_bf16")
+        self._launch("svr_gemm_bf16", C.byref(a))
         if gn_groups > 0 and gn_shared is None:
             if stats is not None:
-                hip_lib.check(self.lib.svr_groupnorm_reduce(_ptr(partial), _ptr(stats), conv.To, nblk, gn_groups,
-                                                            self._stream()), "svr_groupnorm_reduce")
+                self._launch("svr_groupnorm_reduce", _ptr(partial), _ptr(stats), conv.To, nblk, gn_groups)
             return out, stats
         return out
 
@@ -374,8 +375,8 @@ class HipOps:
         if not gn_shared.get("ok", False) or "partial" not in gn_shared:
             return None
         stats = torch.empty(gn_shared["frames"], gn_shared["groups"], 2, dtype=torch.float64, device=self.device)
-        hip_lib.check(self.lib.svr_groupnorm_reduce(_ptr(gn_shared["partial"]), _ptr(stats), gn_shared["frames"], gn_shared["nblk"],
-                                                    gn_shared["groups"], self._stream()), "svr_groupnorm_reduce")
+        self._launch("svr_groupnorm_reduce", _ptr(gn_shared["partial"]), _ptr(stats), gn_shared["frames"], gn_shared["nblk"],
+                     gn_shared["groups"])
         return stats
 
     # ------------------------------------------------------------------ DiT side kernels
@@ -389,18 +390,15 @@ class HipOps:
         rows, dim = x.shape
         if tuple(out.shape) != (rows, dim):
             raise ValueError("rmsnorm_mod: x must be bf16, fp32 or h16 [rows, dim] and out bf16 of the same shape")
-        hip_lib.check(self.lib.svr_rmsnorm_mod(_ptr(x), _ptr(out), rows, dim, eps, self._opt(w, torch.float32, "w", dim),
-                                               self._opt(scale, torch.float32, "scale", dim),
-                                               self._opt(shift, torch.float32, "shift", dim), xf,
-                                               self._stream()), "svr_rmsnorm_mod")
+        self._launch("svr_rmsnorm_mod", _ptr(x), _ptr(out), rows, dim, eps, self._opt(w, torch.float32, "w", dim),
+                     self._opt(scale, torch.float32, "scale", dim), self._opt(shift, torch.float32, "shift", dim), xf)
         return out
 
     def ada_combine(self, emb, params, slots, out):
         self._chk(emb, BF16, "emb"); self._chk(params, BF16, "params")
         self._chk(slots, torch.int32, "slots"); self._chk(out, torch.float32, "out")
         n_vec, dim = params.shape
-        hip_lib.check(self.lib.svr_ada_combine(_ptr(emb), _ptr(params), _ptr(slots), _ptr(out), n_vec, dim,
-                                               self._stream()), "svr_ada_combine")
+        self._launch("svr_ada_combine", _ptr(emb), _ptr(params), _ptr(slots), _ptr(out), n_vec, dim)
         return out
 
     def qknorm_rope(self, qkv, heads, pos, t_offset, cos_tab, sin_tab, wq, wk, eps):
@@ -414,10 +412,8 @@ class HipOps:
             raise ValueError("qknorm_rope: cos / sin tables of different shapes")
         if wq is None or wk is None:
             raise ValueError("qknorm_rope: the q / k norm weights are required (fp32 [128] each)")
-        hip_lib.check(self.lib.svr_qknorm_rope(_ptr(qkv), rows, heads, _ptr(pos), t_offset, _ptr(cos_tab),
-                                               _ptr(sin_tab), n_pos, n_freq, self._opt(wq, torch.float32, "wq", 128),
-                                               self._opt(wk, torch.float32, "wk", 128), eps,
-                                               self._stream()), "svr_qknorm_rope")
+        self._launch("svr_qknorm_rope", _ptr(qkv), rows, heads, _ptr(pos), t_offset, _ptr(cos_tab), _ptr(sin_tab), n_pos, n_freq,
+                     self._opt(wq, torch.float32, "wq", 128), self._opt(wk, torch.float32, "wk", 128), eps)
         return qkv
 
     def attn_varlen(self, qkv, out, seq_rows, out_rows, cu, max_len, heads, head_dim, scale):
@@ -427,32 +423,28 @@ class HipOps:
         if qkv.dim() != 2 or out.dim() != 2 or qkv.shape[1] != 3 * heads * head_dim or out.shape[1] != heads * head_dim or \
                 seq_rows.numel() != out_rows.numel() or cu.numel() < 1:
             raise ValueError("attn_varlen: qkv [rows, 3 * heads * head_dim], out [rows', heads * head_dim], one out_row per seq_row")
-        hip_lib.check(self.lib.svr_attn_varlen(_ptr(qkv), qkv.stride(0), _ptr(out), out.stride(0), _ptr(seq_rows),
-                                               _ptr(out_rows), _ptr(cu), cu.numel() - 1, max_len, heads, head_dim,
-                                               scale, self._stream()), "svr_attn_varlen")
+        self._launch("svr_attn_varlen", _ptr(qkv), qkv.stride(0), _ptr(out), out.stride(0), _ptr(seq_rows), _ptr(out_rows), _ptr(cu),
+                     cu.numel() - 1, max_len, heads, head_dim, scale)
         return out
 
     def softmax_rows(self, S, P, scale):
         """P[r] = softmax(scale * S[r]); S fp32 [rows, cols], P bf16 [rows, cols]."""
         self._chk(S, torch.float32, "S"); self._chk(P, BF16, "P")
         rows, cols = S.shape
-        hip_lib.check(self.lib.svr_softmax_rows(_ptr(S), _ptr(P), rows, cols, S.stride(0), P.stride(0), scale,
-                                                self._stream()), "svr_softmax_rows")
+        self._launch("svr_softmax_rows", _ptr(S), _ptr(P), rows, cols, S.stride(0), P.stride(0), scale)
         return P
 
     def rows_mean(self, src, dst, n_groups, rows_per_group):
         self._chk(src, BF16, "src"); self._chk(dst, BF16, "dst")
         if src.numel() != n_groups * rows_per_group * src.shape[-1] or dst.numel() != rows_per_group * src.shape[-1]:
             raise ValueError("rows_mean: src [n_groups * rows_per_group, dim], dst [rows_per_group, dim]")
-        hip_lib.check(self.lib.svr_rows_mean(_ptr(src), _ptr(dst), n_groups, rows_per_group, src.shape[-1],
-                                             self._stream()), "svr_rows_mean")
+        self._launch("svr_rows_mean", _ptr(src), _ptr(dst), n_groups, rows_per_group, src.shape[-1])
         return dst
 
     def patchify(self, vid, out):
         self._chk(vid, BF16, "vid"); self._chk(out, BF16, "out")
         T, H, W, Cc = vid.shape
-        hip_lib.check(self.lib.svr_patchify(_ptr(vid), _ptr(out), T, H, W, Cc, out.shape[1], self._stream()),
-                      "svr_patchify")
+        self._launch("svr_patchify", _ptr(vid), _ptr(out), T, H, W, Cc, out.shape[1])
         return out
 
     def unpatchify_euler(self, pred, x_t, out):
@@ -460,8 +452,7 @@ class HipOps:
         T, H, W, Cc = out.shape
         if x_t is not None:
             self._chk(x_t, BF16, "x_t")
-        hip_lib.check(self.lib.svr_unpatchify_euler(_ptr(pred), pred.stride(0), _ptr(x_t), _ptr(out), T, H, W, Cc,
-                                                    self._stream()), "svr_unpatchify_euler")
+        self._launch("svr_unpatchify_euler", _ptr(pred), pred.stride(0), _ptr(x_t), _ptr(out), T, H, W, Cc)
         return out
 
     # ------------------------------------------------------------------ VAE side kernels
@@ -472,8 +463,7 @@ class HipOps:
             raise ValueError("groupnorm_stats: stats must be [T, groups, 2]")
         ws = torch.empty(int(self.lib.svr_groupnorm_workspace_bytes(T, H * W, groups)), dtype=torch.uint8,
                          device=self.device)
-        hip_lib.check(self.lib.svr_groupnorm_stats(_ptr(x), _ptr(stats), _ptr(ws), T, H * W, Cc, groups, xf,
-                                                   self._stream()), "svr_groupnorm_stats")
+        self._launch("svr_groupnorm_stats", _ptr(x), _ptr(stats), _ptr(ws), T, H * W, Cc, groups, xf)
         return stats
 
     def groupnorm_apply(self, x, out, stats, gamma, beta, groups, eps, silu):
@@ -483,10 +473,9 @@ class HipOps:
             raise ValueError("groupnorm_apply: out must have x's shape")
         if stats is None or gamma is None or beta is None:
             raise ValueError("groupnorm_apply: stats, gamma and beta are required")
-        hip_lib.check(self.lib.svr_groupnorm_apply(_ptr(x), _ptr(out), self._opt(stats, torch.float64, "stats", T * groups * 2),
-                                                   self._opt(gamma, torch.float32, "gamma", Cc),
-                                                   self._opt(beta, torch.float32, "beta", Cc), T, H * W,
-                                                   Cc, groups, eps, int(silu), xf, self._stream()), "svr_groupnorm_apply")
+        self._launch("svr_groupnorm_apply", _ptr(x), _ptr(out), self._opt(stats, torch.float64, "stats", T * groups * 2),
+                     self._opt(gamma, torch.float32, "gamma", Cc), self._opt(beta, torch.float32, "beta", Cc), T, H * W, Cc, groups,
+                     eps, int(silu), xf)
         return out
 
     def im2col_causal(self, x, out, conv: Conv3dGeom):
@@ -502,8 +491,7 @@ class HipOps:
             g.halo_frames = conv.halo.shape[0]
             g.halo = self._chk(conv.halo, BF16, "halo").data_ptr()
         g.zeros = self.zeros.data_ptr()
-        hip_lib.check(self.lib.svr_im2col_causal(_ptr(x), _ptr(out), C.byref(g), out.shape[1], self._stream()),
-                      "svr_im2col_causal")
+        self._launch("svr_im2col_causal", _ptr(x), _ptr(out), C.byref(g), out.shape[1])
         return out
 
     def blend_accumulate(self, tile, acc, cnt, wy, wx, y0, x0):
@@ -512,9 +500,8 @@ class HipOps:
         Ta, H, W, Ca = acc.shape
         if (Ta, Ca) != (T, Cc) or cnt.numel() != H * W:
             raise ValueError("blend_accumulate: acc [T, H, W, C] for tile [T, h, w, C], cnt [H, W]")
-        hip_lib.check(self.lib.svr_blend_accumulate(_ptr(tile), _ptr(acc), _ptr(cnt), self._opt(wy, torch.float32, "wy", h),
-                                                    self._opt(wx, torch.float32, "wx", w), T, h, w, Cc,
-                                                    H, W, y0, x0, self._stream()), "svr_blend_accumulate")
+        self._launch("svr_blend_accumulate", _ptr(tile), _ptr(acc), _ptr(cnt), self._opt(wy, torch.float32, "wy", h),
+                     self._opt(wx, torch.float32, "wx", w), T, h, w, Cc, H, W, y0, x0)
 
     def blend_finalize(self, acc, cnt, out, scale=1.0, shift=0.0):
         self._chk(acc, torch.float32, "acc"); self._chk(out, BF16, "out")
@@ -522,16 +509,14 @@ class HipOps:
         self._chk(cnt, torch.float32, "cnt")
         if cnt.numel() != H * W or out.numel() != T * H * W * out.shape[-1]:
             raise ValueError("blend_finalize: cnt [H, W], out [T, H, W, c_take]")
-        hip_lib.check(self.lib.svr_blend_finalize(_ptr(acc), _ptr(cnt), _ptr(out), T, H * W, Cc, out.shape[-1], scale,
-                                                  shift, self._stream()), "svr_blend_finalize")
+        self._launch("svr_blend_finalize", _ptr(acc), _ptr(cnt), _ptr(out), T, H * W, Cc, out.shape[-1], scale, shift)
         return out
 
     def affine_slice(self, inp, out, scale=1.0, shift=0.0):
         self._chk(inp, BF16, "inp"); self._chk(out, BF16, "out")
         c_in, c_out = inp.shape[-1], out.shape[-1]
         rows = inp.numel() // c_in
-        hip_lib.check(self.lib.svr_affine_slice(_ptr(inp), _ptr(out), rows, c_in, c_out, scale, shift, self._stream()),
-                      "svr_affine_slice")
+        self._launch("svr_affine_slice", _ptr(inp), _ptr(out), rows, c_in, c_out, scale, shift)
         return out
 
     # ------------------------------------------------------------------ alpha channel
@@ -571,11 +556,10 @@ class HipOps:
             raise ValueError("alpha_upscale: need T >= 1 and frames of at least 2 x 2 pixels")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         rgb_p, ws_p, n_alpha = _ptr(rgb_thwc), _ptr(ws), alpha_lo.numel()
-        hip_lib.check(self.lib.svr_alpha_stats(_ptr(alpha_lo), n_alpha, rgb_p, T, H, W, ld, kind, ws_p, nbytes, self._stream()),
-                      "svr_alpha_stats")
-        hip_lib.check(self.lib.svr_alpha_edges(rgb_p, T, H, W, ld, kind, ws_p, nbytes, self._stream()), "svr_alpha_edges")
-        hip_lib.check(self.lib.svr_alpha_refine(rgb_p, _ptr(base), _ptr(out), self._opt(edge_out, torch.uint8, "edge_out"), T, H, W, ld,
-                                                kind, n_alpha, ws_p, nbytes, self._stream()), "svr_alpha_refine")
+        self._launch("svr_alpha_stats", _ptr(alpha_lo), n_alpha, rgb_p, T, H, W, ld, kind, ws_p, nbytes)
+        self._launch("svr_alpha_edges", rgb_p, T, H, W, ld, kind, ws_p, nbytes)
+        self._launch("svr_alpha_refine", rgb_p, _ptr(base), _ptr(out), self._opt(edge_out, torch.uint8, "edge_out"), T, H, W, ld, kind,
+                     n_alpha, ws_p, nbytes)
         return out
 
     # ------------------------------------------------------------------ packed output frames
@@ -602,8 +586,8 @@ class HipOps:
         uint16 [T, H*W + 2*h2*w2] ("yuv420p10", C = 3).  One launch on the current stream, no host synchronisation.  ``out``: a dense
         tensor of exactly that shape and dtype."""
         T, H, W, Cn, kind, out = self._pack_args("pack_frames", frames, fmt, out)
-        hip_lib.check(self.lib.svr_pack_frames(_ptr(frames), kind, T, H, W, Cn, hip_lib.PACK_FORMATS[fmt], _ptr(out),
-                                               out.numel() * out.element_size(), self._stream()), "svr_pack_frames")
+        self._launch("svr_pack_frames", _ptr(frames), kind, T, H, W, Cn, hip_lib.PACK_FORMATS[fmt], _ptr(out),
+                     out.numel() * out.element_size())
         return out
 
     def pack_yuv420p10(self, frames, matrix="bt709", range_="tv", siting="center", out=None):
@@ -612,9 +596,8 @@ class HipOps:
         [T, H, W, 3] fp32 / bf16, dense -> uint16 [T, H*W + 2*h2*w2].  One launch on the current stream, no host synchronisation.
         ``out``: a dense tensor of exactly that shape and dtype."""
         T, H, W, _, kind, out = self._pack_args("pack_yuv420p10", frames, "yuv420p10", out, colour=(matrix, range_, siting))
-        hip_lib.check(self.lib.svr_pack_yuv420p10(_ptr(frames), kind, T, H, W, hip_lib.COLOUR_MATRICES[matrix],
-                                                  hip_lib.COLOUR_RANGES[range_], hip_lib.COLOUR_SITINGS[siting], _ptr(out),
-                                                  out.numel() * out.element_size(), self._stream()), "svr_pack_yuv420p10")
+        self._launch("svr_pack_yuv420p10", _ptr(frames), kind, T, H, W, hip_lib.COLOUR_MATRICES[matrix], hip_lib.COLOUR_RANGES[range_],
+                     hip_lib.COLOUR_SITINGS[siting], _ptr(out), out.numel() * out.element_size())
         return out
 
     # ------------------------------------------------------------------ frame signatures (cut detection)
@@ -626,8 +609,7 @@ class HipOps:
         T, H, W, Cn, kind = clip_args("frame_signatures", frames, self.device, min_hw=4, after=lambda T, H, W, _: (
             f"frames of H * W = {H * W} pixels; the int32 counters hold fewer than 2^31" if H * W >= 1 << 31 else None))
         out = self._out("frame_signatures", out, (T, 1024), torch.int32)
-        hip_lib.check(self.lib.svr_frame_signatures(_ptr(frames), kind, T, H, W, Cn, _ptr(out), out.numel() * 4, self._stream()),
-                      "svr_frame_signatures")
+        self._launch("svr_frame_signatures", _ptr(frames), kind, T, H, W, Cn, _ptr(out), out.numel() * 4)
         return out
 
     # ------------------------------------------------------------------ active-area profile (letterbox bars)
@@ -644,8 +626,7 @@ class HipOps:
 
         T, H, W, Cn, kind = clip_args("active_profile", frames, self.device, min_hw=1, after=counters_and_dark)
         out = self._out("active_profile", out, (H + W,), torch.int32)
-        hip_lib.check(self.lib.svr_active_profile(_ptr(frames), kind, T, H, W, Cn, dark, _ptr(out), out.numel() * 4, self._stream()),
-                      "svr_active_profile")
+        self._launch("svr_active_profile", _ptr(frames), kind, T, H, W, Cn, dark, _ptr(out), out.numel() * 4)
         return out
 
     # ------------------------------------------------------------------ PNG streams
@@ -679,9 +660,8 @@ class HipOps:
         if tuple(sizes.shape) != (T,):
             raise ValueError(f"encode_png: sizes must be int64 [{T}], got {tuple(sizes.shape)}")
         scratch = torch.empty(nscratch, dtype=torch.uint8, device=self.device)
-        fn, name = (self.lib.svr_png_encode_runs, "svr_png_encode_runs") if runs else (self.lib.svr_png_encode, "svr_png_encode")
-        hip_lib.check(fn(_ptr(frames), kind, T, H, W, Cn, int(depth), _ptr(scratch), nscratch, _ptr(out), out.shape[1], _ptr(sizes),
-                         self._stream()), name)
+        self._launch("svr_png_encode_runs" if runs else "svr_png_encode", _ptr(frames), kind, T, H, W, Cn, int(depth), _ptr(scratch),
+                     nscratch, _ptr(out), out.shape[1], _ptr(sizes))
         return out, sizes
 
     # ------------------------------------------------------------------ colour correction
@@ -715,8 +695,7 @@ class HipOps:
         ss = self._pixels(style, "wavelet_reconstruct: style", content.shape)
         out, os_ = self._pixels_out(out, content, "wavelet_reconstruct: out", content, style)
         T, _, H, W = content.shape
-        hip_lib.check(self.lib.svr_wavelet_reconstruct(_ptr(content), cs, _ptr(style), ss, _ptr(out), os_, T, H, W, 1, self._stream()),
-                      "svr_wavelet_reconstruct")
+        self._launch("svr_wavelet_reconstruct", _ptr(content), cs, _ptr(style), ss, _ptr(out), os_, T, H, W, 1)
         return out
 
     def lab_planes(self, base, style, c_lab=None, s_lab=None):
@@ -732,8 +711,7 @@ class HipOps:
             if tuple(t.shape) != (3, T * H * W):
                 raise ValueError(f"{name} must be fp32 {(3, T * H * W)}, got {tuple(t.shape)}")
             planes.append(t)
-        hip_lib.check(self.lib.svr_lab_planes(_ptr(base), bs, _ptr(style), ss, _ptr(planes[0]), _ptr(planes[1]), T, H, W, 1,
-                                              self._stream()), "svr_lab_planes")
+        self._launch("svr_lab_planes", _ptr(base), bs, _ptr(style), ss, _ptr(planes[0]), _ptr(planes[1]), T, H, W, 1)
         return planes[0], planes[1]
 
     def lab_merge(self, c_L, m_L, m_a, m_b, luminance_weight, shape, out=None):
@@ -752,8 +730,7 @@ class HipOps:
                     raise ValueError(f"lab_merge: {name} must hold T * H * W = {T * H * W} values, got {tuple(t.shape)}")
         like = torch.empty((T, 3, H, W), dtype=torch.float32, device="meta")
         out, os_ = self._pixels_out(out, like, "lab_merge: out")
-        hip_lib.check(self.lib.svr_lab_merge(_ptr(c_L), _ptr(m_L), _ptr(m_a), _ptr(m_b), w, _ptr(out), os_, T, H, W, 1, self._stream()),
-                      "svr_lab_merge")
+        self._launch("svr_lab_merge", _ptr(c_L), _ptr(m_L), _ptr(m_a), _ptr(m_b), w, _ptr(out), os_, T, H, W, 1)
         return out
 
     def chan_stats(self, content, style, stats=None):
@@ -770,8 +747,7 @@ class HipOps:
         if nbytes <= 0:
             raise ValueError(f"chan_stats: at most 21845 frames per call, got {T}")
         ws = torch.empty(nbytes // 8, dtype=torch.float64, device=self.device)
-        hip_lib.check(self.lib.svr_chan_stats(_ptr(content), cs, _ptr(style), ss, _ptr(stats), T, H, W, 1, _ptr(ws), nbytes,
-                                              self._stream()), "svr_chan_stats")
+        self._launch("svr_chan_stats", _ptr(content), cs, _ptr(style), ss, _ptr(stats), T, H, W, 1, _ptr(ws), nbytes)
         return stats
 
     def adain(self, content, style, eps=1e-5, out=None):
@@ -780,8 +756,7 @@ class HipOps:
         cs = self._pixels(content, "adain: content")
         out, os_ = self._pixels_out(out, content, "adain: out")
         T, _, H, W = content.shape
-        hip_lib.check(self.lib.svr_adain_apply(_ptr(content), cs, _ptr(stats), float(eps), _ptr(out), os_, T, H, W, 1, self._stream()),
-                      "svr_adain_apply")
+        self._launch("svr_adain_apply", _ptr(content), cs, _ptr(stats), float(eps), _ptr(out), os_, T, H, W, 1)
         return out
 
     # (colorfix.sort_key / rank_match_spec are the specification, bit for bit; csrc/svr_rank.hip.)
@@ -811,7 +786,7 @@ class HipOps:
 
         sorted_out = out(sorted_out, torch.float32, "sort_f32: sorted_out")
         idx = out(index_out, torch.int32, "sort_f32: index_out") if index else None      # keys only: no index is allocated
-        hip_lib.check(self.lib.svr_sort_f32(_ptr(keys), n, _ptr(sorted_out), _ptr(idx), _ptr(ws), nbytes, self._stream()), "svr_sort_f32")
+        self._launch("svr_sort_f32", _ptr(keys), n, _ptr(sorted_out), _ptr(idx), _ptr(ws), nbytes)
         return sorted_out, idx
 
     def rank_match(self, source, reference, out=None):
@@ -829,8 +804,7 @@ class HipOps:
         if tuple(out.shape) != tuple(source.shape):
             raise ValueError(f"rank_match: out must be fp32 {tuple(source.shape)}, got {tuple(out.shape)}")
         ws, nbytes = self._rank_workspace(n, "rank_match")
-        hip_lib.check(self.lib.svr_rank_match(_ptr(source), _ptr(reference), n, _ptr(out), _ptr(ws), nbytes, self._stream()),
-                      "svr_rank_match")
+        self._launch("svr_rank_match", _ptr(source), _ptr(reference), n, _ptr(out), _ptr(ws), nbytes)
         return out
 
     # (colorfix.hsv_spec / wavelet_adaptive_spec / hue_match_spec are the specification; csrc/svr_hsv.hip.)
@@ -854,8 +828,7 @@ class HipOps:
             if tuple(t.shape) != (k, T * H * W):
                 raise ValueError(f"{name} must be fp32 {(k, T * H * W)}, got {tuple(t.shape)}")
             planes.append(t)
-        hip_lib.check(self.lib.svr_hsv_planes(_ptr(content), cs, _ptr(style), ss, _ptr(planes[0]), _ptr(planes[1]), T, H, W, 1,
-                                              self._stream()), "svr_hsv_planes")
+        self._launch("svr_hsv_planes", _ptr(content), cs, _ptr(style), ss, _ptr(planes[0]), _ptr(planes[1]), T, H, W, 1)
         return planes[0], planes[1]
 
     def hue_match(self, c_h, c_s, s_h, s_s, out=None):
@@ -875,8 +848,7 @@ class HipOps:
         if nbytes <= 0:
             raise ValueError(f"hue_match: between 1 and 2^30 elements per plane, got {n}")
         ws = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        hip_lib.check(self.lib.svr_hue_match(_ptr(c_h), _ptr(c_s), _ptr(s_h), _ptr(s_s), n, _ptr(out), _ptr(ws), nbytes, self._stream()),
-                      "svr_hue_match")
+        self._launch("svr_hue_match", _ptr(c_h), _ptr(c_s), _ptr(s_h), _ptr(s_s), n, _ptr(out), _ptr(ws), nbytes)
         return out
 
     def hsv_merge(self, h, sat, v, shape, out=None):
@@ -887,7 +859,7 @@ class HipOps:
             self._plane(t, T * H * W, f"hsv_merge: {name}")
         like = torch.empty((T, 3, H, W), dtype=torch.float32, device="meta")
         out, os_ = self._pixels_out(out, like, "hsv_merge: out")
-        hip_lib.check(self.lib.svr_hsv_merge(_ptr(h), _ptr(sat), _ptr(v), _ptr(out), os_, T, H, W, 1, self._stream()), "svr_hsv_merge")
+        self._launch("svr_hsv_merge", _ptr(h), _ptr(sat), _ptr(v), _ptr(out), os_, T, H, W, 1)
         return out
 
     def adaptive_blend(self, base, content, style, h, sat, v, threshold=0.15, sharpness=5.0, out=None):
@@ -900,9 +872,8 @@ class HipOps:
         for t, name in ((h, "h"), (sat, "sat"), (v, "v")):
             self._plane(t, T * H * W, f"adaptive_blend: {name}")
         out, os_ = self._pixels_out(out, base, "adaptive_blend: out", base, content, style)
-        hip_lib.check(self.lib.svr_adaptive_blend(_ptr(base), bs, _ptr(content), cs, _ptr(style), ss, _ptr(h), _ptr(sat), _ptr(v),
-                                                  float(threshold), float(sharpness), _ptr(out), os_, T, H, W, 1, self._stream()),
-                      "svr_adaptive_blend")
+        self._launch("svr_adaptive_blend", _ptr(base), bs, _ptr(content), cs, _ptr(style), ss, _ptr(h), _ptr(sat), _ptr(v),
+                     float(threshold), float(sharpness), _ptr(out), os_, T, H, W, 1)
         return out
 
     # ------------------------------------------------------------------ packed input frames
@@ -917,9 +888,8 @@ class HipOps:
             raise ValueError(f"unpack_frames: {e}") from None
         self._chk(packed, None, "unpack_frames: packed")
         out = self._out("unpack_frames", out, (T, H, W, C), torch.float32)
-        hip_lib.check(self.lib.svr_unpack_frames(_ptr(packed), packed.numel() * packed.element_size(), hip_lib.UNPACK_FORMATS[fmt],
-                                                 T, H, W, C, hip_lib.YUV_MATRICES[matrix], hip_lib.YUV_RANGES[range_], _ptr(out),
-                                                 out.numel() * out.element_size(), self._stream()), "svr_unpack_frames")
+        self._launch("svr_unpack_frames", _ptr(packed), packed.numel() * packed.element_size(), hip_lib.UNPACK_FORMATS[fmt], T, H, W, C,
+                     hip_lib.YUV_MATRICES[matrix], hip_lib.YUV_RANGES[range_], _ptr(out), out.numel() * out.element_size())
         return out
 
     # ------------------------------------------------------------------ interlaced sources
@@ -940,10 +910,9 @@ class HipOps:
                 self._chk(frame, None, f"deinterlace: {name}")
         n_out = T * (2 if rate == "field" else 1)
         out = self._out("deinterlace", out, (n_out,) + tuple(shape[1:]), packed.dtype)
-        hip_lib.check(self.lib.svr_deinterlace(_ptr(packed), packed.numel() * packed.element_size(), _ptr(before), _ptr(after),
-                                               hip_lib.UNPACK_FORMATS[fmt], T, H, W, C, hip_lib.FIELD_ORDERS[order],
-                                               hip_lib.DEINT_RATES[rate], _ptr(out), out.numel() * out.element_size(), self._stream()),
-                      "svr_deinterlace")
+        self._launch("svr_deinterlace", _ptr(packed), packed.numel() * packed.element_size(), _ptr(before), _ptr(after),
+                     hip_lib.UNPACK_FORMATS[fmt], T, H, W, C, hip_lib.FIELD_ORDERS[order], hip_lib.DEINT_RATES[rate], _ptr(out),
+                     out.numel() * out.element_size())
         return out
 
     # ------------------------------------------------------------------ field matching
@@ -962,9 +931,8 @@ class HipOps:
             if frame is not None:
                 self._chk(frame, None, f"comb_counts: {name}")
         out = self._out("comb_counts", out, (T, 3, 2), torch.int32)
-        hip_lib.check(self.lib.svr_comb_counts(_ptr(packed), packed.numel() * packed.element_size(), _ptr(before), _ptr(after),
-                                               hip_lib.UNPACK_FORMATS[fmt], T, H, W, C, hip_lib.FIELD_ORDERS[order], thr, _ptr(out),
-                                               out.numel() * 4, self._stream()), "svr_comb_counts")
+        self._launch("svr_comb_counts", _ptr(packed), packed.numel() * packed.element_size(), _ptr(before), _ptr(after),
+                     hip_lib.UNPACK_FORMATS[fmt], T, H, W, C, hip_lib.FIELD_ORDERS[order], thr, _ptr(out), out.numel() * 4)
         return out
 
     def field_select(self, packed, deint, cnt, fmt, T, H, W, C, order, mi, before=None, after=None, out=None, modes=None, stats=None):
@@ -990,12 +958,10 @@ class HipOps:
         if tuple(cnt.shape) != (T, 3, 2):
             raise ValueError(f"field_select: cnt must be {(T, 3, 2)}, got {tuple(cnt.shape)}")
         out = self._out("field_select", out, tuple(shape), packed.dtype)
-        hip_lib.check(self.lib.svr_field_select(_ptr(packed), packed.numel() * packed.element_size(), _ptr(before), _ptr(after),
-                                                _ptr(deint), deint.numel() * deint.element_size(), _ptr(cnt), cnt.numel() * 4,
-                                                hip_lib.UNPACK_FORMATS[fmt], T, H, W, C, hip_lib.FIELD_ORDERS[order], mi, _ptr(out),
-                                                out.numel() * out.element_size(), self._opt(modes, torch.int32, "field_select: modes", T),
-                                                self._opt(stats, torch.int64, "field_select: stats", 6), self._stream()),
-                      "svr_field_select")
+        self._launch("svr_field_select", _ptr(packed), packed.numel() * packed.element_size(), _ptr(before), _ptr(after), _ptr(deint),
+                     deint.numel() * deint.element_size(), _ptr(cnt), cnt.numel() * 4, hip_lib.UNPACK_FORMATS[fmt], T, H, W, C,
+                     hip_lib.FIELD_ORDERS[order], mi, _ptr(out), out.numel() * out.element_size(),
+                     self._opt(modes, torch.int32, "field_select: modes", T), self._opt(stats, torch.int64, "field_select: stats", 6))
         return out
 
     # ------------------------------------------------------------------ GGUF blocks expanded at load
@@ -1019,6 +985,5 @@ class HipOps:
         if blocks.data_ptr() % 32:
             blocks = blocks.clone()
         kind = 1 if out_dtype == torch.float32 else 0                        # SVR_STORE_FP32 / SVR_STORE_BF16
-        hip_lib.check(self.lib.svr_dequant_gguf(_ptr(blocks), int(ggml_type), n, _ptr(out), kind, out.numel() * out.element_size(),
-                                                self._stream()), "svr_dequant_gguf")
+        self._launch("svr_dequant_gguf", _ptr(blocks), int(ggml_type), n, _ptr(out), kind, out.numel() * out.element_size())
         return out

@@ -75,6 +75,26 @@ def test_rmsnorm_mod_rows_in_flight(hip, kind, dim):
             gout.check(f"rmsnorm_mod rows {rows}")
 
 
+@pytest.mark.parametrize("kind", KINDS, ids=KIND_IDS)
+def test_rmsnorm_mod_every_chunk_count(hip, kind):
+    """rmsnorm_mod_kernel<NC, kind> for every NC = ceil(dim / 512) in 1..8 the entry point can select, at the last dim of an NC
+    (512 k: every lane holds k chunks) and the one before (512 k - 8: lane 63 holds one fewer).  9 rows: three workgroups of four
+    waves, the last with one row."""
+    rows = 9
+    ramp = torch.exp2(((torch.arange(rows, device="cuda") * 7) % 11 - 5).float())[:, None]
+    gout = Pool()
+    for dim in [512 * k - d for k in range(1, 9) for d in (8, 0)]:
+        x = rnd(rows, dim, scale=2.0, dtype=F32) * ramp
+        x = (x * H16_SCALE).to(H16) if kind == H16 else x.to(kind)
+        w, sc, sh = (rnd(dim, dtype=F32, seed=s) for s in (1, 2, 3))
+        for kw in (dict(), dict(scale=sc, shift=sh), dict(w=w, scale=sc, shift=sh)):
+            out = gout(rows + 1, dim, dtype=BF16, init=nans(rows + 1, dim))
+            hip.rmsnorm_mod(x, out[:rows], 1e-5, **kw)
+            assert bool(torch.isnan(out[rows]).all())                               # nothing behind the last row
+            le.check_rmsnorm_mod(out[:rows], x, 1e-5, name=f"rmsnorm_mod dim {dim} {sorted(kw)}", **kw)
+            gout.check(f"rmsnorm_mod dim {dim}")
+
+
 # ------------------------------------------------------------------ qknorm_rope
 def _rope_tables(n_pos, n_freq):
     ang = torch.arange(n_pos, dtype=F32)[:, None] * (10000.0 ** (-torch.arange(n_freq, dtype=F32) / max(n_freq, 1)))[None, :]
