@@ -30,6 +30,7 @@
 #include "svr_active.hip"
 #include "svr_deinterlace.hip"
 #include "svr_fieldmatch.hip"
+#include "svr_decimate.hip"
 
 using namespace svr;
 
@@ -1249,20 +1250,29 @@ struct FieldClip {
     struct Plane { int64_t off; int R; int64_t N; int s; } planes[3];
     int n_planes;
 };
-static const char* field_clip_error(const void* packed, const void* before, const void* after, int32_t fmt, int32_t T, int32_t H,
-                                    int32_t W, int32_t C, int32_t order) {
+// (in two steps, so that an entry point with an argument of its own between them -- field matching's order -- keeps its place in the
+// order of the refusals, and one without it -- decimation -- takes the two as they are)
+static const char* clip_shape_error(int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C) {
     const bool yuv = fmt == SVR_UNPACK_YUV420P8 || fmt == SVR_UNPACK_YUV420P10;
-    const bool wide = fmt == SVR_UNPACK_RGB16 || fmt == SVR_UNPACK_YUV420P10;
     if (T < 1 || H < 1 || W < 1) return "need T >= 1, H >= 1, W >= 1";
     if ((int64_t)H * W > ((int64_t)1 << 40) / T) return "T * H * W must not exceed 2^40 pixels";
     if (fmt != SVR_UNPACK_RGB8 && fmt != SVR_UNPACK_BGR8 && fmt != SVR_UNPACK_RGB16 && !yuv)
         return "fmt must be SVR_UNPACK_RGB8, SVR_UNPACK_BGR8, SVR_UNPACK_RGB16, SVR_UNPACK_YUV420P8 or SVR_UNPACK_YUV420P10";
     if (yuv ? C != 3 : (C != 3 && C != 4)) return yuv ? "C must be 3 for the yuv420p formats" : "C must be 3 or 4";
-    if (order != SVR_FIELD_TFF && order != SVR_FIELD_BFF) return "order must be SVR_FIELD_TFF or SVR_FIELD_BFF";
+    return nullptr;
+}
+static const char* clip_alignment_error(const void* packed, const void* before, const void* after, int32_t fmt) {
+    const bool wide = fmt == SVR_UNPACK_RGB16 || fmt == SVR_UNPACK_YUV420P10;
     if (wide && (uintptr_t)packed % 2) return "packed is not aligned to 2 bytes";
     if (wide && (uintptr_t)before % 2) return "before is not aligned to 2 bytes";
     if (wide && (uintptr_t)after % 2) return "after is not aligned to 2 bytes";
     return nullptr;
+}
+static const char* field_clip_error(const void* packed, const void* before, const void* after, int32_t fmt, int32_t T, int32_t H,
+                                    int32_t W, int32_t C, int32_t order) {
+    if (const char* why = clip_shape_error(fmt, T, H, W, C)) return why;
+    if (order != SVR_FIELD_TFF && order != SVR_FIELD_BFF) return "order must be SVR_FIELD_TFF or SVR_FIELD_BFF";
+    return clip_alignment_error(packed, before, after, fmt);
 }
 static FieldClip field_clip(int32_t fmt, int32_t H, int32_t W, int32_t C) {
     FieldClip c;
@@ -1372,6 +1382,88 @@ int svr_field_select(const void* packed, int64_t packed_bytes, const void* befor
         if (int rc = e.launched()) return rc;
     }
     return 0;
+}
+
+// ---- decimation on the packed planes (svr_decimate.hip), after field matching: the clip's own arguments are refused in field
+// matching's words (a clip here has no order and no ``after``)
+int svr_frame_diffs(const void* packed, int64_t packed_bytes, const void* before, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,
+                    void* diff, int64_t diff_bytes, void* stream) {
+    const Launch e{"svr_frame_diffs", stream};
+    const char* why = nullptr;
+    if (!packed) why = "packed is a null pointer";
+    else if (!diff) why = "diff is a null pointer";
+    else if ((why = clip_shape_error(fmt, T, H, W, C))) {}
+    else if ((why = clip_alignment_error(packed, before, nullptr, fmt))) {}
+    else if ((uintptr_t)diff % 4) why = "diff is not aligned to 4 bytes";
+    if (why) return e.refuse("%s", why);
+    const FieldClip c = field_clip(fmt, H, W, C);
+    const int64_t need_in = (int64_t)T * c.frame * c.size, need_diff = (int64_t)T * 4;
+    if (packed_bytes != need_in) return e.wrong_size("packed_bytes", packed_bytes, "the format needs", need_in);
+    if (diff_bytes != need_diff) return e.wrong_size("diff_bytes", diff_bytes, "int32 [T] needs", need_diff);
+    if (rank_overlap(diff, need_diff, packed, need_in)) return e.refuse("diff overlaps packed");
+    if (before && rank_overlap(diff, need_diff, before, c.frame * c.size)) return e.refuse("diff overlaps before");
+    const hipStream_t s = (hipStream_t)stream;
+    if (int rc = e.hip(hipMemsetAsync(diff, 0, (size_t)need_diff, s), "zeroing diff")) return rc;
+    const FieldClip::Plane& p = c.planes[0];
+    const bool vec = (uintptr_t)packed % 16 == 0 && (uintptr_t)before % 16 == 0 && c.frame * c.size % 16 == 0 && p.N * c.size % 16 == 0;
+    const int unit = vec ? 16 / c.size : 1;                                  // samples per lane column
+    const int per = DEC_BLOCK * p.s / unit, cb = DEC_LANES / per;            // lanes per block column, block columns per workgroup
+    const int64_t block_cols = (p.N / p.s + DEC_BLOCK - 1) / DEC_BLOCK;
+    const int chunks = (int)((block_cols + cb - 1) / cb);
+    const unsigned grid = capped_grid((int64_t)T * ((p.R + DEC_BLOCK - 1) / DEC_BLOCK) * chunks * 256);
+    with_const<2, 1>(c.size, [&](auto BYTES) { with_const<1, 0>(vec ? 1 : 0, [&](auto VEC) {
+        typedef typename std::conditional<BYTES() == 2, unsigned short, unsigned char>::type S;
+        hipLaunchKernelGGL((diff_kernel<S, VEC()>), dim3(grid), dim3(DEC_LANES), 0, s, (const S*)packed, (const S*)before, T, c.frame, p.R,
+                           p.N, per, cb, chunks, p.N / unit, (int*)diff);
+    }); });
+    return e.launched();
+}
+
+int svr_decimate_select(const void* packed, int64_t packed_bytes, const void* diff, int64_t diff_bytes, int32_t fmt, int32_t T, int32_t H,
+                        int32_t W, int32_t C, int32_t dup, void* out, int64_t out_bytes, void* drops, void* stats, void* stream) {
+    const Launch e{"svr_decimate_select", stream};
+    const bool wide = fmt == SVR_UNPACK_RGB16 || fmt == SVR_UNPACK_YUV420P10;
+    const char* why = nullptr;
+    if (!packed) why = "packed is a null pointer";
+    else if (!diff) why = "diff is a null pointer";
+    else if (!out) why = "out is a null pointer";
+    else if ((why = clip_shape_error(fmt, T, H, W, C))) {}
+    else if ((why = clip_alignment_error(packed, nullptr, nullptr, fmt))) {}
+    else if (dup < 0 || dup > (1 << 18)) why = "dup must lie in 0..262144";
+    else if (wide && (uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
+    else if ((uintptr_t)diff % 4) why = "diff is not aligned to 4 bytes";
+    else if ((uintptr_t)drops % 4) why = "drops is not aligned to 4 bytes";
+    else if ((uintptr_t)stats % 8) why = "stats is not aligned to 8 bytes";
+    if (why) return e.refuse("%s", why);
+    const FieldClip c = field_clip(fmt, H, W, C);
+    const int cycles = T / DEC_CYCLE;
+    const int64_t one = c.frame * c.size, need = (int64_t)T * one, need_diff = (int64_t)T * 4, need_out = (int64_t)(T - cycles) * one;
+    if (packed_bytes != need) return e.wrong_size("packed_bytes", packed_bytes, "the format needs", need);
+    if (diff_bytes != need_diff) return e.wrong_size("diff_bytes", diff_bytes, "int32 [T] needs", need_diff);
+    if (out_bytes != need_out) return e.wrong_size("out_bytes", out_bytes, "the T - T / 5 frames need", need_out);
+    // no output may overlap an input, or another output (a clip without a whole cycle has no drops)
+    struct Span { const char* name; const void* at; int64_t bytes; };
+    const Span inputs[] = {{"packed", packed, need}, {"diff", diff, need_diff}};
+    const Span outputs[] = {{"out", out, need_out}, {"drops", cycles ? drops : nullptr, (int64_t)cycles * 4}, {"stats", stats, 48}};
+    for (int o = 0; o < 3; ++o) {
+        if (!outputs[o].at) continue;
+        for (const Span& in : inputs)
+            if (rank_overlap(outputs[o].at, outputs[o].bytes, in.at, in.bytes)) return e.refuse("%s overlaps %s", outputs[o].name, in.name);
+        for (int q = 0; q < o; ++q)
+            if (outputs[q].at && rank_overlap(outputs[o].at, outputs[o].bytes, outputs[q].at, outputs[q].bytes))
+                return e.refuse("%s overlaps %s", outputs[o].name, outputs[q].name);
+    }
+    const bool vec = (uintptr_t)packed % 16 == 0 && (uintptr_t)out % 16 == 0 && one % 16 == 0;
+    const int64_t units = vec ? one / 16 : c.frame;
+    const int64_t bound = ((int64_t)dup * c.planes[0].s) << (fmt == SVR_UNPACK_RGB16 ? 8 : fmt == SVR_UNPACK_YUV420P10 ? 2 : 0);
+    const unsigned grid = capped_grid((int64_t)(T - cycles) * units);
+    with_const<2, 1>(c.size, [&](auto BYTES) { with_const<1, 0>(vec ? 1 : 0, [&](auto VEC) {
+        typedef typename std::conditional<BYTES() == 2, unsigned short, unsigned char>::type S;
+        hipLaunchKernelGGL((decimate_select_kernel<S, VEC()>), dim3(grid), dim3(DEC_LANES), 0, (hipStream_t)stream, (const S*)packed,
+                           (const int*)diff, T, c.frame, units, bound, (S*)out, cycles ? (int*)drops : nullptr,
+                           (unsigned long long*)stats);
+    }); });
+    return e.launched();
 }
 
 // ---- GGUF blocks expanded at load (svr_gguf.hip)

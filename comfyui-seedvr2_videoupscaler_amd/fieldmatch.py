@@ -60,7 +60,8 @@ block's eight tested rows.  Both come from SYNTHETIC clips only (tests/fieldmatc
 that is why ``ENABLED = False`` ships: turning it on waits for someone who has measured them on real clips.  No test depends on
 DEFAULTS.
 Known limits:
-  * no decimation: a telecined clip keeps its one repeated picture in five, and its frame rate;
+  * no decimation: a telecined clip keeps its one repeated picture in five, and its frame rate -- decimate.py, the stage that runs
+    after this one, drops that picture;
   * a source tagged progressive is not examined;
   * plane 0 decides for all planes;
   * noise above thr reads as combing;

@@ -964,6 +964,47 @@ class HipOps:
                      self._opt(modes, torch.int32, "field_select: modes", T), self._opt(stats, torch.int64, "field_select: stats", 6))
         return out
 
+    # ------------------------------------------------------------------ decimation
+    def frame_diffs(self, packed, fmt, T, H, W, C, before=None, out=None):
+        """Per frame the largest 32 x 32 block sum of its absolute difference from the frame before it, on plane 0 (decimate.py is the
+        specification; csrc/svr_decimate.hip): ``packed`` as deinterlace takes it, ``before`` one packed frame or None (diff[0] is
+        then 2^31 - 1) -> int32 [T].  The diffs are zeroed and one kernel is launched on the current stream, no host
+        synchronisation.  ``out``: a dense int32 [T] tensor apart from every input."""
+        from . import decimate
+        try:
+            decimate.check_arguments(packed, fmt, T, H, W, C, before=before)
+        except ValueError as e:
+            raise ValueError(f"frame_diffs: {e}") from None
+        self._chk(packed, None, "frame_diffs: packed")
+        if before is not None:
+            self._chk(before, None, "frame_diffs: before")
+        out = self._out("frame_diffs", out, (T,), torch.int32)
+        self._launch("svr_frame_diffs", _ptr(packed), packed.numel() * packed.element_size(), _ptr(before), hip_lib.UNPACK_FORMATS[fmt],
+                     T, H, W, C, _ptr(out), out.numel() * 4)
+        return out
+
+    def decimate_select(self, packed, diff, fmt, T, H, W, C, dup, out=None, drops=None, stats=None):
+        """The frames decimation keeps (decimate.select_torch of decimate.drops_torch(diff); csrc/svr_decimate.hip): ``diff``
+        frame_diffs' int32 [T], read on the device in stream order; ``dup`` in 0..2^18 -> T - T // 5 frames in packed's dtype and
+        layout.  ``drops`` int32 [T // 5] receives the dropped positions, ``stats`` int64 [6] (decimate.Stats.counts) is added to;
+        both may be None.  One launch on the current stream, no host synchronisation.  ``out``: a dense tensor of that shape and
+        packed's dtype, apart from every input."""
+        from . import decimate
+        try:
+            shape = decimate.check_arguments(packed, fmt, T, H, W, C, dup)
+        except ValueError as e:
+            raise ValueError(f"decimate_select: {e}") from None
+        self._chk(packed, None, "decimate_select: packed")
+        self._chk(diff, torch.int32, "decimate_select: diff")
+        if tuple(diff.shape) != (T,):
+            raise ValueError(f"decimate_select: diff must be {(T,)}, got {tuple(diff.shape)}")
+        out = self._out("decimate_select", out, (T - T // decimate.CYCLE,) + tuple(shape[1:]), packed.dtype)
+        self._launch("svr_decimate_select", _ptr(packed), packed.numel() * packed.element_size(), _ptr(diff), diff.numel() * 4,
+                     hip_lib.UNPACK_FORMATS[fmt], T, H, W, C, dup, _ptr(out), out.numel() * out.element_size(),
+                     self._opt(drops, torch.int32, "decimate_select: drops", T // decimate.CYCLE),
+                     self._opt(stats, torch.int64, "decimate_select: stats", 6))
+        return out
+
     # ------------------------------------------------------------------ GGUF blocks expanded at load
     def dequant_gguf(self, blocks, ggml_type, out_dtype=BF16, out=None):
         """GGUF blocks expanded on the device (gguf.py is the specification, bit for bit; csrc/svr_gguf.hip): ``blocks`` a dense uint8

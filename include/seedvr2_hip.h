@@ -74,6 +74,12 @@
  *                                              multiples of 16 bytes, element accesses otherwise
  *   svr_field_select                           as svr_deinterlace, deint counting as an input (cnt and modes 4, stats 8); per plane,
  *                                              16-byte loads and stores or element accesses by svr_deinterlace's rule
+ *   svr_frame_diffs                            element alignment is enough (2 bytes for the 16-bit formats, diff 4); 16-byte loads where
+ *                                              packed and before are 16-byte aligned and the frame and plane 0's rows are
+ *                                              multiples of 16 bytes, element accesses otherwise
+ *   svr_decimate_select                        element alignment is enough (2 bytes for the 16-bit formats, diff and drops 4, stats 8);
+ *                                              16-byte loads and stores where packed and out are 16-byte aligned and the frame is a
+ *                                              multiple of 16 bytes, element accesses otherwise
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -115,6 +121,8 @@ extern "C" {
  * svr_unpack_frames widens them).  A new symbol only.
  * v9, additive: + svr_comb_counts() / svr_field_select() (field matching: per frame the combing of the three weaves its kept field
  * can make, and the frames copied from the first clean weave or from the deinterlaced clip).  New symbols only.
+ * v9, additive: + svr_frame_diffs() / svr_decimate_select() (decimation: per frame the largest block sum of its difference from
+ * the frame before it, and of every cycle of five frames the four that are not the smallest).  New symbols only.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -652,6 +660,31 @@ int svr_comb_counts(const void* packed, int64_t packed_bytes, const void* before
 int svr_field_select(const void* packed, int64_t packed_bytes, const void* before, const void* after, const void* deint,
                      int64_t deint_bytes, const void* cnt, int64_t cnt_bytes, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,
                      int32_t order, int32_t mi, void* out, int64_t out_bytes, void* modes, void* stats, void* stream);
+
+/* ---- decimation -------------------------------------------------------------------------------- */
+/* decimate.py (the specification, bit for bit).  `packed`, fmt, T, H, W, C are svr_deinterlace's: T frames in one of the SVR_UNPACK_*
+ * formats -- normally svr_field_select's output --; `before` one frame, the frame ahead of the clip, or NULL at the clip's start.
+ * There is no order, no `after` and no mirror.
+ * svr_frame_diffs: `diff` int32 [T].  Only plane 0 is read (Y, or the interleaved RGB plane: R = H rows of N samples, channels s
+ *   apart), samples as stored.  Blocks are 32 plane rows by 32 pixel columns (block row r / 32, block column (i / s) / 32, partial
+ *   at the edges).  diff[t] = the largest block sum of |F[t][r][i] - F[t-1][r][i]| (at most 32 * 32 * 4 * 65535 < 2^31); diff[0]
+ *   compares with `before`, and is 2^31 - 1 where `before` is NULL.  The call zeroes `diff` on `stream`; ONE launch follows (block
+ *   sums in LDS, integer atomic max to `diff`: two runs give the same bits).
+ * svr_decimate_select: `diff` as above, read from device memory in stream order -> `out` T - T / 5 frames.  Per whole cycle c of five
+ *   frames the drop is the position 0..4 of the smallest of diff[5c .. 5c + 4], the FIRST of a tie; the cycle's other four frames
+ *   are copied in their order, and so are the T % 5 frames of a trailing partial cycle (T < 5: a copy).  `drops` int32 [T / 5] and
+ *   `stats` int64 [6] may be NULL (and `drops` is not looked at where T < 5): drops[c] is the drop; stats is ADDED to: entries 0..4
+ *   the cycles per drop position, entry 5 the dropped frames with diff > dup * s << shift (s of plane 0; shift 0 for the 8-bit
+ *   formats, 2 for SVR_UNPACK_YUV420P10, 8 for SVR_UNPACK_RGB16; dup in 0..2^18), which decides nothing (one lane per cycle, 64-bit
+ *   integer atomic adds).  ONE launch.
+ * Every argument is checked before anything is enqueued: null pointers, an unknown fmt, a C the format does not take, sizes below 1
+ * (T * H * W <= 2^40 pixels), dup outside 0..2^18, byte counts other than EXACTLY the format's (T - T / 5 frames for out) and 4 T for
+ * diff, a pointer not aligned to its element, an output (diff; out, drops, stats) overlapping an input or another output.  No
+ * host synchronisation, no workspace. */
+int svr_frame_diffs(const void* packed, int64_t packed_bytes, const void* before, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,
+                    void* diff, int64_t diff_bytes, void* stream);
+int svr_decimate_select(const void* packed, int64_t packed_bytes, const void* diff, int64_t diff_bytes, int32_t fmt, int32_t T, int32_t H,
+                        int32_t W, int32_t C, int32_t dup, void* out, int64_t out_bytes, void* drops, void* stats, void* stream);
 
 /* ---- GGUF block-quantised weights, expanded at load ------------------------------------------- */
 /* gguf.py (the specification, bit for bit): `n_blocks` consecutive blocks of one ggml type -> n_blocks * block size values, each

@@ -46,7 +46,13 @@ two parsers by ``ast``), so existing scripts keep working.  What the flags DO is
     (a progressive or telecined picture comes back bit for bit) and deinterlaces only the frames without one (fieldmatch.py /
     csrc/svr_fieldmatch.hip), with fieldmatch.DEFAULTS.  One frame out per frame in, the source's frame rate.  The job ends with
     one line: the frames per decision, and whether the comb counts agree with the tag's order.  It takes precedence over
-    deinterlace.ENABLED.
+    deinterlace.ENABLED;
+  * decimation has no flag either: where decimate.ENABLED is set (it ships off) and the tag names an order,
+    FrameSource matches the fields as above and then drops, of every five matched frames, the one that differs least from its
+    predecessor -- a 3:2 telecined clip's repeated picture -- on the packed planes (decimate.py / csrc/svr_decimate.hip), with
+    decimate.DEFAULTS.  Four frames out per five in, the writer gets 4/5 of the source's frame rate; a trailing partial cycle is
+    kept whole.  The job ends with one more line: the cycles, where in the cycle the drops fell and how many dropped frames were
+    no duplicates.  It takes precedence over fieldmatch.ENABLED.
 """
 import argparse
 import json
@@ -138,15 +144,24 @@ def _fieldmatch():
     return importlib.import_module(f"{PKG}.fieldmatch")
 
 
+def _decimate():
+    import importlib
+    return importlib.import_module(f"{PKG}.decimate")
+
+
 def source_fields(tag, rank: int):
-    """ffprobe's field_order tag -> FrameSource's ``fields``: (order, fieldmatch.RATE) where the tag names an order and
+    """ffprobe's field_order tag -> FrameSource's ``fields``: (order, decimate.RATE) where the tag names an order and
+    decimate.ENABLED is set (it ships off); else (order, fieldmatch.RATE) where the tag names an order and
     fieldmatch.ENABLED is set (it ships off); else (order, deinterlace.RATE) where the tag names an order and
-    deinterlace.ENABLED is set, else None -- with one warning line on rank 0 where the tag says interlaced and both switches are off
+    deinterlace.ENABLED is set, else None -- with one warning line on rank 0 where the tag says interlaced and all switches are off
     (the shipped state): the frames are then upscaled as stored."""
     deinterlace = _deinterlace()
     order = deinterlace.field_order(tag)
     if order is None:
         return None
+    decimate = _decimate()
+    if decimate.ENABLED:
+        return order, decimate.RATE
     fieldmatch = _fieldmatch()
     if fieldmatch.ENABLED:
         return order, fieldmatch.RATE
@@ -164,6 +179,16 @@ def field_summary(stats, order: str) -> str:
     return (f"Field matching ({order}): {r['stored']} frames as stored, {r['prev']} matched to the previous frame, {r['next']} matched to "
             f"the next, {r['deinterlaced']} deinterlaced; combed samples against the previous : next frame over the deinterlaced ones "
             f"{r['sum_prev']} : {r['sum_next']}, which {r['verdict']} the field_order tag")
+
+
+def decimate_summary(stats) -> str:
+    """The one line a decimated job ends with (decimate.Stats.report(): the feature's only read-back)."""
+    r = stats.report()
+    line = (f"Decimation: {r['cycles']} cycles of five frames, the dropped frame at positions 0..4 in "
+            f"{' / '.join(str(n) for n in r['positions'])} of them; {r['not_duplicates']} of the dropped frames were not duplicates")
+    if 2 * r["not_duplicates"] > r["cycles"]:
+        line += ", so the source does not look telecined"
+    return line
 
 
 def output_depth(inp: str, info: Optional[dict] = None) -> int:
@@ -502,10 +527,17 @@ class FrameSource:
     ``fields`` = (order, "match") (fieldmatch.RATE): field matching instead, with the same context and the same one-buffer lead: the
     chunks, concatenated, are fieldmatch.field_match_torch of the whole clip followed by unpack_frames_torch; as many frames as were
     read, ``fps`` unchanged.  ``match``: dict(thr=, mi=), fieldmatch.DEFAULTS where None.  ``field_stats``: the fieldmatch.Stats the
-    chunks add to on the device (None for every other source)."""
+    chunks add to on the device (None for every other source).
+    ``fields`` = (order, "decimate") (decimate.RATE): field matching exactly as above -- the context, the one-buffer lead, ``match``
+    and ``field_stats`` are the same -- and then decimation of the matched packed frames.  The source carries, on the device, the
+    matched frames that do not yet fill a cycle of five (at most 4) and the matched frame ahead of them; from each buffer it emits
+    whole cycles only, a buffer that completes no cycle yields nothing, and the end of the stream emits the partial cycle as it is.
+    For any chunk size the chunks, concatenated, are decimate.decimate_torch of fieldmatch.field_match_torch of the whole clip
+    followed by unpack_frames_torch; ``fps`` is 4/5 of the source's.  ``decimate``: dict(dup=), decimate.DEFAULTS where None.
+    ``decimate_stats``: the decimate.Stats the chunks add to on the device (None for every other source)."""
 
     def __init__(self, exe: str, path: str, info: dict, chunk_size: int, skip: int = 0, cap: int = 0, ops=None, device="cpu",
-                 fields=None, match=None):
+                 fields=None, match=None, decimate=None):
         import importlib
         import tempfile
         import torch
@@ -515,18 +547,25 @@ class FrameSource:
         self.raw, self.fmt, self.C, self.matrix, self.range_ = route_input(info)
         self.H, self.W, self.fps = info["height"], info["width"], info["fps"]
         self.fields, self.match, self.field_stats = fields, None, None
+        self.decimate, self.decimate_stats = None, None
         if fields is not None:
             self.deinterlace = _deinterlace()
             self.fieldmatch = _fieldmatch()
+            self.decimation = _decimate()
             order, rate = fields
-            rates = self.deinterlace.RATES + (self.fieldmatch.RATE,)
+            rates = self.deinterlace.RATES + (self.fieldmatch.RATE, self.decimation.RATE)
             if order not in self.deinterlace.ORDERS or rate not in rates:
                 raise ValueError(f"fields must be (one of {self.deinterlace.ORDERS}, one of {rates}), got {fields!r}")
             if rate == "field":
                 self.fps = 2 * Fraction(info["fps"])
-            if rate == self.fieldmatch.RATE:                     # field matching: its two parameters, and what it did on the device
+            if rate in (self.fieldmatch.RATE, self.decimation.RATE):     # field matching: its two parameters, and what it did on the device
                 self.match = dict(self.fieldmatch.DEFAULTS if match is None else match)
                 self.field_stats = self.fieldmatch.Stats(torch.device(device))
+            if rate == self.decimation.RATE:                     # ... then decimation: four frames out per five in
+                self.fps = Fraction(info["fps"]) * 4 / 5
+                self.decimate = dict(self.decimation.DEFAULTS if decimate is None else decimate)
+                self.decimate_stats = self.decimation.Stats(torch.device(device))
+                self.pending, self.pending_before = None, None   # matched frames short of a cycle; the matched frame ahead of them
         self.chunk_size, self.skip, self.cap, self.ops, self.device = chunk_size, skip, cap, ops, torch.device(device)
         self.frame_bytes = self.frameio_in.frame_bytes(self.H, self.W, self.C, self.fmt)
         pinned = self.device.type == "cuda"
@@ -613,14 +652,34 @@ class FrameSource:
     def _unpack(self, packed, t):
         return self.frameio_in.unpack_frames(packed, self.fmt, t, self.H, self.W, self.C, self.matrix, self.range_, ops=self.ops)
 
+    def _decimated(self, matched, last):
+        """``matched`` [t, frame]: the next matched frames -> the fp32 frames of the whole cycles they complete (``last``: and of the
+        partial cycle the stream ends with), or None where they complete none"""
+        import torch
+        clip = matched if self.pending is None else torch.cat([self.pending, matched])
+        n = clip.shape[0]
+        whole = n if last else n - n % self.decimation.CYCLE
+        if whole == 0:
+            self.pending = clip
+            return None
+        frames = self.decimation.decimate(clip[:whole], self.fmt, whole, self.H, self.W, self.C, self.decimate["dup"],
+                                          before=self.pending_before, ops=self.ops, stats=self.decimate_stats)
+        self.pending_before = clip[whole - 1].clone()            # (copies of at most five frames: the buffer itself goes)
+        self.pending = clip[whole:].clone() if whole < n else None
+        return self._unpack(frames.reshape(-1), whole - whole // self.decimation.CYCLE)
+
     def _progressive(self, packed, t, before, after):
-        """buffer ``packed`` of t woven frames between its neighbours' frames -> the fp32 frames of its T or 2 T outputs"""
+        """buffer ``packed`` of t woven frames between its neighbours' frames -> the fp32 frames of its T or 2 T outputs (decimation:
+        of the cycles it completes, or None)"""
         order, rate = self.fields
+        last = after is None
         if t == 1:                                               # nothing of its own to mirror at an end of the clip: the clip's mirror
             before, after = (after if before is None else before), (before if after is None else after)
-        if rate == self.fieldmatch.RATE:                         # t woven frames -> t progressive ones
+        if rate in (self.fieldmatch.RATE, self.decimation.RATE):                 # t woven frames -> t progressive ones
             frames = self.fieldmatch.field_match(packed, self.fmt, t, self.H, self.W, self.C, order, self.match["thr"], self.match["mi"],
                                                  before=before, after=after, ops=self.ops, stats=self.field_stats)
+            if rate == self.decimation.RATE:
+                return self._decimated(frames.reshape(t, -1), last)
             return self._unpack(frames.reshape(-1), t)
         frames = self.deinterlace.deinterlace(packed, self.fmt, t, self.H, self.W, self.C, order, rate, before=before, after=after,
                                               ops=self.ops)
@@ -637,7 +696,9 @@ class FrameSource:
             for packed, t in self._uploads():
                 packed = packed.reshape(t, -1)
                 if held is not None:
-                    yield self._progressive(held, held.shape[0], before, packed[0])
+                    ready = [self._progressive(held, held.shape[0], before, packed[0])]
+                    if ready[0] is not None:                     # (decimation: a buffer that completes no cycle yields nothing)
+                        yield ready.pop()                        # (the caller's reference is the only one, as in _uploads)
                     before = held[-1].clone()                    # (a copy of one frame: the buffer itself goes)
                 held = packed
                 del packed
@@ -1157,6 +1218,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                 print(f"Saved: {path}")
             if rank == 0 and info is not None and src.field_stats is not None:
                 print(field_summary(src.field_stats, fields[0]))
+            if rank == 0 and info is not None and src.decimate_stats is not None:
+                print(decimate_summary(src.decimate_stats))
             continue
         src = None
         if info is not None:                           # the whole clip, read in chunks and concatenated on the device
@@ -1172,6 +1235,8 @@ def main(argv: Optional[List[str]] = None) -> int:
             print(f"Saved: {path}")
             if src is not None and src.field_stats is not None:                 # what field matching did
                 print(field_summary(src.field_stats, fields[0]))
+            if src is not None and src.decimate_stats is not None:              # what decimation did
+                print(decimate_summary(src.decimate_stats))
     return 0
 
 
