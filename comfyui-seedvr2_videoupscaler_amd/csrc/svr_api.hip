@@ -21,6 +21,7 @@
 #include "svr_frame_pack.hip"
 #include "svr_frame_pack_colour.hip"
 #include "svr_frame_unpack.hip"
+#include "svr_planar.hip"
 #include "svr_png.hip"
 #include "svr_colorfix.hip"
 #include "svr_rank.hip"
@@ -1184,6 +1185,53 @@ int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int
     else with_const<4, 3, 0>(swap, [&](auto CH) {
         hipLaunchKernelGGL((unpack_rgb_kernel<1, CH()>), dim3(grid), dim3(256), 0, s, packed, out, n_units, n);
     });
+    return e.launched();
+}
+
+// ---- planar YUV sources turned into rgb16 codes (svr_planar.hip)
+int svr_planar_codes(const void* planes, int64_t planes_bytes, int32_t sub, int32_t bits, int32_t T, int32_t H, int32_t W,
+                     int32_t matrix, int32_t range, int32_t siting, void* out, int64_t out_bytes, void* stream) {
+    const Launch e{"svr_planar_codes", stream};
+    const bool wide = bits != 8;                                                       // 16-bit samples
+    const char* why = nullptr;
+    if (!planes) why = "planes is a null pointer";
+    else if (!out) why = "out is a null pointer";
+    else if (T < 1 || H < 1 || W < 1) why = "need T >= 1, H >= 1, W >= 1";
+    else if ((int64_t)H * W > ((int64_t)1 << 40) / T) why = "T * H * W must not exceed 2^40 pixels";
+    else if (sub != SVR_PLANAR_420 && sub != SVR_PLANAR_422 && sub != SVR_PLANAR_444)
+        why = "sub must be SVR_PLANAR_420, SVR_PLANAR_422 or SVR_PLANAR_444";
+    else if (bits != 8 && bits != 10 && bits != 12) why = "bits must be 8, 10 or 12";
+    else if (matrix != SVR_COLOUR_MATRIX_BT709 && matrix != SVR_COLOUR_MATRIX_BT601 && matrix != SVR_COLOUR_MATRIX_BT2020)
+        why = "matrix must be SVR_COLOUR_MATRIX_BT709, SVR_COLOUR_MATRIX_BT601 or SVR_COLOUR_MATRIX_BT2020";
+    else if (range != SVR_COLOUR_RANGE_TV && range != SVR_COLOUR_RANGE_PC) why = "range must be SVR_COLOUR_RANGE_TV or SVR_COLOUR_RANGE_PC";
+    else if (siting != SVR_PLANAR_SITING_LEFT && siting != SVR_PLANAR_SITING_TOPLEFT)
+        why = "siting must be SVR_PLANAR_SITING_LEFT or SVR_PLANAR_SITING_TOPLEFT";
+    else if (siting == SVR_PLANAR_SITING_TOPLEFT && sub != SVR_PLANAR_420)
+        why = "siting SVR_PLANAR_SITING_TOPLEFT is for SVR_PLANAR_420 only";
+    else if (wide && (uintptr_t)planes % 2) why = "planes is not aligned to 2 bytes";
+    else if ((uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
+    if (why) return e.refuse("%s", why);
+    const int64_t px = (int64_t)T * H * W;
+    const int64_t hc = sub == SVR_PLANAR_420 ? ((int64_t)H + 1) / 2 : H, wc = sub == SVR_PLANAR_444 ? W : ((int64_t)W + 1) / 2;
+    const int64_t need_in = (int64_t)T * ((int64_t)H * W + 2 * hc * wc) * (wide ? 2 : 1), need_out = px * 6;
+    if (planes_bytes != need_in) return e.wrong_size("planes_bytes", planes_bytes, "the format needs", need_in);
+    if (out_bytes != need_out) return e.wrong_size("out_bytes", out_bytes, "uint16 [T, H, W, 3] needs", need_out);
+    if (rank_overlap(out, need_out, planes, need_in)) return e.refuse("out overlaps planes");
+    // Kr, Kb exact decimals, the four products rounded at 2^16 (planar.MATRICES)
+    const YuvCoef k = matrix == SVR_COLOUR_MATRIX_BT709 ? YuvCoef{103206, 12276, 30679, 121609}
+                    : matrix == SVR_COLOUR_MATRIX_BT601 ? YuvCoef{91881, 22553, 46802, 116130} : YuvCoef{96639, 10784, 37444, 123299};
+    const bool vec = (uintptr_t)planes % 16 == 0 && (uintptr_t)out % 16 == 0 && W % 16 == 0;
+    const unsigned grid = capped_grid(vec ? (int64_t)T * hc * (W / 16) : px);
+    const hipStream_t s = (hipStream_t)stream;
+    with_const<SVR_PLANAR_444, SVR_PLANAR_422, SVR_PLANAR_420>(sub, [&](auto SUB) { with_const<12, 10, 8>(bits, [&](auto BITS) {
+        with_const<SVR_COLOUR_RANGE_PC, SVR_COLOUR_RANGE_TV>(range, [&](auto PC) { with_const<1, 0>(siting == SVR_PLANAR_SITING_TOPLEFT, [&](auto TOPLEFT) {
+            if constexpr (TOPLEFT() && SUB() != SVR_PLANAR_420) return;                // (refused above)
+            else if (vec) hipLaunchKernelGGL((planar_vec_kernel<SUB(), BITS(), PC(), TOPLEFT()>), dim3(grid), dim3(256), 0, s, planes,
+                                             (unsigned short*)out, T, H, W, k);
+            else hipLaunchKernelGGL((planar_kernel<SUB(), BITS(), PC(), TOPLEFT()>), dim3(grid), dim3(256), 0, s, planes,
+                                    (unsigned short*)out, T, H, W, k);
+        }); });
+    }); });
     return e.launched();
 }
 

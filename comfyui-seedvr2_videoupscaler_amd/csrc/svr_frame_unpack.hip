@@ -61,7 +61,7 @@ __global__ __launch_bounds__(256) void unpack_rgb_kernel(const void* __restrict_
 
 struct YuvCoef { int rv, gu, gv, bu; };                   // the matrix scaled by 2^16 (bt709: 103206, 12276, 30679, 121609)
 
-// BITS 8 / 10; PC: full range (y0 = 0, both excursions 2^n - 1) instead of tv (16 / 219 / 224, shifted for 10 bits)
+// BITS 8 / 10 (12: svr_planar.hip); PC: full range (y0 = 0, both excursions 2^n - 1) instead of tv (16 / 219 / 224, shifted for 10 bits)
 template <int BITS, int PC>
 struct YuvFormat {
     static constexpr int MAXV = (1 << BITS) - 1;
@@ -76,11 +76,13 @@ struct YuvFormat {
 
 // q = clamp(floor((2 num + Den) / (2 Den)), 0, 65535) with num = 65535 * s; a numerator <= 0 gives 0 (floor, then the clamp)
 template <class F>
-SVR_DEVICE float yuv_code(int64_t s) {
+SVR_DEVICE uint32_t yuv_q(int64_t s) {
     const int64_t top = 2 * 65535 * s + F::DEN;
     const uint64_t q = top <= 0 ? 0ull : (uint64_t)top / (uint64_t)(2 * F::DEN);
-    return unpack_unit((uint32_t)(q < 65535ull ? q : 65535ull), 65535.f);
+    return (uint32_t)(q < 65535ull ? q : 65535ull);
 }
+template <class F>
+SVR_DEVICE float yuv_code(int64_t s) { return unpack_unit(yuv_q<F>(s), 65535.f); }
 
 // Y a sample, cb8 / cr8 the upsampled chroma over 8
 template <class F>

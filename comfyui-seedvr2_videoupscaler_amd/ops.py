@@ -892,6 +892,24 @@ class HipOps:
                      hip_lib.YUV_MATRICES[matrix], hip_lib.YUV_RANGES[range_], _ptr(out), out.numel() * out.element_size())
         return out
 
+    # ------------------------------------------------------------------ planar YUV sources
+    def planar_codes(self, planes, sub, bits, T, H, W, matrix="bt709", range_="tv", siting="left", out=None):
+        """Planar YUV turned into rgb16 codes on the device (planar.py is the specification; csrc/svr_planar.hip): ``planes`` a dense
+        uint8 (8 bits) or uint16 (10 / 12 bits) tensor of exactly the format's samples, ``sub`` "420" | "422" | "444" -> uint16
+        [T, H, W, 3], unpack_frames' "rgb16".  One launch on the current stream, no host synchronisation.  ``out``: a dense uint16
+        tensor of that shape, apart from ``planes``."""
+        from . import planar
+        try:
+            planar.check_arguments(planes, sub, bits, T, H, W, matrix, range_, siting)
+        except ValueError as e:
+            raise ValueError(f"planar_codes: {e}") from None
+        self._chk(planes, None, "planar_codes: planes")
+        out = self._out("planar_codes", out, (T, H, W, 3), torch.uint16)
+        self._launch("svr_planar_codes", _ptr(planes), planes.numel() * planes.element_size(), hip_lib.PLANAR_SUBS[sub], int(bits), T, H, W,
+                     hip_lib.COLOUR_MATRICES[matrix], hip_lib.COLOUR_RANGES[range_], hip_lib.PLANAR_SITINGS[siting], _ptr(out),
+                     out.numel() * out.element_size())
+        return out
+
     # ------------------------------------------------------------------ interlaced sources
     def deinterlace(self, packed, fmt, T, H, W, C, order, rate, before=None, after=None, out=None):
         """Woven frames made progressive on the packed planes (deinterlace.py is the specification; csrc/svr_deinterlace.hip):

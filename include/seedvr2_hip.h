@@ -80,6 +80,9 @@
  *   svr_decimate_select                        element alignment is enough (2 bytes for the 16-bit formats, diff and drops 4, stats 8);
  *                                              16-byte loads and stores where packed and out are 16-byte aligned and the frame is a
  *                                              multiple of 16 bytes, element accesses otherwise
+ *   svr_planar_codes                           element alignment is enough (2 bytes for the 10 / 12-bit planes and for out); 16-byte
+ *                                              loads and stores where planes and out are 16-byte aligned and W % 16 == 0, element
+ *                                              accesses otherwise
  */
 #ifndef SEEDVR2_HIP_H
 #define SEEDVR2_HIP_H
@@ -123,6 +126,8 @@ extern "C" {
  * can make, and the frames copied from the first clean weave or from the deinterlaced clip).  New symbols only.
  * v9, additive: + svr_frame_diffs() / svr_decimate_select() (decimation: per frame the largest block sum of its difference from
  * the frame before it, and of every cycle of five frames the four that are not the smallest).  New symbols only.
+ * v9, additive: + svr_planar_codes() (planar 4:2:0 / 4:2:2 / 4:4:4 sources of 8 / 10 / 12 bits, BT.709 / BT.601 / BT.2020, turned
+ * into the 16-bit RGB codes svr_unpack_frames takes as SVR_UNPACK_RGB16).  A new symbol only; svr_unpack_frames is untouched.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -611,6 +616,30 @@ int svr_adaptive_blend(const void* base, const int64_t* base_strides, const void
 #define SVR_RANGE_PC 1
 int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int32_t T, int32_t H, int32_t W, int32_t C,
                       int32_t matrix, int32_t range, float* out, int64_t out_bytes, void* stream);
+
+/* ---- planar YUV sources ------------------------------------------------------------------------ */
+/* planar.py (the specification, bit for bit): `planes` T frames of planar YUV as a decoder emits them -> `out` uint16 [T, H, W, 3]
+ * dense: the 16-bit RGB codes svr_unpack_frames, svr_deinterlace, svr_comb_counts and svr_frame_diffs take as SVR_UNPACK_RGB16.
+ *   sub     SVR_PLANAR_420 / _422 / _444.  Per frame the Y plane [H, W], then Cb, then Cr, each [hc, wc] row-major: 420 hc = ceil(H/2),
+ *           wc = ceil(W/2); 422 hc = H, wc = ceil(W/2); 444 hc = H, wc = W.
+ *   bits    8 (uint8 samples), 10 or 12 (uint16; a sample above 2^bits - 1 counts as 2^bits - 1).
+ *   matrix  SVR_COLOUR_MATRIX_BT709 / _BT601 / _BT2020 (non-constant luminance); range SVR_COLOUR_RANGE_TV / _PC (y0 = 16, ys = 219,
+ *           cs = 224, each << (bits - 8); or y0 = 0, ys = cs = 2^bits - 1).
+ *   siting  SVR_PLANAR_SITING_LEFT: chroma co-sited with even luma columns and (420) midway between luma rows -- what
+ *           svr_unpack_frames assumes; SVR_PLANAR_SITING_TOPLEFT (420 only): co-sited with even luma columns AND even luma rows.
+ * Chroma is upsampled bilinearly in integers (weights over 8, indices clamped to the plane), the matrix is svr_unpack_frames' in
+ * exact 64-bit integers: floor division, then clamp to 0..65535.  For 422 and 444 an output row depends on its input row alone.
+ * Every argument is checked before the launch: null pointers, sizes below 1 (T * H * W <= 2^40 pixels), an unknown sub, bits, matrix,
+ * range or siting (TOPLEFT with 422 / 444 included), planes_bytes and out_bytes (= 6 * T*H*W) other than EXACTLY the sizes above, a
+ * 16-bit operand or out not aligned to 2 bytes, out overlapping planes.  One launch on `stream`, no host synchronisation, no
+ * workspace. */
+#define SVR_PLANAR_420 0
+#define SVR_PLANAR_422 1
+#define SVR_PLANAR_444 2
+#define SVR_PLANAR_SITING_LEFT    1    /* (SVR_COLOUR_SITING_LEFT's value) */
+#define SVR_PLANAR_SITING_TOPLEFT 2
+int svr_planar_codes(const void* planes, int64_t planes_bytes, int32_t sub, int32_t bits, int32_t T, int32_t H, int32_t W,
+                     int32_t matrix, int32_t range, int32_t siting, void* out, int64_t out_bytes, void* stream);
 
 /* ---- interlaced sources ------------------------------------------------------------------------ */
 /* deinterlace.py (the specification, bit for bit): `packed` T woven frames in one of the SVR_UNPACK_* formats (same layouts and

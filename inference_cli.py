@@ -191,11 +191,14 @@ def decimate_summary(stats) -> str:
     return line
 
 
-def output_depth(inp: str, info: Optional[dict] = None) -> int:
+def output_depth(inp: str, info: Optional[dict] = None, colour: Optional[dict] = None, fields=None) -> int:
     """Bits per sample of the png files written for this input: 16 where the source is deeper than 8 bits -- a video read through
     ffmpeg whose route is rgb16 / yuv420p10, a 16-bit RGB / RGBA png still --, 8 for everything else (.pt / .npy tensors, the
-    OpenCV reader, 8-bit stills)."""
+    OpenCV reader, 8-bit stills).  A source route_planar() routes (``colour``, ``fields``: FrameSource's) follows its own bits."""
     if info is not None:
+        routed = route_planar(info, colour, fields)
+        if routed is not None:
+            return 8 if routed[2] == 8 else 16
         return 16 if route_input(info)[1] in ("rgb16", "yuv420p10") else 8
     if os.path.splitext(inp)[1].lower() == ".png":
         head = _pngenc().png_header(inp)
@@ -508,6 +511,42 @@ def route_input(info: dict):
     return ("rgba64le" if alpha else "rgb48le"), "rgb16", (4 if alpha else 3), "bt709", "tv"
 
 
+# source pix_fmt -> (subsampling, bits, range or None = from color_range): what planar.py turns into rgb16 codes on the device
+PLANAR_SOURCES = {"yuv422p": ("422", 8, None), "yuvj422p": ("422", 8, "pc"), "yuv444p": ("444", 8, None), "yuvj444p": ("444", 8, "pc"),
+                  "yuv422p10le": ("422", 10, None), "yuv444p10le": ("444", 10, None), "yuv420p12le": ("420", 12, None),
+                  "yuv422p12le": ("422", 12, None), "yuv444p12le": ("444", 12, None),
+                  # route_input's own two, only where it cannot say what the stream is: a BT.2020 matrix or top-left chroma
+                  "yuv420p": ("420", 8, None), "yuv420p10le": ("420", 10, None)}
+PLANAR_MATRIX_OF = dict(MATRIX_OF, bt2020nc="bt2020")
+
+
+def _planar():
+    import importlib
+    return importlib.import_module(f"{PKG}.planar")
+
+
+def route_planar(info: dict, colour: Optional[dict] = None, fields=None):
+    """-> (ffmpeg's -pix_fmt: the planes as they are, sub, bits, matrix, range_, siting) for a source whose planes planar.py turns into
+    rgb16 codes on the device, or None: route_input decides, as it always did.  None while planar.ENABLED is off (it ships off;
+    DESIGN.md 7.3k), for a name outside PLANAR_SOURCES (alpha, semi-planar, 4:1:1 ...), for bt2020c or a matrix outside
+    PLANAR_MATRIX_OF, for 4:2:0 of an interlaced source (``fields``: its vertical chroma filter would mix the fields), and for
+    yuv420p / yuv420p10le that route_input already reads as they are stored (anything but a bt2020nc matrix or top-left chroma)."""
+    pix = info.get("pix_fmt") or ""
+    if not _planar().ENABLED or pix not in PLANAR_SOURCES:
+        return None
+    sub, bits, range_ = PLANAR_SOURCES[pix]
+    space = info.get("color_space")
+    matrix = PLANAR_MATRIX_OF.get(space) if space is not None else ("bt709" if info["height"] >= 720 else "bt601")
+    if matrix is None:
+        return None
+    topleft = sub == "420" and (colour or {}).get("chroma_location") == "topleft"
+    if sub == "420" and (fields is not None or (pix in PLANAR_420 and matrix != "bt2020" and not topleft)):
+        return None
+    if range_ is None:
+        range_ = "pc" if info.get("color_range") in ("pc", "jpeg") else "tv"
+    return pix, sub, bits, matrix, range_, ("topleft" if topleft else "left")
+
+
 class FrameSource:
     """Video -> fp32 chunks on ``device``, the counterpart of FrameSink.  One ffmpeg child decodes every frame exactly once, in
     order (``-f rawvideo`` carries no timestamps, so ffmpeg neither drops nor duplicates frames), at the depth route_input()
@@ -534,10 +573,15 @@ class FrameSource:
     whole cycles only, a buffer that completes no cycle yields nothing, and the end of the stream emits the partial cycle as it is.
     For any chunk size the chunks, concatenated, are decimate.decimate_torch of fieldmatch.field_match_torch of the whole clip
     followed by unpack_frames_torch; ``fps`` is 4/5 of the source's.  ``decimate``: dict(dup=), decimate.DEFAULTS where None.
-    ``decimate_stats``: the decimate.Stats the chunks add to on the device (None for every other source)."""
+    ``decimate_stats``: the decimate.Stats the chunks add to on the device (None for every other source).
+
+    ``colour`` (probe_colour's dictionary): with planar.ENABLED, a source route_planar() routes -- planar 4:2:2 / 4:4:4, 12 bits,
+    BT.2020 or top-left 4:2:0 -- is asked for in its own -pix_fmt, and every uploaded buffer becomes rgb16 codes at once
+    (planar.planar_codes / csrc/svr_planar.hip; ``planar``: its (sub, bits, matrix, range_, siting)).  From there on the source IS an
+    rgb16 source: the chunks, concatenated, are the chains above applied to planar_codes_torch of the whole clip as "rgb16"."""
 
     def __init__(self, exe: str, path: str, info: dict, chunk_size: int, skip: int = 0, cap: int = 0, ops=None, device="cpu",
-                 fields=None, match=None, decimate=None):
+                 fields=None, match=None, decimate=None, colour=None):
         import importlib
         import tempfile
         import torch
@@ -545,6 +589,11 @@ class FrameSource:
             raise ValueError("chunk_size must be positive")
         self.frameio_in = importlib.import_module(f"{PKG}.frameio_in")
         self.raw, self.fmt, self.C, self.matrix, self.range_ = route_input(info)
+        routed, self.planar = route_planar(info, colour, fields), None
+        if routed is not None:                                   # the planes as stored; rgb16 codes from the upload on
+            self.planes = _planar()
+            self.raw, self.planar = routed[0], routed[1:]
+            self.fmt, self.C, self.matrix, self.range_ = "rgb16", 3, "bt709", "tv"
         self.H, self.W, self.fps = info["height"], info["width"], info["fps"]
         self.fields, self.match, self.field_stats = fields, None, None
         self.decimate, self.decimate_stats = None, None
@@ -568,6 +617,8 @@ class FrameSource:
                 self.pending, self.pending_before = None, None   # matched frames short of a cycle; the matched frame ahead of them
         self.chunk_size, self.skip, self.cap, self.ops, self.device = chunk_size, skip, cap, ops, torch.device(device)
         self.frame_bytes = self.frameio_in.frame_bytes(self.H, self.W, self.C, self.fmt)
+        if self.planar is not None:                              # (what the reader fills: the planes, not the codes)
+            self.frame_bytes = self.planes.frame_bytes(self.H, self.W, self.planar[0], self.planar[1])
         pinned = self.device.type == "cuda"
         self.buffers = [torch.empty(chunk_size * self.frame_bytes, dtype=torch.uint8, pin_memory=pinned) for _ in range(2)]
         self.free, self.work = queue.Queue(), queue.Queue()
@@ -645,7 +696,12 @@ class FrameSource:
             host = self.buffers[slot][:t * self.frame_bytes]
             packed = host.to(self.device) if self.device.type == "cuda" else host.clone()         # (returns when the bytes are there)
             self.free.put(slot)
-            ready = [packed.view(self.frameio_in.packed_dtype(self.fmt))]
+            if self.planar is not None:                          # planar YUV -> rgb16 codes: the source is an rgb16 source from here on
+                sub, bits, matrix, range_, siting = self.planar
+                ready = [self.planes.planar_codes(packed.view(self.planes.planar_dtype(bits)), sub, bits, t, self.H, self.W, matrix, range_,
+                                                  siting, ops=self.ops).reshape(-1)]
+            else:
+                ready = [packed.view(self.frameio_in.packed_dtype(self.fmt))]
             del packed, host                                     # (the caller's reference is the only one while this waits for the next)
             yield ready.pop(), t
 
@@ -1181,7 +1237,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         fields = source_fields(probed[0].get("field_order"), rank) if probed else None         # an interlaced source
         job_kw = dict(writer_kw)
         if fmt == "png":                               # a source deeper than 8 bits leaves as 16-bit files
-            job_kw["depth"] = output_depth(inp, info)
+            job_kw["depth"] = output_depth(inp, info, colour, fields)
         if info is not None and info["has_audio"] and fmt == "mp4":            # (via_ffmpeg: the writer is FFmpegWriter)
             job_kw["audio"] = (inp, args.skip_first_frames / float(info["fps"]))
         if fmt == "mp4":                               # an HDR source keeps its colour through --10bit; anything else: BT.709 as always
@@ -1190,7 +1246,8 @@ def main(argv: Optional[List[str]] = None) -> int:
                 print(warning, file=sys.stderr)
             if out_colour is not None:
                 job_kw["colour"] = out_colour
-        source = lambda n: FrameSource(ffmpeg, inp, info, n, args.skip_first_frames, args.load_cap, ops, eng[0].dit.device, fields)
+        source = lambda n: FrameSource(ffmpeg, inp, info, n, args.skip_first_frames, args.load_cap, ops, eng[0].dit.device, fields,
+                                       colour=colour)
         if args.chunk_size > 0 and ext_of(inp) not in IMAGE_EXT:
             # streaming: read, upscale, pack and write --chunk_size frames at a time
             if info is not None:
