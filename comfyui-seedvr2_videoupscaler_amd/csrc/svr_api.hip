@@ -20,6 +20,7 @@
 #include "svr_alpha.hip"
 #include "svr_frame_pack.hip"
 #include "svr_frame_pack_colour.hip"
+#include "svr_planar_out.hip"
 #include "svr_frame_unpack.hip"
 #include "svr_planar.hip"
 #include "svr_png.hip"
@@ -490,9 +491,11 @@ int svr_alpha_refine(const void* rgb, const float* base, float* out, uint8_t* ed
 // ---- packed output frames (svr_frame_pack.hip: rgb8 / bgr8; svr_frame_pack_colour.hip: yuv420p10, whichever entry point asks)
 // The refusals svr_pack_frames and svr_pack_yuv420p10 share, in the order both report them -> 0, or -1 with the message in g_err.
 // ``own``: the caller's refusal of its own format / colour codes (nullptr: none), which ranks between the geometry and the
-// alignment.  ``C8``: bytes per pixel of an 8-bit format, 0 for yuv420p10 planes.  ``needs``: the caller's words.
+// alignment.  ``C8``: bytes per pixel of an 8-bit format, 0 for planes: those of ``sub`` in samples of ``sample`` bytes (yuv420p10
+// where nothing is said; svr_pack_planar says).  ``needs``: the caller's words.
 static int pack_refusal(const Entry& e, const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t C8,
-                        const char* own, const void* out, int64_t out_bytes, const char* needs) {
+                        const char* own, const void* out, int64_t out_bytes, const char* needs, int32_t sub = SVR_PLANAR_420,
+                        int32_t sample = 2) {
     const char* why = nullptr;
     if (!frames) why = "frames is a null pointer";
     else if (!out) why = "out is a null pointer";
@@ -501,10 +504,10 @@ static int pack_refusal(const Entry& e, const void* frames, int32_t x_kind, int3
     else if ((int64_t)H * W > ((int64_t)1 << 40) / T) why = "T * H * W must not exceed 2^40 pixels";
     else if (own) why = own;
     else if ((uintptr_t)frames % (x_kind == SVR_STORE_FP32 ? 4 : 2)) why = "frames is not aligned to its element size";
-    else if (!C8 && (uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
+    else if (!C8 && sample == 2 && (uintptr_t)out % 2) why = "out is not aligned to 2 bytes";
     if (why) return e.refuse("%s", why);
-    const int64_t h2 = ((int64_t)H + 1) / 2, w2 = ((int64_t)W + 1) / 2;
-    const int64_t need = C8 ? (int64_t)T * H * W * C8 : 2 * (int64_t)T * ((int64_t)H * W + 2 * h2 * w2);
+    const int64_t h2 = sub == SVR_PLANAR_420 ? ((int64_t)H + 1) / 2 : H, w2 = sub == SVR_PLANAR_444 ? W : ((int64_t)W + 1) / 2;
+    const int64_t need = C8 ? (int64_t)T * H * W * C8 : sample * (int64_t)T * ((int64_t)H * W + 2 * h2 * w2);
     return out_bytes == need ? 0 : e.wrong_size("out_bytes", out_bytes, needs, need);
 }
 
@@ -566,6 +569,41 @@ int svr_pack_yuv420p10(const void* frames, int32_t x_kind, int32_t T, int32_t H,
     if (pack_refusal(e, frames, x_kind, T, H, W, 0, own, out, out_bytes, "the planes need")) return -1;
     launch_pack_yuv420p10(frames, x_kind, T, H, W, pack_coef(matrix, range), siting == SVR_COLOUR_SITING_LEFT, (unsigned short*)out,
                           (hipStream_t)stream);
+    return e.launched();
+}
+
+// ---- planar YUV planes of a chosen subsampling, depth, matrix, range and chroma siting (svr_planar_out.hip)
+int svr_pack_planar(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t sub, int32_t bits, int32_t matrix,
+                    int32_t range, int32_t siting, void* out, int64_t out_bytes, void* stream) {
+    const Launch e{"svr_pack_planar", stream};
+    const char* own = nullptr;
+    if (sub != SVR_PLANAR_420 && sub != SVR_PLANAR_422 && sub != SVR_PLANAR_444)
+        own = "sub must be SVR_PLANAR_420, SVR_PLANAR_422 or SVR_PLANAR_444";
+    else if (bits != 8 && bits != 10 && bits != 12) own = "bits must be 8, 10 or 12";
+    else if (matrix != SVR_COLOUR_MATRIX_BT709 && matrix != SVR_COLOUR_MATRIX_BT601 && matrix != SVR_COLOUR_MATRIX_BT2020)
+        own = "matrix must be SVR_COLOUR_MATRIX_BT709, SVR_COLOUR_MATRIX_BT601 or SVR_COLOUR_MATRIX_BT2020";
+    else if (range != SVR_COLOUR_RANGE_TV && range != SVR_COLOUR_RANGE_PC) own = "range must be SVR_COLOUR_RANGE_TV or SVR_COLOUR_RANGE_PC";
+    else if (siting != SVR_COLOUR_SITING_CENTER && siting != SVR_COLOUR_SITING_LEFT && siting != SVR_PLANAR_SITING_TOPLEFT)
+        own = "siting must be SVR_COLOUR_SITING_CENTER, SVR_COLOUR_SITING_LEFT or SVR_PLANAR_SITING_TOPLEFT";
+    else if (siting == SVR_PLANAR_SITING_TOPLEFT && sub != SVR_PLANAR_420) own = "siting SVR_PLANAR_SITING_TOPLEFT is for SVR_PLANAR_420 only";
+    else if (siting == SVR_COLOUR_SITING_CENTER && sub == SVR_PLANAR_444) own = "siting must be SVR_COLOUR_SITING_LEFT for SVR_PLANAR_444";
+    const bool wide = bits != 8;                                                       // 16-bit samples
+    if (pack_refusal(e, frames, x_kind, T, H, W, 0, own, out, out_bytes, "the planes need", sub, wide ? 2 : 1)) return -1;
+    PlanarOutCoef c{pack_coef(matrix, range), 1 << (bits - 1), (1 << bits) - 1};       // (planar.yuv_constants at this depth)
+    if (range == SVR_COLOUR_RANGE_TV) { c.k.y0 = 16 << (bits - 8); c.k.ys = 219 << (bits - 8); c.k.cs = 224 << (bits - 8); }
+    else { c.k.y0 = 0; c.k.ys = c.k.cs = c.top; }
+    const bool vec = (uintptr_t)frames % 16 == 0 && (uintptr_t)out % 16 == 0 && W % 16 == 0;
+    const int64_t hc = sub == SVR_PLANAR_420 ? ((int64_t)H + 1) / 2 : H, wc = sub == SVR_PLANAR_444 ? W : ((int64_t)W + 1) / 2;
+    const unsigned grid = capped_grid((int64_t)T * hc * (vec ? W / 16 : wc));
+    const hipStream_t s = (hipStream_t)stream;
+    with_kind(x_kind, [&](auto K) { with_const<SVR_PLANAR_444, SVR_PLANAR_422, SVR_PLANAR_420>(sub, [&](auto SUB) {
+        with_const<2, 1, 0>(siting, [&](auto SIT) { with_const<1, 0>(wide, [&](auto WIDE) {
+            if constexpr ((SIT() == 2 && SUB() != SVR_PLANAR_420) || (SIT() == 0 && SUB() == SVR_PLANAR_444)) return;   // (refused above)
+            else if (vec) hipLaunchKernelGGL((planar_out_vec_kernel<K(), SUB(), SIT(), WIDE() != 0>), dim3(grid), dim3(256), 0, s, frames, out,
+                                             T, H, W, c);
+            else hipLaunchKernelGGL((planar_out_kernel<K(), SUB(), SIT(), WIDE() != 0>), dim3(grid), dim3(256), 0, s, frames, out, T, H, W, c);
+        }); });
+    }); });
     return e.launched();
 }
 

@@ -31,6 +31,7 @@ COLOUR_RANGES = {"tv": 0, "pc": 1}                         # SVR_COLOUR_RANGE_*
 COLOUR_SITINGS = {"center": 0, "left": 1}                  # SVR_COLOUR_SITING_*
 PLANAR_SUBS = {"420": 0, "422": 1, "444": 2}               # SVR_PLANAR_* (svr_planar_codes; its matrix and range are COLOUR_*)
 PLANAR_SITINGS = {"left": 1, "topleft": 2}                 # SVR_PLANAR_SITING_*
+PLANAR_OUT_SITINGS = {"center": 0, "left": 1, "topleft": 2}       # svr_pack_planar: SVR_COLOUR_SITING_* and SVR_PLANAR_SITING_TOPLEFT
 # svr_gemm_kernel_class() codes (include/seedvr2_hip.h)
 KERNEL_CLASSES = {0: "none", 1: "gemm", 2: "gemm_persistent", 3: "conv_halo", 4: "conv_subpixel", 5: "conv_thin_in",
                   6: "conv_thinout", 7: "conv_generic"}
@@ -129,6 +130,7 @@ SYMBOLS = {
     "svr_adaptive_blend": (C.c_int, [_vp, _strides, _vp, _strides, _vp, _strides, _vp, _vp, _vp, C.c_double, C.c_double, _vp, _strides,
                                      _i32, _i32, _i32, _i32, _vp]),
     "svr_unpack_frames": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
+    "svr_pack_planar": (C.c_int, [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_planar_codes": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_deinterlace": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
     "svr_comb_counts": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),

@@ -563,13 +563,17 @@ class HipOps:
         return out
 
     # ------------------------------------------------------------------ packed output frames
-    def _pack_args(self, name, frames, fmt, out, colour=None):
-        """What pack_frames and pack_yuv420p10 check before their launch -> (T, H, W, Cn, x_kind, out); ``out`` allocated where it
-        was None.  ``colour``: pack_yuv420p10's (matrix, range_, siting), refused with the format."""
-        from . import frameio
+    def _pack_args(self, name, frames, fmt, out, colour=None, planes=None):
+        """What pack_frames, pack_yuv420p10 and pack_planar check before their launch -> (T, H, W, Cn, x_kind, out); ``out`` allocated
+        where it was None.  ``colour``: pack_yuv420p10's (matrix, range_, siting), refused with the format.  ``planes``: pack_planar's
+        (sub, bits, matrix, range_, siting) in place of a format."""
+        from . import frameio, planar, planar_out
 
         def codes_and_channels(T, H, W, Cn):                   # (the format judges the channel count)
             try:
+                if planes is not None:
+                    planar_out.check_arguments(*planes)
+                    return planar_out.check_channels(Cn)
                 if colour is not None:
                     frameio.check_colour(*colour)
                 frameio.packed_shape(T, H, W, Cn, fmt)
@@ -577,6 +581,8 @@ class HipOps:
                 return str(e)
 
         T, H, W, Cn, kind = clip_args(name, frames, self.device, channels=None, before=codes_and_channels)
+        if planes is not None:
+            return T, H, W, Cn, kind, self._out(name, out, planar.planar_shape(T, H, W, planes[0]), planar.planar_dtype(planes[1]))
         out = self._out(name, out, frameio.packed_shape(T, H, W, Cn, fmt), frameio.packed_dtype(fmt), suffix="" if colour else f" for {fmt}")
         return T, H, W, Cn, kind, out
 
@@ -598,6 +604,17 @@ class HipOps:
         T, H, W, _, kind, out = self._pack_args("pack_yuv420p10", frames, "yuv420p10", out, colour=(matrix, range_, siting))
         self._launch("svr_pack_yuv420p10", _ptr(frames), kind, T, H, W, hip_lib.COLOUR_MATRICES[matrix], hip_lib.COLOUR_RANGES[range_],
                      hip_lib.COLOUR_SITINGS[siting], _ptr(out), out.numel() * out.element_size())
+        return out
+
+    def pack_planar(self, frames, sub, bits, matrix="bt709", range_="tv", siting="left", out=None):
+        """Planar YUV planes of a chosen subsampling ("420" | "422" | "444"), depth (8 | 10 | 12), matrix, range and chroma siting
+        ("center" | "left" | "topleft", as far as the subsampling takes them) on the device (planar_out.pack_planar_torch is the
+        specification; csrc/svr_planar_out.hip): frames [T, H, W, 3] fp32 / bf16, dense -> uint8 (8 bits) or uint16
+        [T, H*W + 2*hc*wc], planar.planar_shape's layout.  One launch on the current stream, no host synchronisation.  ``out``: a
+        dense tensor of exactly that shape and dtype."""
+        T, H, W, _, kind, out = self._pack_args("pack_planar", frames, None, out, planes=(sub, bits, matrix, range_, siting))
+        self._launch("svr_pack_planar", _ptr(frames), kind, T, H, W, hip_lib.PLANAR_SUBS[sub], int(bits), hip_lib.COLOUR_MATRICES[matrix],
+                     hip_lib.COLOUR_RANGES[range_], hip_lib.PLANAR_OUT_SITINGS[siting], _ptr(out), out.numel() * out.element_size())
         return out
 
     # ------------------------------------------------------------------ frame signatures (cut detection)

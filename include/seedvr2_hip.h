@@ -51,6 +51,9 @@
  *                                              for yuv420p10, W % 16 == 0), element accesses otherwise
  *   svr_pack_yuv420p10                         as svr_pack_frames' yuv420p10: element alignment is enough; 16-byte loads and stores where
  *                                              frames and out are 16-byte aligned and W % 16 == 0, element accesses otherwise
+ *   svr_pack_planar                            element alignment is enough (frames 4 / 2 bytes, out 2 bytes at 10 / 12 bits, 1 at 8);
+ *                                              16-byte loads and 16- / 8-byte stores where frames and out are 16-byte aligned and
+ *                                              W % 16 == 0, element accesses otherwise
  *   svr_unpack_frames                          element alignment is enough (packed 2 bytes for the 16-bit formats, out 4 bytes);
  *                                              16-byte loads and stores where packed and out are 16-byte aligned (and, for the
  *                                              yuv420p formats, W % 16 == 0), element accesses otherwise
@@ -128,6 +131,9 @@ extern "C" {
  * the frame before it, and of every cycle of five frames the four that are not the smallest).  New symbols only.
  * v9, additive: + svr_planar_codes() (planar 4:2:0 / 4:2:2 / 4:4:4 sources of 8 / 10 / 12 bits, BT.709 / BT.601 / BT.2020, turned
  * into the 16-bit RGB codes svr_unpack_frames takes as SVR_UNPACK_RGB16).  A new symbol only; svr_unpack_frames is untouched.
+ * v9, additive: + svr_pack_planar() (output frames as planar 4:2:0 / 4:2:2 / 4:4:4 of 8 / 10 / 12 bits, BT.709 / BT.601 / BT.2020, chroma
+ * sited center, left or, for 4:2:0, topleft: what svr_planar_codes reads, written).  A new symbol only; svr_pack_frames and
+ * svr_pack_yuv420p10 are untouched.
  * v9, clarification: the operand-layout contract above (alignment and pitch of every pointer + leading-dimension pair) is written
  * down and enforced on the host: a layout whose serving kernel would make a misaligned vector access, or whose pitch does not cover
  * its extent, is routed to a kernel with aligned accesses or refused before any launch instead of being launched as it was.  Dense,
@@ -640,6 +646,28 @@ int svr_unpack_frames(const void* packed, int64_t packed_bytes, int32_t fmt, int
 #define SVR_PLANAR_SITING_TOPLEFT 2
 int svr_planar_codes(const void* planes, int64_t planes_bytes, int32_t sub, int32_t bits, int32_t T, int32_t H, int32_t W,
                      int32_t matrix, int32_t range, int32_t siting, void* out, int64_t out_bytes, void* stream);
+
+/* ---- planar YUV output ------------------------------------------------------------------------- */
+/* planar_out.py (the specification, bit for bit): `frames` [T, H, W, 3] dense, fp32 or bf16 (x_kind SVR_STORE_FP32 / SVR_STORE_BF16)
+ * -> `out`: per frame the Y plane [H, W], then Cb, then Cr, each [hc, wc] row-major, svr_planar_codes' layout: uint8 samples at 8
+ * bits, uint16 at 10 and 12 -- ffmpeg's yuv4??p / yuv4??p10le / yuv4??p12le rawvideo.
+ *   sub     SVR_PLANAR_420 / _422 / _444;  bits 8, 10 or 12 (n);  matrix SVR_COLOUR_MATRIX_*, the weights of svr_pack_yuv420p10;
+ *           range SVR_COLOUR_RANGE_TV (y0 = 16, ys = 219, cs = 224, each << (n - 8)) / _PC (y0 = 0, ys = cs = 2^n - 1).
+ *   siting  the taps of one chroma sample, indices clamped to the frame, total weight S = Sv * Sh:
+ *           vertical    422 / 444 the row itself; 420 SVR_COLOUR_SITING_CENTER / _LEFT rows 2j, 2j+1, weights 1, 1;
+ *                       420 SVR_PLANAR_SITING_TOPLEFT rows 2j-1, 2j, 2j+1, weights 1, 2, 1
+ *           horizontal  444 the column itself; CENTER columns 2k, 2k+1, weights 1, 1; LEFT / TOPLEFT columns 2k-1, 2k, 2k+1,
+ *                       weights 1, 2, 1
+ *           TOPLEFT is for 420 only; 444 takes LEFT only.
+ * q = rint(clamp(x, 0, 1) * 65535) (NaN -> 0), D = 65535 * 65536, half = 2^(n-1), top = 2^n - 1:
+ *   Y  = y0 + (ys * (wr r + wg g + wb b) + D/2) / D
+ *   Cb = min((S half D + cs * (cb_r sr + cb_g sg + 32768 sb) + S D/2) / (S D), top), Cr likewise: every numerator is positive and
+ *   below 2^62.  (420, 10 bits, CENTER / LEFT) is svr_pack_yuv420p10, bit for bit.
+ * Every argument is checked before the launch, in svr_pack_yuv420p10's order: null pointers, x_kind, sizes below 1 (T * H * W <=
+ * 2^40 pixels), an unknown sub, bits, matrix, range or siting and a siting its sub does not take, misaligned frames (and out at 10 /
+ * 12 bits: 2 bytes), out_bytes other than EXACTLY the planes' size.  One launch on `stream`, no host synchronisation, no workspace. */
+int svr_pack_planar(const void* frames, int32_t x_kind, int32_t T, int32_t H, int32_t W, int32_t sub, int32_t bits, int32_t matrix,
+                    int32_t range, int32_t siting, void* out, int64_t out_bytes, void* stream);
 
 /* ---- interlaced sources ------------------------------------------------------------------------ */
 /* deinterlace.py (the specification, bit for bit): `packed` T woven frames in one of the SVR_UNPACK_* formats (same layouts and

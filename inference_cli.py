@@ -547,6 +547,34 @@ def route_planar(info: dict, colour: Optional[dict] = None, fields=None):
     return pix, sub, bits, matrix, range_, ("topleft" if topleft else "left")
 
 
+def _planar_out():
+    import importlib
+    return importlib.import_module(f"{PKG}.planar_out")
+
+
+# source pix_fmt -> (subsampling, bits): PLANAR_420's and PLANAR_SOURCES' names
+SOURCE_PLANES = {**{pix: ("420", 10 if "10" in fmt else 8) for pix, (_, fmt, _r) in PLANAR_420.items()},
+                 **{pix: (sub, bits) for pix, (sub, bits, _r) in PLANAR_SOURCES.items()}}
+
+
+def route_output(info: Optional[dict], colour: Optional[dict], video_backend: str = "ffmpeg", ten_bit: bool = False):
+    """-> the (sub, bits, matrix, range_, siting) an mp4 is written as through planar_out.pack_planar (FFmpegWriter's ``planes``), or
+    None: the writer packs as it always did.  None while planar_out.ENABLED is off (it ships off), for a backend
+    other than ffmpeg and for a bt2020c source (output_colour's warning stands; today's route).  sub: the source's own subsampling
+    (SOURCE_PLANES; any other name, and a source not read through ffprobe, "420").  bits: 8 without --10bit; with it 12 for a 12-bit
+    source, else 10.  matrix / range: output_colour's decision -- bt2020 tv for an HDR / BT.2020 source with --10bit, bt709 tv
+    otherwise.  siting: "topleft" for 4:2:0 from a source whose chroma_location says so, else "left" (what an untold decoder
+    assumes and planar.py inverts)."""
+    if not _planar_out().ENABLED or video_backend != "ffmpeg" or (colour or {}).get("color_space") == "bt2020c":
+        return None
+    sub, source_bits = SOURCE_PLANES.get((info or {}).get("pix_fmt") or "", ("420", 8))
+    bits = 8 if not ten_bit else 12 if source_bits == 12 else 10
+    hdr = output_colour(colour, video_backend, ten_bit)[0]
+    matrix, range_ = (hdr["matrix"], hdr["range_"]) if hdr else ("bt709", "tv")
+    topleft = sub == "420" and (colour or {}).get("chroma_location") == "topleft"
+    return sub, bits, matrix, range_, ("topleft" if topleft else "left")
+
+
 class FrameSource:
     """Video -> fp32 chunks on ``device``, the counterpart of FrameSink.  One ffmpeg child decodes every frame exactly once, in
     order (``-f rawvideo`` carries no timestamps, so ffmpeg neither drops nor duplicates frames), at the depth route_input()
@@ -868,15 +896,31 @@ class FFmpegWriter:
     tagged bt2020nc, the dictionary's primaries and transfer, tv range and that chroma location.  ``exe``: the executable (find_ffmpeg(), resolved before any GPU work; a test passes its own).  ``fps``: a float or a
     Fraction (passed on as num/den).  ``audio``: (source path, offset in seconds) -- the source as a second input whose audio
     stream, where it has one, is copied (no re-encoding: a codec the container refuses is ffmpeg's own message); None: the command
-    without it, as it always was."""
+    without it, as it always was.  ``planes`` (route_output's (sub, bits, matrix, range_, siting); None: everything above, byte for
+    byte): FrameSink hands over planar_out.pack_planar's planes, the raw input and the output are both planar_out.pix_fmt(sub, bits)
+    (libx264 at 8 bits, libx265 at 10 and 12), nothing is left to a scale filter, and the matrix, range, the primaries and transfer
+    (``colour``'s, else bt709) and, for 4:2:0 and 4:2:2, the chroma location are tagged on both sides of the raw input."""
     alpha = False
+    MATRIX_TAGS = {"bt709": "bt709", "bt601": "smpte170m", "bt2020": "bt2020nc"}
 
-    def __init__(self, exe: str, path: str, fps, ten_bit: bool = False, audio=None, colour=None):
+    def __init__(self, exe: str, path: str, fps, ten_bit: bool = False, audio=None, colour=None, planes=None):
         self.exe, self.path, self.fps, self.ten_bit, self.audio = exe, path, fps, ten_bit, audio
         self.fmt = "yuv420p10" if ten_bit else "bgr8"
         self.colour = colour if ten_bit else None
         self.pack = (self.colour["matrix"], self.colour["range_"], self.colour["siting"]) if self.colour else None
+        self.planes = tuple(planes) if planes is not None else None
         self.proc, self.errlog = None, None
+
+    def planes_command(self, height, width, rate, second, mux):
+        sub, bits, matrix, range_, siting = self.planes
+        pix = _planar_out().pix_fmt(sub, bits)
+        primaries, trc = (self.colour["primaries"], self.colour["trc"]) if self.colour else ("bt709", "bt709")
+        tags = ["-colorspace", self.MATRIX_TAGS[matrix], "-color_primaries", primaries, "-color_trc", trc, "-color_range", range_]
+        if sub != "444":
+            tags += ["-chroma_sample_location", siting]
+        return ([self.exe, "-y", "-loglevel", "error", "-f", "rawvideo", "-pix_fmt", pix, "-s", f"{width}x{height}", "-r", rate]
+                + tags + ["-i", "-"] + second + mux
+                + ["-c:v", "libx264" if bits == 8 else "libx265", "-pix_fmt", pix, "-preset", "medium", "-crf", "12"] + tags + [self.path])
 
     def command(self, height, width):
         raw, codec, pix = ("yuv420p10le", "libx265", "yuv420p10le") if self.ten_bit else ("bgr24", "libx264", "yuv420p")
@@ -893,6 +937,8 @@ class FFmpegWriter:
             src, offset = self.audio
             second = (["-ss", f"{float(offset):.6f}"] if offset > 0 else []) + ["-i", src]
             mux = ["-map", "0:v:0", "-map", "1:a?", "-c:a", "copy", "-shortest"]
+        if self.planes is not None:
+            return self.planes_command(height, width, rate, second, mux)
         return ([self.exe, "-y", "-loglevel", "error", "-f", "rawvideo", "-pix_fmt", raw, "-s", f"{width}x{height}", "-r", rate]
                 + (tags if self.ten_bit else []) + ["-i", "-"] + second + convert + mux
                 + ["-c:v", codec, "-pix_fmt", pix, "-preset", "medium", "-crf", "12"] + tags + [self.path])
@@ -948,7 +994,8 @@ class TensorWriter:
 
 class FrameSink:
     """Frames -> writer.  ``put(frames)`` narrows a chunk to the writer's format -- or, for a writer whose ``pack`` attribute names
-    a (matrix, range_, siting), to those yuv420p10 planes (frameio.pack_yuv420p10) -- where the frames live (``ops.pack_frames`` on the
+    a (matrix, range_, siting), to those yuv420p10 planes (frameio.pack_yuv420p10), or, for one whose ``planes`` attribute names a
+    (sub, bits, matrix, range_, siting), to those planar YUV planes (planar_out.pack_planar) -- where the frames live (``ops.pack_frames`` on the
     device, ``ops`` being the resident runner's backend; frameio's torch statement for a backend without one and for host frames),
     copies the result into one of TWO host buffers (pinned for device frames) and hands it to ONE writer thread through a queue of depth 2, so the encoder works while the next chunk computes.  The thread makes no GPU
     call.  An exception of the writer is raised in the caller's thread at the next put() or at close().
@@ -1038,7 +1085,10 @@ class FrameSink:
             self.work.put((None, q, height, width))
             return
         how, ops = getattr(self.writer, "pack", None), self.ops if frames.is_cuda else None
-        if how is None:
+        planes = getattr(self.writer, "planes", None)
+        if planes is not None:                                   # planar_out's planes: (sub, bits, matrix, range_, siting)
+            packed = _planar_out().pack_planar(frames.contiguous(), *planes, ops=ops)
+        elif how is None:
             packed = frameio.pack_frames(frames.contiguous(), self.writer.fmt, ops)
         else:
             packed = frameio.pack_yuv420p10(frames.contiguous(), *how, ops=ops)
@@ -1065,13 +1115,13 @@ class FrameSink:
 
 
 def open_writer(fmt: str, path: str, fps: float, single: bool = False, video_backend: str = "opencv", ten_bit: bool = False,
-                ffmpeg: Optional[str] = None, audio=None, colour=None, depth: int = 8):
+                ffmpeg: Optional[str] = None, audio=None, colour=None, depth: int = 8, planes=None):
     if fmt == "pt":
         return TensorWriter(path)
     if fmt == "png":
         return PngWriter(path, single, depth, runs=_pngenc().RUNS)
     if video_backend == "ffmpeg":
-        return FFmpegWriter(ffmpeg or find_ffmpeg(), path, fps, ten_bit, audio, colour)
+        return FFmpegWriter(ffmpeg or find_ffmpeg(), path, fps, ten_bit, audio, colour, planes)
     return OpenCVWriter(path, fps)
 
 
@@ -1246,6 +1296,9 @@ def main(argv: Optional[List[str]] = None) -> int:
                 print(warning, file=sys.stderr)
             if out_colour is not None:
                 job_kw["colour"] = out_colour
+            planes = route_output(info, colour, args.video_backend, writer_kw["ten_bit"])      # (None as shipped: DESIGN.md 7.3l)
+            if planes is not None:
+                job_kw["planes"] = planes
         source = lambda n: FrameSource(ffmpeg, inp, info, n, args.skip_first_frames, args.load_cap, ops, eng[0].dit.device, fields,
                                        colour=colour)
         if args.chunk_size > 0 and ext_of(inp) not in IMAGE_EXT:
